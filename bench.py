@@ -7,11 +7,16 @@ barrier + torch.cuda.synchronize() on both sides, MAX over ranks, rank 0 prints 
 
 `value` is the contract measurement to the letter: W warm-up steps, then K timed steps, on the device as the setup left it.  An MI355X that idled for
 ~10 ms is back at its idle clocks and needs tens of milliseconds of load to reach its sustained ones -- a timed region of 20 steps (0.6 ms) sees 29 us per
-step, a rollout loop that has been running for 50 ms sees 26.3 -- so bench.py ALSO reports what a running rollout loop sees: after `value` is taken it runs
---condition-ms (default 200) of the same step launches and then W + K steps again: `value_sustained` / `ms_per_step_sustained` at the top level
+step, a rollout loop that has been running for 50 ms sees 26.3 -- so bench.py --full ALSO reports what a running rollout loop sees: after `value` is taken it
+runs --condition-ms (default 200) of the same step launches and then W + K steps again: `value_sustained` / `ms_per_step_sustained` at the top level
 (`warmup_effective_steps_sustained` says how many steps preceded that timed region), details in config.sustained.  --condition-ms 0 skips it.  Rounds
 1-3 reported the contract figure as `value`, round 4 the sustained one (with the contract figure in config.cold_start); from round 5 on `value` is the
 contract figure again and stays comparable with rounds 1-3 and with the driver's clock.
+
+A plain run (no --full) does only what `value` needs: setup, W warm-up steps, K timed steps, --dump-outputs DIR if given, the JSON line.  --full adds,
+after the headline, the sustained-clock figure, config.per_step_launch, config.lines (the other single-GPU BASELINE configurations) and cpu_baseline.
+--dump-outputs DIR writes what the last timed step computed (env state, observation, reward, done, the step's rollout record row) as DIR/<name>.npy;
+the inputs are seeded, so two builds run with the same arguments can be compared output for output.
 
 A "step" is one pass of the hot path over one batch of synthetic input: agents x envs stepped once by the fused kernel, which also writes
 the rollout record of the step (observation incl. the terminal one, reward, done -- the reference's step_and_maybe_reset keeps both the
@@ -442,6 +447,24 @@ class GpuRun:
         return (sum(int(e.buffer(capi.BUF_COL_FLAGS)[..., 3].sum().item()) for e in self.envs),
                 sum(int(e.buffer(capi.BUF_COL_FLAGS)[..., 1:3].sum().item()) for e in self.envs))
 
+    def outputs(self):
+        """{name: device tensor with the envs of this GPU first} -- what a caller of the timed path holds after its last step: the env buffers
+        (state, observation, reward, done) and, with a rollout record, that step's record row (observation incl. the terminal one, reward, done);
+        --cbf-qp adds the safe actions of the QP filter."""
+        from sigmarl_amd import capi
+        from sigmarl_amd.shard import unpack_slab
+        torch = self.torch
+        cat = lambda ts: torch.cat(ts, 0) if len(ts) > 1 else ts[0]  # noqa: E731
+        out = {name: cat([e.buffer(which) for e in self.envs]) for name, which in
+               (("state", capi.BUF_STATE), ("obs", capi.BUF_OBS), ("reward", capi.BUF_REWARD), ("done", capi.BUF_DONE))}
+        if self.gather is not None and self.gather.completed:
+            k, valid = self.gather.completed[-1]
+            obs, reward, done = unpack_slab(self.gather.chunks[k][valid - 1], self.N, self.D)
+            out.update(record_obs=obs, record_reward=reward, record_done=done)
+        if self.safe_bufs:
+            out["actions_safe"] = cat(self.safe_bufs)
+        return out
+
     def close(self):
         for e in self.envs:
             e.close()
@@ -487,6 +510,30 @@ class SurfaceRun:
     episodes_reset = GpuRun.episodes_reset
     agent_requests = GpuRun.agent_requests
     close = GpuRun.close
+    safe_bufs = ()
+    outputs = GpuRun.outputs
+
+
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays, n_envs):
+    """--dump-outputs: every array (envs on axis 0) as <out_dir>/<name>.npy, float64 stays float64, everything else becomes float32.  Above
+    DUMP_MAX_BYTES in all, a fixed sample of envs (seeded, sorted) is written instead, and its indices as env_index.npy."""
+    import numpy as np
+
+    host = {k: v.detach().cpu().numpy() for k, v in arrays.items()}
+    host = {k: v if v.dtype == np.float64 else v.astype(np.float32) for k, v in host.items()}
+    total = sum(v.nbytes for v in host.values())
+    budget = DUMP_MAX_BYTES - 1024 * (len(host) + 1)  # (room for the .npy headers)
+    if total > budget:
+        keep = max(1, int(n_envs * budget // (total + 8 * n_envs)))
+        idx = np.sort(np.random.default_rng(0).choice(n_envs, keep, replace=False))
+        host = {k: v[idx] for k, v in host.items()}
+        host["env_index"] = idx.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for k, v in host.items():
+        np.save(os.path.join(out_dir, k + ".npy"), np.ascontiguousarray(v))
 
 
 def cbf_valu_roofline(kernel_name, N, Bs, kernel_ms, hbm_roofline):
@@ -734,22 +781,28 @@ def main():
     ap.add_argument("--surface", action="store_true", help="time the DROP-IN SURFACE instead of the C-ABI: ScenarioRoadTraffic driven the way vmas' Environment drives "
                     "a scenario (tests/vmas_env_shim.py: set actions per agent, world.step(), reward / observation / info per agent -- every returned tensor cloned --, "
                     "done(), device-side resets) -- what sigmarl/mappo_cavs.py:166-184 sees per env.step()")
-    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="budget of the cpu_baseline leg (0 disables it)")
+    ap.add_argument("--full", action="store_true", help="after the headline, also measure what it does not need: the sustained-clock figure (--condition-ms), "
+                    "the one-launch-per-step comparison (config.per_step_launch), the other BASELINE configurations (config.lines) and the CPU baseline "
+                    "(--cpu-seconds).  Without it a run sets up, warms up, times --steps steps and prints the headline line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps: what the timed path computed in its last step (env state, "
+                    "observation, reward, done, that step's rollout record row; the safe actions with --cbf-qp) as DIR/<name>.npy in float32 / float64, envs on "
+                    "axis 0 (rank 0's envs); above 64 MB in all a fixed seeded sample of envs, its indices in env_index.npy")
+    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="--full: budget of the cpu_baseline leg (0 disables it)")
     ap.add_argument("--sweep", action="store_true", help="also time the metric's batch sweep (envs per GPU in --sweep-envs, same agents / map) and "
                     "report it in `sweep`; the headline stays --envs-per-gpu")
     ap.add_argument("--sweep-envs", default="256,512,1024,2048,4096,8192,16384,32768")
     ap.add_argument("--sweep-steps", type=int, default=64)
     ap.add_argument("--chunk", type=int, default=0, help="steps per launch (sigmaenv_step_autoreset_n); 0 = the largest divisor of --steps up to 32; 1 = one launch "
                     "per step (sigmaenv_step_autoreset); modes with a launch between the steps (--policy, --cbf, --cbf-qp, --separate-reset) always use 1")
-    ap.add_argument("--condition-ms", type=float, default=200.0, help="after `value` (the contract's W warm-up + K timed steps on the device as the setup left it) is taken: this "
+    ap.add_argument("--condition-ms", type=float, default=200.0, help="--full: after `value` (the contract's W warm-up + K timed steps on the device as the setup left it) is taken: this "
                     "many milliseconds of the SAME step launches, then W + K steps again -- the GPU's sustained clocks, what a running rollout loop sees (an MI355X that idled "
                     "for 10 ms is back at its idle clocks, and a launch of 20 steps -- 0.6 ms -- is over before they have risen: 29 us per step against 26.5 sustained).  "
                     "Reported as value_sustained / config.sustained; 0 skips it")
     ap.add_argument("--no-one-stream", "--no-compare", dest="no_compare", action="store_true",
-                    help="skip the additional per-step-launch measurement reported in config.per_step_launch")
+                    help="--full: skip the additional per-step-launch measurement reported in config.per_step_launch")
     ap.add_argument("--emulate-ranks", type=int, default=0, help="after the headline: BASELINE config 3's workload on this ONE GPU -- R shards of --envs-per-gpu envs "
                     "(rank r = envs [r B, (r + 1) B) of the batch), each timed like the headline with its own rollout exchange; reported in config.emulated_ranks")
-    ap.add_argument("--no-lines", dest="lines", action="store_false", help="skip config.lines (--no-compare skips them too: profile runs must hold the headline's launches only): the other single-GPU BASELINE configurations (config 4, config 5, mtv, the "
+    ap.add_argument("--no-lines", dest="lines", action="store_false", help="--full: skip config.lines (--no-compare skips them too: profile runs must hold the headline's launches only): the other single-GPU BASELINE configurations (config 4, config 5, mtv, the "
                     "reference's defaults), each timed for a few seconds AFTER the headline's regions and appended to the headline's JSON line")
     ap.add_argument("--no-reset", action="store_true", help="diagnostic: leave finished envs un-reset")
     ap.add_argument("--separate-reset", action="store_true", help="two launches per step (sigmaenv_step; sigmaenv_auto_reset) instead of the fused one")
@@ -831,8 +884,10 @@ def main():
     run.kernel_timing()  # drops the warm-up launches' brackets
     elapsed = timed(run, args.steps, args.warmup, use_dist, dist, torch, device)
     ktimes = run.kernel_timing()
+    if args.dump_outputs and rank == 0:  # the last timed step's outputs: the same with and without --full
+        dump_outputs(args.dump_outputs, run.outputs(), B)
     sustained = None
-    if args.condition_ms > 0 and not args.surface:
+    if args.full and args.condition_ms > 0 and not args.surface:
         # (2) what a running rollout loop sees: the same launches for --condition-ms (a step count derived from the MAX-reduced time of (1): equal on every rank, so
         # that the ranks issue the same number of chunk exchanges), then W + K steps again
         n_cond = condition_device(run, torch, args.condition_ms, elapsed / args.steps, T)
@@ -1009,7 +1064,7 @@ def main():
                                   "(fp16 / bf16 2.5 PFLOP/s, fp32 157.3 TFLOP/s); fp32_equivalent_tflops counts every fp32 product once"})
         out["roofline"].update(cbf_valu_roofline(_capi.KERNEL_NAMES[dom], N, Bs, dms, out["roofline"]))
     run.close()
-    if T > 1 and not args.no_compare and world == 1 and not use_dist:
+    if args.full and T > 1 and not args.no_compare and world == 1 and not use_dist:
         # the same workload with ONE launch per step (two env shards on two streams, the round-2 form): what the step loop inside the kernel buys
         r1 = GpuRun(args, device, B, world, rank, T=1)
         condition_device(r1, torch, args.condition_ms, step_s)
@@ -1026,7 +1081,7 @@ def main():
         out["roofline"]["frac_full_outputs_note"] = ("algorithmic bytes x config.per_step_launch.value / 8 TB/s: one launch per step materialises every per-step output; "
                                                      "`frac` credits the T-step launch with stores it elides (see traffic_over_algorithmic / frac_measured)")
         r1.close()
-    if args.lines and not args.no_compare and world == 1 and not use_dist and plain and args.scenario == "cpm_entire" and N == 16 and not args.param and not args.defaults and args.distance == "c2c":
+    if args.full and args.lines and not args.no_compare and world == 1 and not use_dist and plain and args.scenario == "cpm_entire" and N == 16 and not args.param and not args.defaults and args.distance == "c2c":
         out["config"]["lines"] = baseline_lines(args, device, torch, dist, step_s)
     if args.emulate_ranks > 1 and world == 1:
         # BASELINE config 3 (16 agents x 32768 envs over 8 GPUs) on the one GPU of this box: rank r's shard -- envs [r B, (r + 1) B) of the batch, the
@@ -1059,7 +1114,7 @@ def main():
                           "env_shards_per_gpu": r.S, "steps_per_launch": Tx, "roofline_frac": bytes_per * (N * Bx * args.sweep_steps / el) / 1e9 / HBM_PEAK_GBPS})
             r.close()
         out["sweep"] = sweep
-    if rank == 0 and args.cpu_seconds > 0 and world == 1:
+    if args.full and rank == 0 and args.cpu_seconds > 0 and world == 1:
         out["cpu_baseline"] = cpu_baseline(args, B, args.cpu_seconds)
     if use_dist:
         dist.destroy_process_group()

@@ -5,6 +5,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -21,7 +22,7 @@ def _run(*extra):
 
 
 def test_default_line_follows_the_contract():
-    d = _run("--cpu-seconds", "1.5")
+    d = _run("--full", "--cpu-seconds", "1.5")
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data", "config",
               "roofline", "cpu_baseline"):
         assert k in d, k
@@ -77,8 +78,34 @@ def test_default_line_follows_the_contract():
 
 
 def test_without_conditioning_there_is_no_sustained_figure():
-    d = _run("--cpu-seconds", "0", "--no-compare", "--condition-ms", "0", "--no-lines")
+    d = _run("--full", "--cpu-seconds", "0", "--no-compare", "--condition-ms", "0", "--no-lines")
     assert "value_sustained" not in d and "sustained" not in d["config"] and d["warmup_effective_steps"] == 4 and "lines" not in d["config"]
+
+
+def test_plain_run_times_the_headline_only_and_dumps_its_last_step(tmp_path):
+    """Without --full a run holds the headline and nothing else (no sustained figure, per-step-launch comparison, config.lines or CPU baseline);
+    --dump-outputs writes the last timed step's outputs in float32, and the same arguments give the same inputs, hence the same outputs."""
+    dumps = []
+    for k in range(2):
+        d = _run("--dump-outputs", str(tmp_path / f"run{k}"))
+        assert d["steps"] == 24 and d["warmup"] == 4 and d["warmup_effective_steps"] == 4 and d["ms_per_step"] > 0
+        assert abs(d["value"] - 16 * 4096 / (d["ms_per_step"] * 1e-3)) <= 1e-6 * d["value"]
+        assert d["metric"].endswith("(open loop, 24 steps per launch)") and d["config"]["steps_per_launch"] == 24
+        for extra in ("value_sustained", "ms_per_step_sustained", "cpu_baseline"):
+            assert extra not in d, extra
+        for extra in ("sustained", "per_step_launch", "lines"):
+            assert extra not in d["config"], extra
+        out = {f[:-4]: np.load(tmp_path / f"run{k}" / f) for f in sorted(os.listdir(tmp_path / f"run{k}"))}
+        dumps.append(out)
+    D = 32 + (d["roofline"]["algorithmic_bytes_per_agent_env_step"] - 375) // 4  # (SURVEY.md 8d: 4 bytes per observation entry)
+    shapes = {"state": (4096, 16, 8), "obs": (4096, 16, D), "reward": (4096, 16), "done": (4096,), "record_obs": (4096, 16, D), "record_reward": (4096, 16),
+              "record_done": (4096,)}
+    a, b = dumps
+    assert sorted(a) == sorted(shapes) and sum(v.nbytes for v in a.values()) <= 64 << 20
+    for k, shape in shapes.items():
+        assert a[k].dtype == np.float32 and a[k].shape == shape and np.isfinite(a[k]).all(), k
+        assert np.array_equal(a[k], b[k]), k
+    assert set(np.unique(a["done"])) <= {0.0, 1.0} and np.abs(a["obs"]).max() > 0
 
 
 def test_config4_and_qp_lines_name_their_workload():

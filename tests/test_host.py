@@ -376,6 +376,35 @@ def test_bench_device_conditioning_is_a_rank_independent_step_count():
     assert bench.condition_device(FakeRun(), FakeTorch, 0.0, 29e-6, 32) == 0
 
 
+def test_bench_dump_outputs_writes_float_arrays_and_samples_large_ones(tmp_path):
+    """bench.py --dump-outputs: one DIR/<name>.npy per array in float32 (float64 kept), the values unchanged; above 64 MB in all a fixed, seeded sample of envs
+    (the same rows of every array, indices in env_index.npy) that fits."""
+    import importlib.util
+
+    import torch
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    g = torch.Generator().manual_seed(0)
+    small = {"obs": torch.rand((8, 4, 3), generator=g), "done": torch.tensor([0, 1, 0, 0, 1, 1, 0, 1], dtype=torch.uint8),
+             "margin": torch.rand((8, 2), generator=g, dtype=torch.float64)}
+    bench.dump_outputs(str(tmp_path / "small"), small, 8)
+    assert sorted(os.listdir(tmp_path / "small")) == ["done.npy", "margin.npy", "obs.npy"]
+    for k, v in small.items():
+        a = np.load(tmp_path / "small" / (k + ".npy"))
+        assert a.dtype == (np.float64 if k == "margin" else np.float32) and np.array_equal(a, v.numpy().astype(a.dtype))
+    B = 4096
+    big = {"obs": torch.arange(B * 4096, dtype=torch.float32).reshape(B, 4096), "reward": torch.arange(B, dtype=torch.float32)}  # 64 MB + 16 KB
+    for d in ("big1", "big2"):
+        bench.dump_outputs(str(tmp_path / d), big, B)
+    idx = np.load(tmp_path / "big1" / "env_index.npy")
+    assert idx.dtype == np.float64 and np.all(np.diff(idx) > 0) and 0 < len(idx) < B
+    assert np.array_equal(idx, np.load(tmp_path / "big2" / "env_index.npy"))
+    obs, rew = np.load(tmp_path / "big1" / "obs.npy"), np.load(tmp_path / "big1" / "reward.npy")
+    assert np.array_equal(rew, idx.astype(np.float32)) and np.array_equal(obs[:, 0], idx.astype(np.float32) * 4096)
+    assert sum(os.path.getsize(tmp_path / "big1" / f) for f in os.listdir(tmp_path / "big1")) <= 64 << 20
+
+
 @pytest.mark.parametrize("tag,testing", [("train", False), ("test", True)])
 def test_device_sampler_specification_matches_the_reference_distribution(tag, testing):
     """The counter-based reset sampler (oracle side of the specification the HIP kernels share) draws (path, point, speed) with the marginals of

@@ -33,12 +33,33 @@ def test_compiled_table_equals_reference_parser_output(scen):
     assert mt.n_paths == ref["center"].shape[0] and sum(mt.list_count.values()) == mt.n_paths
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/sigmarl/scenarios/assets/maps"), reason="raw .osm files only exist next to the reference")
+def _josm_osm_text(src):
+    """The node / way lists of a MapSource as a JOSM .osm document, laid out as the scenario files are: <bounds>, nodes with action / visible
+    attributes, ways with <nd ref> lists, a `lanes` tag among other tags (none on an ignored way).  Coordinates in repr form (exact round trip)."""
+    lines = ["<?xml version='1.0' encoding='UTF-8'?>", "<osm version='0.6' generator='JOSM'>"]
+    lat, lon = src.node_latlon[:, 0], src.node_latlon[:, 1]
+    lines.append(f"  <bounds minlat='{lat.min()!r}' minlon='{lon.min()!r}' maxlat='{lat.max()!r}' maxlon='{lon.max()!r}' origin='JOSM' />")
+    for i, (a, b) in zip(src.node_id, src.node_latlon):
+        lines.append(f"  <node id='{int(i)}' action='modify' visible='true' lat='{float(a)!r}' lon='{float(b)!r}' />")
+    for w, lanes in enumerate(src.way_lanes):
+        lines.append(f"  <way id='{-100000 - w}' action='modify' visible='true'>")
+        lines.extend(f"    <nd ref='{int(r)}' />" for r in src.way_nodes[src.way_off[w]:src.way_off[w + 1]])
+        if lanes >= 0:
+            lines.append("    <tag k='highway' v='road' />")
+            lines.append(f"    <tag k='lanes' v='{int(lanes)}' />")
+        lines.append("  </way>")
+    lines.append("</osm>")
+    return "\n".join(lines) + "\n"
+
+
 @pytest.mark.parametrize("scen", OSM_SCENARIOS[:4])
-def test_osm_reader_matches_the_extracted_sources(scen):
+def test_osm_reader_matches_the_extracted_sources(scen, tmp_path):
+    """read_osm on a full-size scenario map written in the JOSM layout of the scenario files returns the shipped node / way lists bit for bit."""
     spec = mapc.scenario_specs()[scen]
-    raw = mapc.read_osm(os.path.join("/root/reference/sigmarl/scenarios/assets/maps", spec["map_path"]))
     src = mapc.load_source(scen)
+    p = tmp_path / spec["map_path"]
+    p.write_text(_josm_osm_text(src))
+    raw = mapc.read_osm(str(p))
     for f in ("node_id", "node_latlon", "way_lanes", "way_off", "way_nodes"):
         assert np.array_equal(getattr(raw, f), getattr(src, f)), f
 
@@ -78,10 +99,38 @@ def test_hand_made_map(tmp_path):
     assert abs(float(t["world_x_dim"]) - ((4 + m + w / 2) + m)) < 1e-4  # max x (right boundary of the vertical leg) + min x
 
 
-@pytest.mark.skipif(not os.path.exists("/root/reference/sigmarl/scenarios/assets/maps/cpm.xml"), reason="cpm.xml only exists next to the reference")
-def test_commonroad_reader_matches_the_extracted_source():
-    raw = mapc.read_commonroad_xml("/root/reference/sigmarl/scenarios/assets/maps/cpm.xml")
+def _commonroad_xml_text(src):
+    """The bound points of a LaneletSource as a CommonRoad XML document: a <location> element first, every <lanelet> with its <leftBound> /
+    <rightBound> point lists (each with a <lineMarking>), predecessor / successor / adjacency / type children, and an <intersection> after the
+    lanelets -- the elements the reader must pass over.  Coordinates in repr form (exact round trip)."""
+    lines = ["<?xml version='1.0' encoding='UTF-8'?>", '<commonRoad timeStepSize="0.1" commonRoadVersion="2020a" author="" affiliation="" source="" benchmarkID="">',
+             "  <location><geoNameId>-999</geoNameId><gpsLatitude>0.0</gpsLatitude><gpsLongitude>0.0</gpsLongitude></location>"]
+    n = len(src.lanelet_id)
+    for i, lid in enumerate(src.lanelet_id):
+        lines.append(f'  <lanelet id="{int(lid)}">')
+        for tag, pts, off in (("leftBound", src.left, src.left_off), ("rightBound", src.right, src.right_off)):
+            lines.append(f"    <{tag}>")
+            lines.extend(f"      <point><x>{float(x)!r}</x><y>{float(y)!r}</y></point>" for x, y in pts[off[i]:off[i + 1]])
+            lines.append(f"      <lineMarking>{'dashed' if tag == 'leftBound' else 'solid'}</lineMarking>")
+            lines.append(f"    </{tag}>")
+        if i > 0:
+            lines.append(f'    <predecessor ref="{int(src.lanelet_id[i - 1])}"/>')
+        if i + 1 < n:
+            lines.append(f'    <successor ref="{int(src.lanelet_id[i + 1])}"/>')
+            lines.append(f'    <adjacentLeft ref="{int(src.lanelet_id[i + 1])}" drivingDir="same"/>')
+        lines.append("    <laneletType>urban</laneletType>")
+        lines.append("  </lanelet>")
+    lines.append(f'  <intersection id="{100000}"><incoming id="{100001}"><incomingLanelet ref="{int(src.lanelet_id[0])}"/></incoming></intersection>')
+    lines.append("</commonRoad>")
+    return "\n".join(lines) + "\n"
+
+
+def test_commonroad_reader_matches_the_extracted_source(tmp_path):
+    """read_commonroad_xml on the whole CPM map written as a CommonRoad XML document returns the shipped bound point lists bit for bit."""
     src = mapc.load_lanelet_source("cpm")
+    p = tmp_path / "cpm.xml"
+    p.write_text(_commonroad_xml_text(src))
+    raw = mapc.read_commonroad_xml(str(p))
     for f in ("lanelet_id", "left_off", "right_off", "left", "right"):
         assert np.array_equal(getattr(raw, f), getattr(src, f)), f
 

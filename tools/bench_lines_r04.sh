@@ -2,7 +2,7 @@
 # The measurement lines SURVEY.md section 8(d) names beside the headline (run on the GPU box): mtv, the reference's own defaults, the drop-in surface, and
 # the non-default observation rows inside the T-step launch.  Usage: tools/bench_lines_r04.sh <tag>
 tag=$1; R=$GRAFT_REPO_ROOT; out=$R/gpurun_out/$tag; mkdir -p $out
-B="python $R/bench.py --steps 256 --warmup 32"
+B="python $R/bench.py --full --steps 256 --warmup 32"
 $B > $out/bench.json 2> $out/bench.err
 $B --distance mtv > $out/bench_mtv.json 2>> $out/bench.err
 $B --defaults > $out/bench_reference_defaults.json 2>> $out/bench.err

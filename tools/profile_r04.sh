@@ -5,7 +5,7 @@ tag=$1
 R=$GRAFT_REPO_ROOT
 out=$R/gpurun_out/$tag; mkdir -p $out
 cd /tmp && export TMPDIR=/tmp
-B="python $R/bench.py"
+B="python $R/bench.py --full"
 trace() { name=$1; shift; rocprofv3 --kernel-trace --stats --output-format csv -d $out/trace_$name -o t -- $B "$@" > $out/${name}_bench_under_rocprof.json 2> $out/trace_$name.err; cp $(ls $out/trace_$name/*kernel_stats.csv | head -1) $out/${name}_kernel_stats.csv; }
 pmc() { name=$1; shift; ctrs=$1; shift; rocprofv3 --pmc $ctrs --output-format csv -d $out/pmc_$name -o p -- $B "$@" > /dev/null 2> $out/pmc_$name.err; }
 SQ1="SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_WAVE_CYCLES SQ_BUSY_CYCLES"

@@ -4,7 +4,7 @@
 tag=$1
 R=$GRAFT_REPO_ROOT
 out=$R/gpurun_out/$tag; mkdir -p $out
-B="python $R/bench.py"
+B="python $R/bench.py --full"
 cd $R
 $B --policy --cpu-seconds 8 > $out/bench_policy_fp32_split.json 2> $out/bench.err
 $B --policy --policy-mode exact --cpu-seconds 0 > $out/bench_policy_fp32_exact.json 2>> $out/bench.err
