@@ -351,7 +351,9 @@ int sigmaenv_actor_forward(sigmaenv_t* h, sigmaenv_actor_t* a, const float* obs,
  *   critic  sigmarl/modules/optimization_module.py:16-32      dims = {n_agents * obs_dim, 256, 256, 256, 1}, one row per env (MAPPO, centralised:
  *           the observations of all agents of the env concatenated -- exactly a row of SIGMAENV_BUF_OBS viewed as [B, N * D]; the one output
  *           is the state value of every agent of the env)
- * weights[l]: torch.nn.Linear layout [dims[l+1], dims[l]] row-major fp32 (host pointers), biases[l]: [dims[l+1]].
+ * weights[l]: torch.nn.Linear layout [dims[l+1], dims[l]] row-major fp32 (host pointers), biases[l]: [dims[l+1]].  2 to 4 layers; dims[0] (the input width)
+ * 1 .. 4096, every hidden width 256, dims[n_layers] 1 .. 32; anything else: SIGMAENV_EINVAL.
+ * forward: in / out device f32 [rows, dims[0]] / [rows, dims[n_layers]]; `in` must be 16-byte aligned (the rows are read with 16-byte loads).
  * sigmaenv_actor_forward_f32 = this MLP + the distribution head of sigmaenv_actor_forward (same outputs); scratch: device f32 [B * N * 4]. */
 typedef struct sigmaenv_mlp32 sigmaenv_mlp32_t;
 /* How the products of these fp32 networks are formed.  Both modes accumulate in fp32 and are held to torch.nn (fp32, CPU) within 1e-5 by the test-suite.
@@ -359,7 +361,8 @@ typedef struct sigmaenv_mlp32 sigmaenv_mlp32_t;
  *   SPLIT  (default) every fp32 operand as hi + lo, two fp16 numbers (22 significant bits, scaled so that lo is a normal number); w x = w_hi x_hi + w_hi x_lo
  *          + w_lo x_hi on v_mfma_f32_32x32x16_f16 with exact products: 3/16 of the matrix time.  Measured against fp64 on K = 256 dot products: 3.6e-7 against
  *          6.4e-7 for the exact chain (tools/mfma_probe/probe_f16_split.hip).  Ranges: |weight| < 255 (else the handle stays EXACT and set_mode(SPLIT)
- *          returns SIGMAENV_EINVAL), |input| < 4094 (an input outside gives inf / nan rows). */
+ *          returns SIGMAENV_EINVAL), |input| < 4094 (an input outside is saturated to +-4094: finite but wrong
+ *          outputs), dims[0] <= 592 (a wider network stays EXACT, as above). */
 #define SIGMAENV_MLP32_EXACT 0
 #define SIGMAENV_MLP32_SPLIT 1
 int sigmaenv_mlp32_set_mode(sigmaenv_mlp32_t* m, int32_t mode);

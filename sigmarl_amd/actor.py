@@ -30,20 +30,23 @@ def make_mlp(obs_dim: int = 32, hidden: int = 256, n_out: int = 4) -> torch.nn.S
 class Mlp32:
     """``sigmaenv_mlp32_*``: a Tanh MLP with hidden width 256 in fp32 on the matrix cores; ``forward(env, x[rows, in_dim]) -> [rows, out_dim]``.
     ``mode``: ``"split"`` (default: every fp32 operand as two fp16 numbers, three exact-product MFMAs per fp32 product, 3/16 of the fp32 matrix time; falls back
-    to exact when a weight is outside +-255) or ``"exact"`` (``v_mfma_f32_32x32x2_f32`` fma chains).  Both are held to torch.nn within 1e-5."""
+    to exact when a weight is outside +-255 or the input is wider than 592) or ``"exact"`` (``v_mfma_f32_32x32x2_f32`` fma chains).  Input widths 1 to 4096.  Both are
+    held to torch.nn in fp64 within the precision class of torch.nn in fp32 (tests/network_check.py)."""
 
     def __init__(self, mlp: torch.nn.Module, lib: capi.Library | None = None, mode: str = "split"):
         if mode not in ("split", "exact"):
             raise ValueError("mode must be 'split' or 'exact'")
         self.mode = mode
-        # A handle belongs to the library that made it, and an env handle to the build of ITS n_points_short_term (libsigmaenv_ns<k>.so): every call
-        # that takes ``env.h`` goes through ``env.lib`` with a network handle created by that same library (one per library, made on first use).
-        self.lib = lib or capi.load_library()
         self._handles = {}
         lin = [m for m in mlp.modules() if isinstance(m, torch.nn.Linear)]
         if not (2 <= len(lin) <= 4) or any(m.out_features != 256 for m in lin[:-1]) or lin[-1].out_features > 32:
             raise ValueError("expected 2-4 Linear layers with hidden width 256 and at most 32 outputs")
         self.in_dim, self.out_dim = lin[0].in_features, lin[-1].out_features
+        if not 1 <= self.in_dim <= 4096:
+            raise ValueError(f"input width {self.in_dim}: sigmaenv_mlp32 takes 1 to 4096 inputs (include/sigmaenv.h)")
+        # A handle belongs to the library that made it, and an env handle to the build of ITS n_points_short_term (libsigmaenv_ns<k>.so): every call
+        # that takes ``env.h`` goes through ``env.lib`` with a network handle created by that same library (one per library, made on first use).
+        self.lib = lib or capi.load_library()
         dims = np.asarray([self.in_dim] + [m.out_features for m in lin], np.int32)
         ws = [np.ascontiguousarray(m.weight.detach().cpu().numpy(), np.float32) for m in lin]
         bs = [np.ascontiguousarray(m.bias.detach().cpu().numpy(), np.float32) for m in lin]
@@ -92,9 +95,13 @@ class Mlp32:
     def forward(self, env: SigmaEnv, x: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
         if not (x.is_cuda and x.dtype == torch.float32 and x.is_contiguous() and x.shape[-1] == self.in_dim):
             raise TypeError(f"input must be a contiguous float32 CUDA tensor [..., {self.in_dim}]")
+        if x.data_ptr() % 16:  # (a view at a storage offset: the kernels read the rows with 16-byte loads, include/sigmaenv.h)
+            x = x.clone()
         rows = x.numel() // self.in_dim
         if out is None:
             out = torch.empty((*x.shape[:-1], self.out_dim), dtype=torch.float32, device=x.device)
+        if rows == 0:
+            return out
         rc = env.lib.mlp32_forward(env.h, self.handle(env.lib), C.c_void_p(x.data_ptr()), rows, C.c_void_p(out.data_ptr()))
         if rc != 0:
             raise RuntimeError(f"sigmaenv_mlp32_forward failed with code {rc}: {env.lib.last_error(env.h).decode()}")

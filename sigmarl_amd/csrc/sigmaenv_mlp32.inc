@@ -27,6 +27,7 @@ typedef float f32x16_t __attribute__((ext_vector_type(16)));
 #define MLP32_ROWS 64
 #define MLP32_MAX_LAYERS 4
 #define MLP32_H 256
+#define MLP32_KC 256  // layer 0's input columns staged in LDS at a time (a wider input is multiplied chunk by chunk: the LDS per workgroup does not grow with it)
 
 struct Mlp32Weights {
   const float* w[MLP32_MAX_LAYERS];  // layer l packed [Fp_l / 32][K_l / 8][2][32][4] (see above; K padded to a multiple of 8, features to 32, zeros)
@@ -103,9 +104,8 @@ __global__ void __launch_bounds__(256, 2) sigmaenv_mlp32_kernel(Mlp32Weights mw,
   }
 #endif
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-  const int KA = mw.K[0] > MLP32_H ? mw.K[0] : MLP32_H;
-  float* x = reinterpret_cast<float*>(smem_raw);                        // [KA / 8][64][2][4]: the activations of the current layer
-  float* part = x + (size_t)KA * MLP32_ROWS;                            // [2][32][32]: partial sums of the output layer's second k half
+  float* x = reinterpret_cast<float*>(smem_raw);                        // [256 / 8][2][64][4]: the activations of the current layer (layer 0: a chunk of its inputs)
+  float* part = x + (size_t)MLP32_H * MLP32_ROWS;                       // [2][32][32]: partial sums of the output layer's second k half
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, m = lane & 31, h = lane >> 5;
   const int row0 = blockIdx.x * MLP32_ROWS;
   const int K0 = mw.K[0];
@@ -130,25 +130,29 @@ __global__ void __launch_bounds__(256, 2) sigmaenv_mlp32_kernel(Mlp32Weights mw,
     const int k1 = KQ0 > 1 ? 1 : 0;
     l0w[0] = wa0[0]; l0w[1] = wa0[(size_t)KQ0 * 64]; l0w[2] = wa0[(size_t)k1 * 64]; l0w[3] = wa0[(size_t)(KQ0 + k1) * 64];
   }
-  if ((in_dim & 3) == 0 && (K0 & 3) == 0) {  // input tile, four columns per lane and load (rows are 16-byte aligned)
-    const int Q0 = K0 >> 2;
-    for (int e = tid; e < Q0 * MLP32_ROWS; e += blockDim.x) {
-      const int n = e / Q0, k = (e - n * Q0) << 2;
-      const int row = row0 + n;
-      float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (row < R && k < in_dim) v = reinterpret_cast<const float4*>(in + (size_t)row * in_dim)[k >> 2];
-      // columns k, k + 2 share a fragment (k parity 0), k + 1, k + 3 the one 64 fragments further (mlp32_act_idx)
-      float* d = x + mlp32_act_idx(k, n);
-      *reinterpret_cast<float2*>(d) = make_float2(v.x, v.z);
-      *reinterpret_cast<float2*>(d + MLP32_ROWS * 4) = make_float2(v.y, v.w);
+  // input tile, columns [c0, c0 + cw) of layer 0 (cw a multiple of 8, at most MLP32_KC; columns >= in_dim are zeros) at LDS columns [0, cw)
+  auto stage = [&](const int c0, const int cw) {
+    if ((in_dim & 3) == 0) {  // four columns per lane and load (rows are 16-byte aligned: include/sigmaenv.h)
+      const int Q = cw >> 2;
+      for (int e = tid; e < Q * MLP32_ROWS; e += blockDim.x) {
+        const int n = e / Q, kl = (e - n * Q) << 2, k = c0 + kl;
+        const int row = row0 + n;
+        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (row < R && k < in_dim) v = reinterpret_cast<const float4*>(in + (size_t)row * in_dim)[k >> 2];
+        // columns k, k + 2 share a fragment (k parity 0), k + 1, k + 3 the one 64 fragments further (mlp32_act_idx)
+        float* d = x + mlp32_act_idx(kl, n);
+        *reinterpret_cast<float2*>(d) = make_float2(v.x, v.z);
+        *reinterpret_cast<float2*>(d + MLP32_ROWS * 4) = make_float2(v.y, v.w);
+      }
+    } else {
+      for (int e = tid; e < cw * MLP32_ROWS; e += blockDim.x) {            // (coalesced along k within a row)
+        const int n = e / cw, kl = e - n * cw, k = c0 + kl;
+        const int row = row0 + n;
+        x[mlp32_act_idx(kl, n)] = (row < R && k < in_dim) ? in[(size_t)row * in_dim + k] : 0.0f;
+      }
     }
-  } else {
-    for (int e = tid; e < K0 * MLP32_ROWS; e += blockDim.x) {             // input tile (coalesced along k within a row)
-      const int n = e / K0, k = e - n * K0;
-      const int row = row0 + n;
-      x[mlp32_act_idx(k, n)] = (row < R && k < in_dim) ? in[(size_t)row * in_dim + k] : 0.0f;
-    }
-  }
+  };
+  stage(0, K0 < MLP32_KC ? K0 : MLP32_KC);
   __syncthreads();
   MLP32_TS(1);
   const float4* x4 = reinterpret_cast<const float4*>(x);
@@ -188,13 +192,26 @@ __global__ void __launch_bounds__(256, 2) sigmaenv_mlp32_kernel(Mlp32Weights mw,
       float4 a0, a1, n0, n1;
       if (l == 0) { a0 = l0w[0]; a1 = l0w[1]; n0 = l0w[2]; n1 = l0w[3]; }  // (requested before the input tile was staged)
       else { a0 = wa[0]; a1 = wa[(size_t)KQ * 64]; n0 = wa[(size_t)k1 * 64]; n1 = wa[(size_t)(KQ + k1) * 64]; }
-      for (int kq = 0; kq < KQ; ++kq) {
-        const int kn = kq + 2 < KQ ? kq + 2 : KQ - 1;                    // weights two k blocks ahead
-        const float4 p0 = wa[(size_t)kn * 64], p1 = wa[(size_t)(KQ + kn) * 64];
-        const float4 b0 = xb[(size_t)kq * (MLP32_ROWS * 2)], b1 = xb[(size_t)kq * (MLP32_ROWS * 2) + 32];
-        mlp32_mfma4(acc[0][0], a0, b0); mlp32_mfma4(acc[0][1], a0, b1);
-        mlp32_mfma4(acc[1][0], a1, b0); mlp32_mfma4(acc[1][1], a1, b1);
-        a0 = n0; a1 = n1; n0 = p0; n1 = p1;
+      // (only layer 0 comes here: every later layer has K = 256.)  Its inputs arrive in chunks of MLP32_KC columns; the k order of the four chains is that of one
+      // pass over all K (the weight requests run across the chunk boundaries), so the results do not depend on the chunking
+      for (int c0 = 0; c0 < KQ; c0 += MLP32_KC / 8) {
+        if (c0 > 0) {
+          __syncthreads();  // every wavefront is done reading the previous chunk
+#ifdef SIGMAENV_POISON
+          for (int e = tid; e < MLP32_KC * MLP32_ROWS; e += blockDim.x) x[e] = __uint_as_float(0xFFFFFFFFu);  // (a read of a column the new chunk does not stage is a NaN)
+#endif
+          stage(c0 * 8, KQ - c0 < MLP32_KC / 8 ? (KQ - c0) * 8 : MLP32_KC);
+          __syncthreads();
+        }
+        const int c1 = KQ - c0 < MLP32_KC / 8 ? KQ : c0 + MLP32_KC / 8;
+        for (int kq = c0; kq < c1; ++kq) {
+          const int kn = kq + 2 < KQ ? kq + 2 : KQ - 1;                  // weights two k blocks ahead
+          const float4 p0 = wa[(size_t)kn * 64], p1 = wa[(size_t)(KQ + kn) * 64];
+          const float4 b0 = xb[(size_t)(kq - c0) * (MLP32_ROWS * 2)], b1 = xb[(size_t)(kq - c0) * (MLP32_ROWS * 2) + 32];
+          mlp32_mfma4(acc[0][0], a0, b0); mlp32_mfma4(acc[0][1], a0, b1);
+          mlp32_mfma4(acc[1][0], a1, b0); mlp32_mfma4(acc[1][1], a1, b1);
+          a0 = n0; a1 = n1; n0 = p0; n1 = p1;
+        }
       }
 #pragma unroll
       for (int ft = 0; ft < 2; ++ft)
@@ -343,8 +360,7 @@ extern "C" int sigmaenv_mlp32_create(int32_t n_layers, const int32_t* dims, cons
     m->w.w[l] = (const float*)dw; m->w.b[l] = (const float*)db;
     m->w.K[l] = Kp; m->w.F[l] = F; m->w.Fp[l] = Fp;
   }
-  m->smem = ((size_t)(m->w.K[0] > MLP32_H ? m->w.K[0] : MLP32_H) * MLP32_ROWS + 2 * 32 * 32) * sizeof(float);
-  if (m->smem > 160 * 1024) { sigmaenv_mlp32_destroy(m); return SIGMAENV_EINVAL; }
+  m->smem = ((size_t)MLP32_H * MLP32_ROWS + 2 * 32 * 32) * sizeof(float);  // 72 KB for every input width (layer 0's inputs are staged MLP32_KC columns at a time)
   // the split form: (hi, lo) fp16 fragments of the weights times 2^8, biases times the accumulator scale of their layer
   m->ws.n_layers = n_layers;
   for (int l = 0; l < n_layers && m->split_ok; ++l)

@@ -10,7 +10,7 @@
 // 3.6e-7 for the split, 6.4e-7 for the exact fp32 fma chain (the fp16 instruction sums its 16 products before it rounds) -- the same error class as
 // torch.nn.Linear in fp32, whose summation order differs anyway; tests/test_gpu_actor.py holds both modes to the same 1e-5.
 // Scales: weights and hidden activations (|tanh| <= 1) are stored times 2^8, the input rows times 2^4, so that the lo parts of values down to 2^-11 (2^-7 for
-// inputs) are fp16 normals; ranges |w| < 255, |input| < 4094 (create falls back to the exact mode when a weight is outside; an input outside gives inf / nan).
+// inputs) are fp16 normals; ranges |w| < 255, |input| < 4094 (create falls back to the exact mode when a weight is outside; an input outside is saturated: mlp32s_sat).
 // The accumulator carries the product of the two scales (biases are pre-scaled: exact), the epilogue multiplies by its reciprocal (exact).
 //
 // Mapping: as the exact kernel -- one workgroup (4 wavefronts) owns 64 rows through all layers, wavefront w owns feature tiles 2 w, 2 w + 1 x both row tiles,

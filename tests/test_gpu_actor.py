@@ -2,29 +2,9 @@
 torch.nn and a bf16-emulating restatement; the distribution head; rollouts without the host."""
 import numpy as np
 import pytest
+from network_check import emulated_bf16 as _emulated
 
 pytestmark = pytest.mark.gpu
-
-
-def _bf16(a):
-    """round-to-nearest-even fp32 -> bf16 -> fp32 (numpy)"""
-    u = np.ascontiguousarray(a, np.float32).view(np.uint32).astype(np.uint64)
-    u = (u + 0x7FFF + ((u >> 16) & 1)) & 0xFFFF0000
-    return u.astype(np.uint32).view(np.float32)
-
-
-def _emulated(mlp, obs):
-    """What the kernel computes: bf16 inputs / weights / hidden activations, fp32 accumulation (the summation order inside the matrix
-    cores differs, hence the tolerance)."""
-    import torch
-    lin = [m for m in mlp.modules() if isinstance(m, torch.nn.Linear)]
-    x = _bf16(obs)
-    for k, m in enumerate(lin):
-        w, b = _bf16(m.weight.detach().numpy()), m.bias.detach().numpy().astype(np.float32)
-        x = (x.astype(np.float64) @ w.T.astype(np.float64) + b).astype(np.float32)
-        if k < 3:
-            x = _bf16(np.tanh(x))
-    return x
 
 
 def _setup(B=64, N=16, seed=0, precision="bf16", **pkw):

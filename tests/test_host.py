@@ -141,6 +141,15 @@ def test_product_refuses_to_run_without_gpu():
         SigmaEnv(Parameters(n_agents=2, scenario_type="cpm_entire", is_apply_mask=False), n_envs=1)
 
 
+def test_mlp32_refuses_inputs_wider_than_4096_at_construction():
+    """sigmaenv_mlp32 takes input widths 1 .. 4096 (include/sigmaenv.h): a wider network is a ValueError when it is built, before any library call."""
+    from sigmarl_amd.actor import Critic, Mlp32, make_mlp
+
+    for cls in (Mlp32, Critic):
+        with pytest.raises(ValueError, match="4096"):
+            cls(make_mlp(4097, n_out=1))
+
+
 def test_oracle_auto_reset_invariants():
     """Device-style sampler spec (shared with the HIP kernel): feasible, on-path, deterministic per (seed, counter)."""
     mp = load_map("cpm_entire")
