@@ -385,10 +385,74 @@ int sigmaenv_rollout(sigmaenv_t* h, sigmaenv_actor_t* a, int32_t n_steps, float*
 /* The same with the actor in the REFERENCE's precision (an fp32 torch MLP, decision_making_module.py:34-82): sigmaenv_actor_forward_f32 in front of
  * every step instead of the bf16 kernel; `m` from sigmaenv_mlp32_create (obs_dim -> 256 -> 256 -> 256 -> 4), low / high HOST pointers (2 floats each),
  * scratch device f32 [B * N * 4].  Step t == sigmaenv_actor_forward_f32(.., seed, counter0 + t, ..) then sigmaenv_step_autoreset(.., seed, counter0 + t, ..)
- * bit for bit.  The policy reads SIGMAENV_BUF_OBS, i.e. the observation incl. the sensor noise when sigmaenv_config_t.obs_noise_level > 0. */
+ * bit for bit.  The policy reads SIGMAENV_BUF_OBS, i.e. the observation incl. the sensor noise when sigmaenv_config_t.obs_noise_level > 0.
+ * This runs the PLAIN policy (or the CBF-constrained one, above) only: opponent modelling and prioritized action propagation are sigmaenv_rollout_f32_ex. */
 int sigmaenv_rollout_f32(sigmaenv_t* h, sigmaenv_mlp32_t* m, const float* low, const float* high, float* scratch, int32_t n_steps, float* actions_buf,
                          float* slab_base, float* logp_base, float* actions_rec, uint64_t seed, uint64_t counter0, int32_t path_first, int32_t path_count,
                          int32_t deterministic);
+
+/* ---- policy wrappers of the training collector in the device rollout ----------------------------------------------------------------
+ * SyncDataCollectorCustom.rollout (sigmarl/helper_training.py:708-740) runs one of four policies per step: the CBF-constrained one (sigmaenv_rollout_f32 after
+ * sigmaenv_cbf_attach), opponent modelling, prioritized action propagation, or the plain policy (sigmaenv_rollout_f32).  sigmaenv_rollout_f32_ex adds the two
+ * middle ones; with opts == NULL or wrapper == SIGMAENV_WRAP_PLAIN it IS sigmaenv_rollout_f32 (same bits).  The collector's chain is if / elif: a wrapper on a
+ * handle with a "cbf" rew_method (SIGMAENV_REW_CBF / SIGMAENV_REW_CBF_QP) is SIGMAENV_EINVAL.
+ *
+ * SIGMAENV_WRAP_OPPONENT (opponent_modeling, helper_training.py:1071-1142; needs SIGMAENV_OBS_OPPONENT_PAD, `m` takes the handle's obs_dim).  Step t:
+ *   tentative forward  sigmaenv_actor_forward_f32 on SIGMAENV_BUF_OBS with seed ^ (1 << 63) (the TENTATIVE key), counter counter0 + t, log-probabilities dropped;
+ *   sigmaenv_opponent_fill on its actions;  final forward with (seed, counter0 + t) -- the key of the plain rollout's step t -- into the step's actions /
+ *   log-probabilities;  the step.  The reference samples the policy twice on the filled observation (:1139, then the collector at :730) and keeps the second
+ *   draw; one draw from the same distribution is made here.  tentative_rec (optional, device f32 [n_steps, B, N, K, 2]): the neighbour actions written into the
+ *   placeholder columns at step t (the step rewrites the observation: this is how a trainer recovers the filled observation the reference stores).
+ *
+ * SIGMAENV_WRAP_PRIORITIZED (prioritized_ap_policy, helper_training.py:1162-1315; `m` takes obs_dim + 2 K inputs: the base observation, SIGMAENV_BUF_OBS padded
+ * with 2 K columns as info()["base_observation"] is -- also when the handle has SIGMAENV_OBS_OPPONENT_PAD).  Step t:
+ *   1. ranks [B, N] (agent indices, highest priority first) from priority_source:
+ *      SIGMAENV_PRIORITY_NET     sigmaenv_priority_forward of priority_net on SIGMAENV_BUF_OBS (the priority observation) with (seed, counter0 + t);
+ *      SIGMAENV_PRIORITY_RANDOM  sigmaenv_priority_random with (seed, counter0 + t) (prioritization_method "random");
+ *      SIGMAENV_PRIORITY_GIVEN   ranks_given, device i32 [B, N], the same every step (entries outside [0, N) act for nobody).
+ *   2. the step's actions are zeroed (combined_action), then N turns: turn k gathers, for every env b, the base observation of agent i = ranks[b, k] with the
+ *      current actions of its K observed neighbours (SIGMAENV_BUF_NEARING) in the 2 K padded columns -- zeros for neighbours that have not acted yet -- into a
+ *      compact [B, obs_dim + 2 K] buffer, and runs the actor on those B rows only; the head writes agent (b, i)'s action / log-probability and draws with that
+ *      row's key, so that the sample is bit for bit what sigmaenv_actor_forward_f32 on all B * N rows with (seed, counter0 + t) gives that row.
+ *   3. the step on the combined actions.  The collector calls the policy once more on the turn observations (:743): a re-draw from the same distributions;
+ *      the turn draws are kept here.
+ *   Records (optional): rank_rec i32 [n_steps, B, N]; score_rec / score_logp_rec f32 [n_steps, B, N] (SIGMAENV_PRIORITY_NET); tentative_rec as above = the
+ *   neighbour actions each agent saw at its turn.  Communication noise (is_communication_noise, :1240-1254) is not built.
+ * A first call per handle allocates a workspace (grown when a later call needs more): do not make that first call inside a stream capture. */
+#define SIGMAENV_WRAP_PLAIN 0
+#define SIGMAENV_WRAP_OPPONENT 1
+#define SIGMAENV_WRAP_PRIORITIZED 2
+#define SIGMAENV_PRIORITY_NET 0
+#define SIGMAENV_PRIORITY_RANDOM 1
+#define SIGMAENV_PRIORITY_GIVEN 2
+typedef struct sigmaenv_rollout_opts {
+  int32_t wrapper;                   /* SIGMAENV_WRAP_* */
+  int32_t priority_source;           /* SIGMAENV_PRIORITY_* (SIGMAENV_WRAP_PRIORITIZED) */
+  sigmaenv_mlp32_t* priority_net;    /* SIGMAENV_PRIORITY_NET: obs_dim -> 256 -> 256 -> 2 */
+  const int32_t* ranks_given;        /* SIGMAENV_PRIORITY_GIVEN: device i32 [B, N] */
+  float* tentative_rec;              /* optional device f32 [n_steps, B, N, K, 2] */
+  int32_t* rank_rec;                 /* optional device i32 [n_steps, B, N] */
+  float* score_rec;                  /* optional device f32 [n_steps, B, N] */
+  float* score_logp_rec;             /* optional device f32 [n_steps, B, N] */
+  int32_t reserved[4];               /* zero */
+} sigmaenv_rollout_opts_t;
+int sigmaenv_rollout_f32_ex(sigmaenv_t* h, sigmaenv_mlp32_t* m, const float* low, const float* high, float* scratch, int32_t n_steps, float* actions_buf,
+                            float* slab_base, float* logp_base, float* actions_rec, uint64_t seed, uint64_t counter0, int32_t path_first, int32_t path_count,
+                            int32_t deterministic, const sigmaenv_rollout_opts_t* opts);
+
+/* The priority module (sigmarl/modules/priority_module.py).  sigmaenv_priority_forward: priority_net (MultiAgentMLP depth 2: obs_dim -> 256 -> 256 -> 2, Tanh,
+ * :34-51) on `obs` (device f32 [B * N, obs_dim], or NULL for SIGMAENV_BUF_OBS), NormalParamExtractor ("biased_softplus_1.0", as the actor's) and a 1-D
+ * TanhNormal on [-1, 1] (:52-66): score = clamp(tanh(loc + scale z), -1 + 1e-6, 1 - 1e-6), z from draw 7100 of (seed, counter, env, agent) (0 when
+ * deterministic), log_prob = Normal(loc, scale).log_prob(x) - log(1 - tanh(x)^2).  scores / log_prob (optional) device f32 [B, N]; ranks (optional) device
+ * i32 [B, N] = sigmaenv_priority_rank of the scores.  scratch: device f32 [B * N * 2].
+ * sigmaenv_priority_rank (rank_agents, :118-135): ranks[b, :] = the agents of env b by descending score.  torch.argsort is not stable: here ties go to the
+ * LOWER agent index first (a stable descending sort); a NaN score ranks below every number.
+ * sigmaenv_priority_random (:147-153, prioritization_method "random"): ranks[b, :] = a uniform permutation of 0 .. N - 1 per env (inside-out Fisher-Yates on
+ * draws 7200 + i of (seed, counter, env, i)). */
+int sigmaenv_priority_forward(sigmaenv_t* h, sigmaenv_mlp32_t* priority_net, const float* obs, float* scratch, float* scores, float* log_prob, int32_t* ranks,
+                              uint64_t seed, uint64_t counter, int32_t deterministic);
+int sigmaenv_priority_rank(sigmaenv_t* h, const float* scores, int32_t* ranks);
+int sigmaenv_priority_random(sigmaenv_t* h, uint64_t seed, uint64_t counter, int32_t* ranks);
 
 /* ---- QP-free CBF margin reward ---------------------------------------------------------------------------
  * CBFQP.update_qp with Parameters.is_solve_qp == False (sigmarl/cbf_qp.py:2534-2560): the nominal CBF constraint margins of every

@@ -8,6 +8,8 @@
   ``precision="bf16"``            the fast inference variant: bf16 weights / activations, fp32 accumulation, one fused MFMA kernel; also what
                                   ``sigmaenv_rollout`` (policy + step without the host in the loop) runs
 ``Critic`` is the MAPPO critic of ``sigmarl/modules/optimization_module.py:16-32`` (centralised, shared parameters) in fp32 (same modes).
+``PriorityNet`` is the priority actor of ``sigmarl/modules/priority_module.py`` (scores, log-probabilities and ranks); ``Actor.rollout(wrapper=...)`` runs the
+collector's opponent-modelling or prioritized-propagation policy in the fp32 device rollout (``sigmaenv_rollout_f32_ex``).
 Weights come from any ``torch.nn.Sequential`` of four ``Linear`` layers (the parameter layout torchrl's shared-parameter MLP has).
 """
 from __future__ import annotations
@@ -19,6 +21,7 @@ import torch
 
 from . import capi
 from .env import SigmaEnv
+from .params import check_rollout_wrapper
 
 
 def make_mlp(obs_dim: int = 32, hidden: int = 256, n_out: int = 4) -> torch.nn.Sequential:
@@ -121,6 +124,51 @@ class Critic(Mlp32):
         return v.reshape(env.B, 1, 1).expand(env.B, env.N, 1)
 
 
+def make_priority_mlp(obs_dim: int, hidden: int = 256) -> torch.nn.Sequential:
+    """The priority actor's network in plain torch.nn (priority_module.py:34-51: ``MultiAgentMLP(depth=2, num_cells=256, Tanh)``, 2 outputs = loc, scale)."""
+    return torch.nn.Sequential(torch.nn.Linear(obs_dim, hidden), torch.nn.Tanh(), torch.nn.Linear(hidden, hidden), torch.nn.Tanh(), torch.nn.Linear(hidden, 2))
+
+
+class PriorityNet(Mlp32):
+    """The priority module (sigmarl/modules/priority_module.py): an fp32 network obs_dim -> 256 -> 256 -> 2 on the priority observation (``SigmaEnv.obs``,
+    without placeholder columns), a 1-D TanhNormal on [-1, 1] for the scores and ``rank_agents`` (agents by descending score; ties to the lower index).
+    ``forward`` is the network alone (``Mlp32``); ``scores`` runs all three (``sigmaenv_priority_forward``)."""
+
+    def __init__(self, mlp: torch.nn.Module, lib: capi.Library | None = None, mode: str = "split"):
+        super().__init__(mlp, lib, mode)
+        if self.out_dim != 2:
+            raise ValueError("a priority network has 2 outputs (loc, scale)")
+
+    def scores(self, env: SigmaEnv, obs: torch.Tensor | None = None, seed: int = 0, counter: int = 0, deterministic: bool = False):
+        """(scores [B,N], log_prob [B,N], ranks [B,N] int32) of ``env.obs`` (or ``obs [B*N, obs_dim]``); enqueued on the env's stream."""
+        if self.in_dim != (obs.shape[-1] if obs is not None else env.D):
+            raise ValueError(f"priority network input width {self.in_dim} != observation width")
+        kw = dict(dtype=torch.float32, device=env.device)
+        scratch, sc, lp = torch.empty((env.B * env.N, 2), **kw), torch.empty((env.B, env.N), **kw), torch.empty((env.B, env.N), **kw)
+        ranks = torch.empty((env.B, env.N), dtype=torch.int32, device=env.device)
+        p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
+        rc = env.lib.priority_forward(env.h, self.handle(env.lib), p(obs), p(scratch), p(sc), p(lp), p(ranks), int(seed), int(counter), int(bool(deterministic)))
+        if rc != 0:
+            raise RuntimeError(f"sigmaenv_priority_forward failed with code {rc}: {env.lib.last_error(env.h).decode()}")
+        return sc, lp, ranks
+
+
+def rank_scores(env: SigmaEnv, scores: torch.Tensor) -> torch.Tensor:
+    """``sigmaenv_priority_rank``: ranks [B,N] int32 of ``scores [B,N]`` (descending; ties to the lower agent index)."""
+    if not (scores.is_cuda and scores.dtype == torch.float32 and scores.is_contiguous() and tuple(scores.shape) == (env.B, env.N)):
+        raise TypeError(f"scores must be a contiguous float32 CUDA tensor [{env.B}, {env.N}]")
+    ranks = torch.empty((env.B, env.N), dtype=torch.int32, device=env.device)
+    env._chk(env.lib.priority_rank(env.h, C.c_void_p(scores.data_ptr()), C.c_void_p(ranks.data_ptr())), "priority_rank")
+    return ranks
+
+
+def random_ranks(env: SigmaEnv, seed: int = 0, counter: int = 0) -> torch.Tensor:
+    """``sigmaenv_priority_random``: one uniform permutation of the agents per env ([B,N] int32; prioritization_method "random")."""
+    ranks = torch.empty((env.B, env.N), dtype=torch.int32, device=env.device)
+    env._chk(env.lib.priority_random(env.h, int(seed), int(counter), C.c_void_p(ranks.data_ptr())), "priority_random")
+    return ranks
+
+
 class Actor:
     def __init__(self, mlp: torch.nn.Module, low, high, lib: capi.Library | None = None, precision: str = "fp32", mode: str = "split"):
         if precision not in ("fp32", "bf16"):
@@ -207,16 +255,36 @@ class Actor:
 
     def rollout(self, env: SigmaEnv, n_steps: int, slab: torch.Tensor | None = None, log_prob: torch.Tensor | None = None,
                 actions: torch.Tensor | None = None, seed: int = 0, counter0: int = 0, path_first: int | None = None, path_count: int | None = None,
-                deterministic: bool = False, precision: str | None = None, slab_ptr: int | None = None):
+                deterministic: bool = False, precision: str | None = None, slab_ptr: int | None = None, wrapper: str | None = None,
+                priority=None, tentative: torch.Tensor | None = None, ranks: torch.Tensor | None = None, scores: torch.Tensor | None = None,
+                score_log_prob: torch.Tensor | None = None):
         """``n_steps`` x (policy -> fused step + record + resets) enqueued back to back; optional records ``slab [T,B,W]``,
         ``log_prob [T,B,N]``, ``actions [T,B,N,2]`` (CUDA float32, contiguous).  ``slab_ptr``: the record target as a raw device address instead of ``slab`` (an env
         shard's first row inside a ``[T, B_total, W]`` buffer of the whole batch, with ``env.set_rollout_slab_stride(B_total * W)``).  ``precision`` (default: the actor's): "fp32" = the reference's
-        arithmetic (``sigmaenv_rollout_f32``), "bf16" = the fast inference variant (``sigmaenv_rollout``)."""
+        arithmetic (``sigmaenv_rollout_f32``), "bf16" = the fast inference variant (``sigmaenv_rollout``).
+
+        ``wrapper`` (fp32 only; ``params.rollout_wrapper`` gives the collector's choice for a ``Parameters``): ``None`` = the plain policy as above;
+        ``"plain"`` = the same through ``sigmaenv_rollout_f32_ex``; ``"opponent"`` = opponent modelling (the env needs ``is_using_opponent_modeling``);
+        ``"prioritized"`` = prioritized action propagation (the actor takes obs_dim + 2 n_nearing inputs) with ``priority`` = a ``PriorityNet``, ``"random"``
+        or a rank tensor [B,N] int32 (CUDA).  Records: ``tentative [T,B,N,K,2]`` (the neighbour actions the policy saw), ``ranks [T,B,N]`` int32,
+        ``scores`` / ``score_log_prob [T,B,N]`` (``PriorityNet`` only).  Step semantics: include/sigmaenv.h, sigmaenv_rollout_f32_ex."""
+        check_rollout_wrapper(getattr(env, "parameters", None), wrapper)
         if path_first is None:
             path_first, path_count = env.default_paths()
         scratch = self._scratch_actions(env)
         p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
         p_slab = C.c_void_p(int(slab_ptr)) if slab_ptr else p(slab)
+        if wrapper is not None:
+            if (precision or self.precision) != "fp32":
+                raise ValueError("the rollout wrappers run the fp32 actor (precision='fp32')")
+            opts = self._wrapper_opts(env, int(n_steps), wrapper, priority, tentative, ranks, scores, score_log_prob)
+            lo, hi = self._keep[-2], self._keep[-1]
+            rc = env.lib.rollout_f32_ex(env.h, self._mlp32.handle(env.lib), lo.ctypes.data_as(C.c_void_p), hi.ctypes.data_as(C.c_void_p), p(self._scratch_out4(env)),
+                                         int(n_steps), p(scratch), p_slab, p(log_prob), p(actions), int(seed), int(counter0), int(path_first), int(path_count),
+                                         int(bool(deterministic)), C.byref(opts))
+            if rc != 0:
+                raise RuntimeError(f"sigmaenv_rollout_f32_ex failed with code {rc}: {env.lib.last_error(env.h).decode()}")
+            return
         if (precision or self.precision) == "fp32":
             lo, hi = self._keep[-2], self._keep[-1]
             rc = env.lib.rollout_f32(env.h, self._mlp32.handle(env.lib), lo.ctypes.data_as(C.c_void_p), hi.ctypes.data_as(C.c_void_p), p(self._scratch_out4(env)), int(n_steps),
@@ -229,3 +297,38 @@ class Actor:
                               int(path_count), int(bool(deterministic)))
         if rc != 0:
             raise RuntimeError(f"sigmaenv_rollout failed with code {rc}: {env.lib.last_error(env.h).decode()}")
+
+    def _wrapper_opts(self, env: SigmaEnv, T: int, wrapper: str, priority, tentative, ranks, scores, score_log_prob) -> capi.RolloutOpts:
+        opts = capi.RolloutOpts()
+        opts.wrapper = {"plain": capi.WRAP_PLAIN, "opponent": capi.WRAP_OPPONENT, "prioritized": capi.WRAP_PRIORITIZED}[wrapper]
+
+        def rec(t, shape, dtype, what):
+            if t is None:
+                return None
+            if not (t.is_cuda and t.dtype == dtype and t.is_contiguous() and tuple(t.shape) == tuple(shape)):
+                raise TypeError(f"{what} must be a contiguous {dtype} CUDA tensor {list(shape)}")
+            return t.data_ptr()
+
+        opts.tentative_rec = rec(tentative, (T, env.B, env.N, env.K, 2), torch.float32, "tentative")
+        if wrapper != "prioritized":
+            if priority is not None or ranks is not None or scores is not None or score_log_prob is not None:
+                raise ValueError("priority / ranks / scores / score_log_prob belong to wrapper='prioritized'")
+            return opts
+        opts.rank_rec = rec(ranks, (T, env.B, env.N), torch.int32, "ranks")
+        if isinstance(priority, PriorityNet):
+            opts.priority_source = capi.PRIORITY_NET
+            opts.priority_net = priority.handle(env.lib)
+            opts.score_rec = rec(scores, (T, env.B, env.N), torch.float32, "scores")
+            opts.score_logp_rec = rec(score_log_prob, (T, env.B, env.N), torch.float32, "score_log_prob")
+        else:
+            if scores is not None or score_log_prob is not None:
+                raise ValueError("scores / score_log_prob are recorded with a PriorityNet only")
+            if isinstance(priority, str) and priority == "random":
+                opts.priority_source = capi.PRIORITY_RANDOM
+            elif isinstance(priority, torch.Tensor):
+                opts.priority_source = capi.PRIORITY_GIVEN
+                opts.ranks_given = rec(priority, (env.B, env.N), torch.int32, "priority (ranks)")
+                self._given_ranks = priority  # (kept alive until the next call: the launches read it asynchronously)
+            else:
+                raise TypeError("priority must be a PriorityNet, 'random' or an int32 rank tensor [B, N]")
+        return opts

@@ -80,6 +80,20 @@ class CbfConfig(C.Structure):
     ]
 
 
+WRAP_PLAIN, WRAP_OPPONENT, WRAP_PRIORITIZED = 0, 1, 2  # sigmaenv_rollout_opts_t.wrapper
+PRIORITY_NET, PRIORITY_RANDOM, PRIORITY_GIVEN = 0, 1, 2  # sigmaenv_rollout_opts_t.priority_source
+
+
+class RolloutOpts(C.Structure):
+    """``sigmaenv_rollout_opts_t`` (sigmaenv_rollout_f32_ex): the collector's policy wrapper and its records."""
+
+    _fields_ = [
+        ("wrapper", C.c_int32), ("priority_source", C.c_int32), ("priority_net", C.c_void_p), ("ranks_given", C.c_void_p),
+        ("tentative_rec", C.c_void_p), ("rank_rec", C.c_void_p), ("score_rec", C.c_void_p), ("score_logp_rec", C.c_void_p),
+        ("reserved", C.c_int32 * 4),
+    ]
+
+
 # vehicle constants of the reference, sigmarl/constants.py:628-647
 AGENTS = {
     "width": 0.107, "length": 0.22, "l_f": 0.075, "l_r": 0.075, "l_wb": 0.15,
@@ -189,6 +203,11 @@ _PRODUCT_ONLY = {
                               C.c_int32, C.c_int32, C.c_int32]),
     "rollout": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_int32,
                           C.c_int32, C.c_int32]),
+    "rollout_f32_ex": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64,
+                                 C.c_uint64, C.c_int32, C.c_int32, C.c_int32, C.POINTER(RolloutOpts)]),
+    "priority_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_int32]),
+    "priority_rank": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "priority_random": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p]),
 }
 
 

@@ -1771,6 +1771,8 @@ struct sigmaenv {
   void* cbf_cand_big = nullptr;   // [B][N (N - 1) C^2] u32: the CBF-QP's candidate pair rows for 33 .. 64 vehicles (allocated by the first such sigmaenv_cbf_qp)
   int32_t* cbf_groups = nullptr;  // [B,N] group index of every vehicle (grouped CBF-QPs), formed by the first sigmaenv_cbf_qp call
   bool cbf_groups_valid = false;
+  void* wrap_ws = nullptr;        // workspace of the rollout wrappers (sigmaenv_wrappers.inc), grown on demand
+  size_t wrap_ws_bytes = 0;
   std::string err;
 };
 
@@ -2237,17 +2239,19 @@ extern "C" int sigmaenv_set_lanelets(sigmaenv_t* h, int32_t n_lanelets, int32_t 
   return SIGMAENV_OK;
 }
 
-extern "C" int sigmaenv_opponent_fill(sigmaenv_t* h, const float* actions) {
+// rec: see sigmaenv_opponent_fill_kernel (nullptr for the C-ABI call)
+static int opponent_fill_impl(sigmaenv_t* h, const float* actions, float* rec) {
   if (!h || !actions) return SIGMAENV_EINVAL;
   if (!(h->cfg.obs_flags & SIGMAENV_OBS_OPPONENT_PAD)) { h->err = "opponent_fill: the configuration has no placeholder columns (SIGMAENV_OBS_OPPONENT_PAD)"; return SIGMAENV_EINVAL; }
   HIPCHK(h, hipSetDevice(h->device));
   const size_t n = (size_t)h->B * h->N * h->cfg.n_nearing;
   if (n == 0) return SIGMAENV_OK;
   hipLaunchKernelGGL(obsvar::sigmaenv_opponent_fill_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, h->buf.obs, h->D, h->buf.nearing, actions, h->B, h->N,
-                     h->cfg.n_nearing);
+                     h->cfg.n_nearing, rec);
   HIPCHK(h, hipGetLastError());
   return SIGMAENV_OK;
 }
+extern "C" int sigmaenv_opponent_fill(sigmaenv_t* h, const float* actions) { return opponent_fill_impl(h, actions, nullptr); }
 
 // the path range of a device-side reset: [path_first, path_first + path_count) of the table, or the handle's sub-scenario lists
 static bool paths_ok(const sigmaenv* h, int32_t path_first, int32_t path_count) {
@@ -2560,4 +2564,5 @@ extern "C" int sigmaenv_trig_selftest(sigmaenv_t* h, int32_t kind, int32_t n, co
 
 #include "sigmaenv_actor.inc"
 #include "sigmaenv_mlp32.inc"
+#include "sigmaenv_wrappers.inc"
 #include "sigmaenv_cbf.inc"

@@ -294,15 +294,18 @@ __global__ void __launch_bounds__(256, 2) sigmaenv_mlp32_kernel(Mlp32Weights mw,
 
 #include "sigmaenv_mlp32s.inc"  // the same networks on the fp16 matrix rate (every fp32 operand as hi + lo): mode SIGMAENV_MLP32_SPLIT
 
-// the distribution head of the actor on the 4 outputs per row of the exact MLP (same function as the bf16 kernel's epilogue)
+// the distribution head of the actor on the 4 outputs per row of the exact MLP (same function as the bf16 kernel's epilogue); row_map as Mlp32sHead::row_map
 __global__ void sigmaenv_actor_head_kernel(const float* __restrict__ out4, int R, int n_agents, int env_base, float low0, float low1, float high0, float high1, float* __restrict__ actions,
-                                           float* __restrict__ log_prob, float* __restrict__ loc_scale, uint64_t seed, uint64_t counter, int deterministic) {
+                                           float* __restrict__ log_prob, float* __restrict__ loc_scale, uint64_t seed, uint64_t counter, int deterministic,
+                                           const int32_t* __restrict__ row_map) {
   sigma_poison_lds();
   const int row = blockIdx.x * blockDim.x + threadIdx.x;
   if (row >= R) return;
+  const int orow = row_map ? row_map[row] : row;
+  if (orow < 0) return;
   const float4 o = reinterpret_cast<const float4*>(out4)[row];
   const float low[2] = {low0, low1}, high[2] = {high0, high1};
-  actor_distribution(low, high, row, n_agents, env_base, o.x, o.y, o.z, o.w, actions, log_prob, loc_scale, seed, counter, deterministic);
+  actor_distribution(low, high, orow, n_agents, env_base, o.x, o.y, o.z, o.w, actions, log_prob, loc_scale, seed, counter, deterministic);
 }
 
 // ---- host side -------------------------------------------------------------------------------------------------------------------
@@ -473,26 +476,32 @@ static int mlp32_forward_impl(sigmaenv_t* h, sigmaenv_mlp32* m, const float* in,
 
 // The actor in the reference's precision: exact-fp32 MLP (obs_dim -> 256 -> 256 -> 256 -> 4) + the distribution head.  Same outputs as
 // sigmaenv_actor_forward; `scratch`: device f32 [B * N * 4].
-extern "C" int sigmaenv_actor_forward_f32(sigmaenv_t* h, sigmaenv_mlp32* m, const float* obs, float* scratch, const float* low, const float* high, float* actions,
-                                          float* log_prob, float* loc_scale, uint64_t seed, uint64_t counter, int32_t deterministic) {
-  if (!h || !m || !scratch || !actions || !low || !high || m->out_dim != 4 || (!obs && m->in_dim != h->D)) return SIGMAENV_EINVAL;
-  const int R = h->B * h->N;
+// R network rows `in` [R, in_dim] -> the actor's outputs of agent rows row_map[r] (nullptr: R = B * N, identity); scratch: device f32 [R * 4]
+static int actor_rows_f32(sigmaenv_t* h, sigmaenv_mlp32* m, const float* in, int R, const int32_t* row_map, float* scratch, const float* low, const float* high, float* actions,
+                          float* log_prob, float* loc_scale, uint64_t seed, uint64_t counter, int32_t deterministic) {
   Mlp32sHead hd{};
   hd.n_agents = h->N; hd.env_base = h->cfg.env_index_base; hd.deterministic = (int)deterministic;
   hd.low0 = low[0]; hd.low1 = low[1]; hd.high0 = high[0]; hd.high1 = high[1];
-  hd.actions = actions; hd.log_prob = log_prob; hd.loc_scale = loc_scale; hd.seed = seed; hd.counter = counter;
+  hd.actions = actions; hd.log_prob = log_prob; hd.loc_scale = loc_scale; hd.seed = seed; hd.counter = counter; hd.row_map = row_map;
   bool head_done = false;
-  int rc = mlp32_forward_impl(h, m, obs ? obs : h->buf.obs, R, scratch, &hd, &head_done);
+  int rc = mlp32_forward_impl(h, m, in, R, scratch, &hd, &head_done);
   if (rc) return rc;
   if (head_done) return SIGMAENV_OK;  // (split mode: the head ran as the network kernel's epilogue)
   hipLaunchKernelGGL(sigmaenv_actor_head_kernel, dim3((R + 255) / 256), dim3(256), 0, h->stream, scratch, R, h->N, h->cfg.env_index_base, low[0], low[1], high[0], high[1], actions, log_prob,
-                     loc_scale, seed, counter, (int)deterministic);
+                     loc_scale, seed, counter, (int)deterministic, row_map);
   HIPCHK(h, hipGetLastError());
   return SIGMAENV_OK;
 }
 
+extern "C" int sigmaenv_actor_forward_f32(sigmaenv_t* h, sigmaenv_mlp32* m, const float* obs, float* scratch, const float* low, const float* high, float* actions,
+                                          float* log_prob, float* loc_scale, uint64_t seed, uint64_t counter, int32_t deterministic) {
+  if (!h || !m || !scratch || !actions || !low || !high || m->out_dim != 4 || (!obs && m->in_dim != h->D)) return SIGMAENV_EINVAL;
+  return actor_rows_f32(h, m, obs ? obs : h->buf.obs, h->B * h->N, nullptr, scratch, low, high, actions, log_prob, loc_scale, seed, counter, deterministic);
+}
+
 // sigmaenv_rollout in the reference's precision (decision_making_module.py:34-82: an fp32 torch MLP): n_steps x (exact-fp32 actor forward + distribution
-// head -> [CBF launch] -> fused step + record + resets), enqueued back to back without returning to the caller.  Step t is exactly
+// head -> [CBF launch] -> fused step + record + resets), enqueued back to back without returning to the caller.  The plain policy only: the
+// opponent-modelling and prioritized wrappers of the collector run through sigmaenv_rollout_f32_ex (sigmaenv_wrappers.inc).  Step t is exactly
 // sigmaenv_actor_forward_f32(..., seed, counter0 + t, ...) followed by sigmaenv_step_autoreset(..., seed, counter0 + t, ...) with the record row t.
 // scratch: device f32 [B * N * 4]; the other arguments as sigmaenv_rollout.
 extern "C" int sigmaenv_rollout_f32(sigmaenv_t* h, sigmaenv_mlp32* m, const float* low, const float* high, float* scratch, int32_t n_steps, float* actions_buf,

@@ -86,11 +86,14 @@ __device__ __forceinline__ void mlp32s_act(const f32x16_t (&v)[2], int j, float 
 
 // The actor's distribution head as the kernel's epilogue (sigmaenv_actor_forward_f32 / sigmaenv_rollout_f32 in split mode): with 4 output features the lane that holds a
 // row's feature 0 holds all four -- the same floats the stand-alone head kernel reads back from `out`, without its launch.
+// row_map (nullptr: identity): network row r is agent row row_map[r] = env * n_agents + agent of the outputs and of the random draws; a negative entry writes nothing
+// (the B-row turn forward of prioritized action propagation, sigmaenv_wrappers.inc)
 struct Mlp32sHead {
   int on, n_agents, env_base, deterministic;
   float low0, low1, high0, high1;
   float *actions, *log_prob, *loc_scale;
   uint64_t seed, counter;
+  const int32_t* row_map;
 };
 __global__ void __launch_bounds__(256, 2) sigmaenv_mlp32s_kernel(Mlp32sWeights mw, const float* __restrict__ in, int R, int in_dim, float* __restrict__ out, Mlp32sHead hd MLP32_TS_ARG) {
   sigma_poison_lds();
@@ -279,7 +282,9 @@ __global__ void __launch_bounds__(256, 2) sigmaenv_mlp32s_kernel(Mlp32sWeights m
       }
       if (hd.on && h == 0 && row0 + rt * 32 + m < R) {  // (Fl == 4: features 0 .. 3 of the row are this lane's first four)
         const float low[2] = {hd.low0, hd.low1}, high[2] = {hd.high0, hd.high1};
-        actor_distribution(low, high, row0 + rt * 32 + m, hd.n_agents, hd.env_base, o4[0], o4[1], o4[2], o4[3], hd.actions, hd.log_prob, hd.loc_scale, hd.seed, hd.counter, hd.deterministic);
+        const int orow = hd.row_map ? hd.row_map[row0 + rt * 32 + m] : row0 + rt * 32 + m;
+        if (orow >= 0)
+          actor_distribution(low, high, orow, hd.n_agents, hd.env_base, o4[0], o4[1], o4[2], o4[3], hd.actions, hd.log_prob, hd.loc_scale, hd.seed, hd.counter, hd.deterministic);
       }
     }
     MLP32_TS(13);

@@ -3,8 +3,10 @@
 // observations -- the fused step and its T-step loop incl. the rollout record, the resets, sigmaenv_observe.)
 namespace obsvar {
 
-// opponent_modeling's gather (helper_training.py:1117-1137): obs[b, i, -(K - k) * 2 : +2] = actions[b, nearing[b, i, k]]; one lane per (env, agent, k)
-__global__ void __launch_bounds__(256) sigmaenv_opponent_fill_kernel(float* __restrict__ obs, int D, const int32_t* __restrict__ nearing, const float* __restrict__ actions, int B, int N, int K) {
+// opponent_modeling's gather (helper_training.py:1117-1137): obs[b, i, -(K - k) * 2 : +2] = actions[b, nearing[b, i, k]]; one lane per (env, agent, k).
+// rec (optional, [B, N, K, 2]): the same pairs once more (the rollout's record of what the policy saw, sigmaenv_rollout_f32_ex)
+__global__ void __launch_bounds__(256) sigmaenv_opponent_fill_kernel(float* __restrict__ obs, int D, const int32_t* __restrict__ nearing, const float* __restrict__ actions, int B, int N, int K,
+                                                                     float* __restrict__ rec) {
   sigma_poison_lds();
   const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= (size_t)B * N * K) return;
@@ -16,6 +18,7 @@ __global__ void __launch_bounds__(256) sigmaenv_opponent_fill_kernel(float* __re
   float* dst = obs + bi * D + (D - 2 * (K - k));
   dst[0] = a.x;
   dst[1] = a.y;
+  if (rec) reinterpret_cast<float2*>(rec)[t] = a;
 }
 
 }  // namespace obsvar

@@ -104,6 +104,29 @@ def obs_flags(p: Parameters) -> int:
     return f
 
 
+def rollout_wrapper(p: Parameters) -> str | None:
+    """The policy wrapper the training collector runs for ``p`` (``Actor.rollout(wrapper=...)``): ``"opponent"``, ``"prioritized"`` or ``None`` (the plain policy,
+    or the CBF-constrained one, which the rollout runs from the handle's ``rew_method``).  SyncDataCollectorCustom.rollout (sigmarl/helper_training.py:708-740)
+    tests CBF training, then opponent modelling, then prioritized propagation, as an if / elif chain; the evaluation rollout (:208-250) tests prioritized
+    before opponent modelling.  The rollout is the training collector's, so its order holds: both flags set gives ``"opponent"``."""
+    if getattr(p, "is_using_cbf_training", False):
+        return None
+    if getattr(p, "is_using_opponent_modeling", False):
+        return "opponent"
+    if getattr(p, "is_using_prioritized_marl", False):
+        return "prioritized"
+    return None
+
+
+def check_rollout_wrapper(p: Parameters | None, wrapper: str | None) -> None:
+    """Raise for a wrapper / configuration pair the device rollout does not build: communication noise on the propagated actions
+    (``is_communication_noise``, helper_training.py:1240-1254) is not built for ``"prioritized"`` -- refused, never ignored."""
+    if wrapper not in (None, "plain", "opponent", "prioritized"):
+        raise ValueError(f"wrapper must be None, 'plain', 'opponent' or 'prioritized', not {wrapper!r}")
+    if wrapper == "prioritized" and p is not None and getattr(p, "is_communication_noise", False):
+        raise NotImplementedError("is_communication_noise (noise on the propagated actions, helper_training.py:1240-1254) is not built in the prioritized device rollout")
+
+
 def check_supported(p: Parameters) -> None:
     """Raise for observation/feature flags the fused step does not implement (fail loudly, never silently differ)."""
     bad = []
@@ -132,7 +155,7 @@ def check_supported(p: Parameters) -> None:
     # is_using_opponent_modeling IS built: the placeholder columns (observation_provider_rt.py:606-611, capi.OBS_OPPONENT_PAD) and the gather of the
     # neighbours' tentative actions into them (SigmaEnv.opponent_fill; helper_training.py:1117-1137).
     # is_using_prioritized_marl: the environment's share is two extra info() entries (road_traffic.py:1513-1520, :1616-1625), built in scenario.info();
-    # priority assignment and action propagation are the trainer's.  is_using_pseudo_distance is read nowhere in the reference outside Parameters
+    # priority assignment and action propagation run in the device rollout (Actor.rollout(wrapper="prioritized"), rollout_wrapper / check_rollout_wrapper).  is_using_pseudo_distance is read nowhere in the reference outside Parameters
     # (helper_common.py:117, :229): accepted, no effect -- as there.
     if p.is_using_cbf_training or p.is_using_cbf_testing or "cbf" in p.rew_method:
         # built: the centralized QP (is_solve_qp=True), the grouped QPs (is_grouping_agents) and the QP-free margin reward
