@@ -305,6 +305,15 @@ int sigmaenv_set_slab(sigmaenv_t* h, void* dev_ptr);
  * sigmaenv_step_autoreset_n does through its slab_stride argument.  Returns SIGMAENV_EINVAL for a stride below the handle's own block. */
 int sigmaenv_set_rollout_slab_stride(sigmaenv_t* h, int64_t stride_floats);
 
+/* Root-observation record of sigmaenv_rollout / sigmaenv_rollout_f32 / sigmaenv_rollout_f32_ex: base device f32, or NULL (the default) for none.  When set, step t
+ * copies SIGMAENV_BUF_OBS ([B, N*D]) to base + t * stride_floats AFTER the policy and BEFORE the step, on the handle's stream: exactly the rows the step's final
+ * actor forward read (opponent modelling: with the filled placeholder columns; prioritized propagation: the observation at the start of the step).  This is the
+ * "observation" entry of the tensordict SyncDataCollectorCustom.rollout stacks (sigmarl/helper_training.py:687-788) -- the record row of step t - 1 holds it only
+ * for envs in which nothing was re-placed at step t - 1.  stride_floats 0 = B * N * D; a stride below that is SIGMAENV_EINVAL; env shards record into ONE
+ * [T, B_total, N*D] buffer with base + k * Bs * N * D and the stride B_total * N * D, as sigmaenv_set_rollout_slab_stride does for the slab.  Nothing else of a
+ * rollout changes with the record on. */
+int sigmaenv_set_rollout_obs_record(sigmaenv_t* h, float* base, int64_t stride_floats);
+
 /* Blocks until everything enqueued on the handle's stream has finished. */
 int sigmaenv_sync(sigmaenv_t* h);
 
@@ -373,6 +382,16 @@ int sigmaenv_mlp32_forward(sigmaenv_t* h, sigmaenv_mlp32_t* m, const float* in, 
 int sigmaenv_actor_forward_f32(sigmaenv_t* h, sigmaenv_mlp32_t* m, const float* obs, float* scratch, const float* low, const float* high, float* actions,
                                float* log_prob, float* loc_scale, uint64_t seed, uint64_t counter, int32_t deterministic);
 
+/* sigmaenv_mlp32_forward on rows that are NOT dense: network row r = t * rows_per_block + b (t < n_blocks, b < rows_per_block) is read from
+ * in + t * block_stride + b * row_stride (dims[0] floats; strides in floats, row_stride >= dims[0]); out is dense [n_blocks * rows_per_block, dims[n_layers]].
+ * `in` and the rows need 4-byte alignment only.  This is how the critic reads a rollout's records without a staging copy: the observation part of the rows of a
+ * [T, B_total, W] slab (row_stride = W = N*(D+1)+1, odd; block_stride = B_total * W) or a root-observation record (sigmaenv_set_rollout_obs_record) -- the
+ * `value_network(tensordict)` passes of torchrl's GAE inside _compute_gae (sigmarl/mappo_cavs.py:357-386).  Both arithmetic modes; only the staging of the input
+ * tile differs from sigmaenv_mlp32_forward (16-byte loads when base and strides are multiples of 4 floats, realigned 16-byte loads otherwise), so a row's
+ * result is bit for bit what sigmaenv_mlp32_forward gives the same row copied to a dense aligned buffer. */
+int sigmaenv_mlp32_forward_rows(sigmaenv_t* h, sigmaenv_mlp32_t* m, const float* in, int32_t rows_per_block, int64_t row_stride, int32_t n_blocks, int64_t block_stride,
+                                float* out);
+
 /* n_steps x (sigmaenv_actor_forward; sigmaenv_step_autoreset) enqueued back to back (SyncDataCollectorCustom.rollout,
  * sigmarl/helper_training.py:687-788, without its per-step Python): actions_buf device f32 [B,N,2] scratch; optional records:
  * slab_base device f32 [n_steps, B, N*(D+1)+1], logp_base device f32 [n_steps, B, N], actions_rec device f32 [n_steps, B, N, 2].
@@ -439,6 +458,36 @@ typedef struct sigmaenv_rollout_opts {
 int sigmaenv_rollout_f32_ex(sigmaenv_t* h, sigmaenv_mlp32_t* m, const float* low, const float* high, float* scratch, int32_t n_steps, float* actions_buf,
                             float* slab_base, float* logp_base, float* actions_rec, uint64_t seed, uint64_t counter0, int32_t path_first, int32_t path_count,
                             int32_t deterministic, const sigmaenv_rollout_opts_t* opts);
+
+/* ---- from a rollout's records to a learner's batch -------------------------------------------------------------------------------------
+ * sigmaenv_gae: what the trainer computes right after collector.rollout() -- _compute_gae (sigmarl/mappo_cavs.py:357-386: torchrl GAE(gamma, lmbda,
+ * value_network = critic, average_gae = False), sigmarl/modules/optimization_module.py:62-67) and, optionally, compute_td_error (sigmarl/helper_training.py:
+ * 1029-1068, the priorities of the prioritized replay buffer) -- on the records of n_steps rollout steps of this handle.  torchrl is third-party and absent: its
+ * GAE is restated from published behaviour (done = terminated: the scenario has one flag; the critic's one value per env is every agent's).
+ *   slab              device f32, the record rows [N*D observation | N reward | 1 done] of step t at slab + t * slab_stride (0: B * (N*(D+1)+1)); reward of agent i
+ *                     and done are read IN PLACE at offsets N*D + i and N*(D+1) of the env's row
+ *   state_value       device f32 [n_steps, B]: the critic on the root observations (sigmaenv_set_rollout_obs_record);  next_state_value: on the record rows
+ *   advantage, value_target   device f32 [n_steps, B, N]
+ * Arithmetic contract: fp32, one IEEE operation per operator, no contraction, c = fl32(fl32(gamma) * fl32(lmbda)); backwards over t with A_next = 0 beyond the
+ * last step:
+ *     nd = 1 - done[t,b];  d = (r[t,b,i] + (gamma * v_next[t,b]) * nd) - v[t,b];  A = d + ((c * nd) * A_next);  advantage = A;  value_target = A + v[t,b]
+ * td_priority (optional, device f32 [n_steps, B]): x[t,b] = (sum over i = 0 .. N-1, in that order, of |(r + (td_gamma * v_next) * nd) - v|) / N, then with min / max
+ * over THIS HANDLE's [n_steps, B] (an env shard normalises over its own envs): ((x - min) / max(max - min, 1e-3)) * 10 clamped to [1e-3, 10].  The result does not
+ * depend on scheduling.  The first call with td_priority allocates two words: do not make it inside a stream capture.  Enqueued on the handle's stream. */
+typedef struct sigmaenv_gae_args {
+  int32_t n_steps;
+  int32_t reserved0;               /* zero */
+  const float* slab;
+  int64_t slab_stride;             /* floats between the record blocks of consecutive steps; 0: B * (N*(D+1)+1) */
+  const float* state_value;
+  const float* next_state_value;
+  float* advantage;
+  float* value_target;
+  float* td_priority;              /* optional */
+  float gamma, lmbda, td_gamma;
+  int32_t reserved[5];             /* zero */
+} sigmaenv_gae_args_t;
+int sigmaenv_gae(sigmaenv_t* h, const sigmaenv_gae_args_t* a);
 
 /* The priority module (sigmarl/modules/priority_module.py).  sigmaenv_priority_forward: priority_net (MultiAgentMLP depth 2: obs_dim -> 256 -> 256 -> 2, Tanh,
  * :34-51) on `obs` (device f32 [B * N, obs_dim], or NULL for SIGMAENV_BUF_OBS), NormalParamExtractor ("biased_softplus_1.0", as the actor's) and a 1-D

@@ -10,6 +10,8 @@
 ``Critic`` is the MAPPO critic of ``sigmarl/modules/optimization_module.py:16-32`` (centralised, shared parameters) in fp32 (same modes).
 ``PriorityNet`` is the priority actor of ``sigmarl/modules/priority_module.py`` (scores, log-probabilities and ranks); ``Actor.rollout(wrapper=...)`` runs the
 collector's opponent-modelling or prioritized-propagation policy in the fp32 device rollout (``sigmaenv_rollout_f32_ex``).
+``Actor.rollout(obs_rec=...)`` records the observation every step's policy acted on, ``Mlp32.forward_rows`` / ``Critic.rollout_values`` run a network on the
+rollout's records where they lie (``sigmaenv_mlp32_forward_rows``); ``sigmarl_amd.learn`` builds the learner's batch from them.
 Weights come from any ``torch.nn.Sequential`` of four ``Linear`` layers (the parameter layout torchrl's shared-parameter MLP has).
 """
 from __future__ import annotations
@@ -110,6 +112,36 @@ class Mlp32:
             raise RuntimeError(f"sigmaenv_mlp32_forward failed with code {rc}: {env.lib.last_error(env.h).decode()}")
         return out
 
+    def forward_rows(self, env: SigmaEnv, base: torch.Tensor, offset: int, rows_per_block: int, row_stride: int, n_blocks: int = 1, block_stride: int = 0,
+                     out: torch.Tensor | None = None) -> torch.Tensor:
+        """``sigmaenv_mlp32_forward_rows``: the network on rows that lie inside ``base`` (any contiguous float32 CUDA tensor, read as flat floats) -- row
+        ``t * rows_per_block + b`` starts at float ``offset + t * block_stride + b * row_stride`` -- without copying them out; 4-byte alignment suffices.  Returns
+        ``[n_blocks, rows_per_block, out_dim]``, bit for bit what ``forward`` gives the same rows copied dense.  Enqueued on the env's stream."""
+        if not (base.is_cuda and base.dtype == torch.float32 and base.is_contiguous()):
+            raise TypeError("the rows must lie in a contiguous float32 CUDA tensor")
+        offset, rpb, rs, nb, bs = int(offset), int(rows_per_block), int(row_stride), int(n_blocks), int(block_stride)
+        if rpb < 0 or nb < 0 or offset < 0 or rs < self.in_dim or bs < 0:
+            raise ValueError(f"forward_rows: counts and offsets must be >= 0 and row_stride >= the input width {self.in_dim}")
+        if rpb and nb and offset + (nb - 1) * bs + (rpb - 1) * rs + self.in_dim > base.numel():
+            raise ValueError("forward_rows: the last row ends beyond the tensor")
+        if out is None:
+            out = torch.empty((nb, rpb, self.out_dim), dtype=torch.float32, device=base.device)
+        elif not (out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.numel() == nb * rpb * self.out_dim):
+            raise TypeError(f"out must be a contiguous float32 CUDA tensor of {nb * rpb * self.out_dim} elements")
+        if rpb == 0 or nb == 0:
+            return out
+        rc = env.lib.mlp32_forward_rows(env.h, self.handle(env.lib), C.c_void_p(base.data_ptr() + 4 * offset), rpb, rs, nb, bs, C.c_void_p(out.data_ptr()))
+        if rc != 0:
+            raise RuntimeError(f"sigmaenv_mlp32_forward_rows failed with code {rc}: {env.lib.last_error(env.h).decode()}")
+        return out
+
+
+def check_record(t, shape, what: str):
+    """A rollout record the device loop writes: a contiguous float32 CUDA tensor of exactly ``shape``."""
+    if not isinstance(t, torch.Tensor) or not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == tuple(shape)):
+        raise TypeError(f"{what} must be a contiguous float32 CUDA tensor {list(shape)}")
+    return t
+
 
 class Critic(Mlp32):
     """The MAPPO critic (optimization_module.py:16-32): ``MultiAgentMLP(centralised=True, share_params=True, depth=3, num_cells=256, Tanh)`` --
@@ -122,6 +154,27 @@ class Critic(Mlp32):
             raise ValueError(f"critic input width {self.in_dim} != n_agents * obs_dim = {env.N * env.D}")
         v = self.forward(env, o.reshape(env.B, env.N * env.D))
         return v.reshape(env.B, 1, 1).expand(env.B, env.N, 1)
+
+    def rollout_values(self, env: SigmaEnv, slab: torch.Tensor, obs_rec: torch.Tensor, T: int, env_first: int = 0, state_value: torch.Tensor | None = None,
+                       next_state_value: torch.Tensor | None = None):
+        """The critic's two passes of GAE over the records of a ``T``-step rollout, read where they lie (``forward_rows``: no slice, no staging copy):
+        ``state_value [T, B]`` from the root observations ``obs_rec [T, Bt, N, D]`` and ``next_state_value [T, B]`` from the observation part of the record rows
+        ``slab [T, Bt, W]``.  ``Bt >= env.B``: the buffers of the whole batch, of which ``env`` owns the envs ``[env_first, env_first + env.B)`` (an env shard;
+        ``Bt = env.B`` and 0 for a single handle).  Both sides are computed (as torchrl's GAE runs its value network on both); nothing is reused across steps."""
+        T, B, N, D = int(T), env.B, env.N, env.D
+        W, e0 = N * (D + 1) + 1, int(env_first)
+        if self.in_dim != N * D or self.out_dim != 1:
+            raise ValueError(f"the critic maps n_agents * obs_dim = {N * D} inputs to 1 value, not {self.in_dim} to {self.out_dim}")
+        if T < 1 or slab.dim() != 3 or slab.shape[0] < T or slab.shape[2] != W:
+            raise TypeError(f"slab must be [>= {T}, Bt, {W}]")
+        Bt = slab.shape[1]
+        if not 0 <= e0 <= Bt - B:
+            raise ValueError(f"envs [{e0}, {e0 + B}) are not inside the buffers' {Bt}")
+        if obs_rec.dim() < 2 or obs_rec.shape[0] < T or obs_rec.shape[1] != Bt or obs_rec[0, 0].numel() != N * D:
+            raise TypeError(f"obs_rec must be [>= {T}, {Bt}, {N}, {D}]")
+        sv = self.forward_rows(env, obs_rec, e0 * N * D, B, N * D, T, Bt * N * D, out=state_value)
+        nv = self.forward_rows(env, slab, e0 * W, B, W, T, Bt * W, out=next_state_value)
+        return sv.view(T, B), nv.view(T, B)
 
 
 def make_priority_mlp(obs_dim: int, hidden: int = 256) -> torch.nn.Sequential:
@@ -257,7 +310,7 @@ class Actor:
                 actions: torch.Tensor | None = None, seed: int = 0, counter0: int = 0, path_first: int | None = None, path_count: int | None = None,
                 deterministic: bool = False, precision: str | None = None, slab_ptr: int | None = None, wrapper: str | None = None,
                 priority=None, tentative: torch.Tensor | None = None, ranks: torch.Tensor | None = None, scores: torch.Tensor | None = None,
-                score_log_prob: torch.Tensor | None = None):
+                score_log_prob: torch.Tensor | None = None, obs_rec: torch.Tensor | None = None):
         """``n_steps`` x (policy -> fused step + record + resets) enqueued back to back; optional records ``slab [T,B,W]``,
         ``log_prob [T,B,N]``, ``actions [T,B,N,2]`` (CUDA float32, contiguous).  ``slab_ptr``: the record target as a raw device address instead of ``slab`` (an env
         shard's first row inside a ``[T, B_total, W]`` buffer of the whole batch, with ``env.set_rollout_slab_stride(B_total * W)``).  ``precision`` (default: the actor's): "fp32" = the reference's
@@ -267,8 +320,20 @@ class Actor:
         ``"plain"`` = the same through ``sigmaenv_rollout_f32_ex``; ``"opponent"`` = opponent modelling (the env needs ``is_using_opponent_modeling``);
         ``"prioritized"`` = prioritized action propagation (the actor takes obs_dim + 2 n_nearing inputs) with ``priority`` = a ``PriorityNet``, ``"random"``
         or a rank tensor [B,N] int32 (CUDA).  Records: ``tentative [T,B,N,K,2]`` (the neighbour actions the policy saw), ``ranks [T,B,N]`` int32,
-        ``scores`` / ``score_log_prob [T,B,N]`` (``PriorityNet`` only).  Step semantics: include/sigmaenv.h, sigmaenv_rollout_f32_ex."""
+        ``scores`` / ``score_log_prob [T,B,N]`` (``PriorityNet`` only).  Step semantics: include/sigmaenv.h, sigmaenv_rollout_f32_ex.
+
+        ``obs_rec [T,B,N,D]`` (any precision, any wrapper): the root observations -- row t = ``env.obs`` as the final actor forward of step t read it, i.e. the
+        ``observation`` of the collector's tensordict (the record row of step t - 1 holds it only where nothing was re-placed).  ``None``: the handle's setting is
+        left as it is (off unless ``env.set_rollout_obs_record`` set it, as an env shard that records into the whole batch's buffer does)."""
         check_rollout_wrapper(getattr(env, "parameters", None), wrapper)
+        if obs_rec is not None:
+            check_record(obs_rec, (int(n_steps), env.B, env.N, env.D), "obs_rec")
+            env.set_rollout_obs_record(obs_rec)
+            try:
+                return self.rollout(env, n_steps, slab, log_prob, actions, seed, counter0, path_first, path_count, deterministic, precision, slab_ptr, wrapper, priority,
+                                    tentative, ranks, scores, score_log_prob)
+            finally:
+                env.set_rollout_obs_record(None)  # (the copies are enqueued: the setting is only read while the loop enqueues)
         if path_first is None:
             path_first, path_count = env.default_paths()
         scratch = self._scratch_actions(env)

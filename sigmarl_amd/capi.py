@@ -94,6 +94,16 @@ class RolloutOpts(C.Structure):
     ]
 
 
+class GaeArgs(C.Structure):
+    """``sigmaenv_gae_args_t`` (sigmaenv_gae): the records and values of a rollout, the advantage / value-target / TD-priority outputs."""
+
+    _fields_ = [
+        ("n_steps", C.c_int32), ("reserved0", C.c_int32), ("slab", C.c_void_p), ("slab_stride", C.c_int64), ("state_value", C.c_void_p),
+        ("next_state_value", C.c_void_p), ("advantage", C.c_void_p), ("value_target", C.c_void_p), ("td_priority", C.c_void_p),
+        ("gamma", C.c_float), ("lmbda", C.c_float), ("td_gamma", C.c_float), ("reserved", C.c_int32 * 5),
+    ]
+
+
 # vehicle constants of the reference, sigmarl/constants.py:628-647
 AGENTS = {
     "width": 0.107, "length": 0.22, "l_f": 0.075, "l_r": 0.075, "l_wb": 0.15,
@@ -185,6 +195,7 @@ _PRODUCT_ONLY = {
     "kernel_time_ms": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_int32)]),
     "set_slab": (C.c_int, [C.c_void_p, C.c_void_p]),
     "set_rollout_slab_stride": (C.c_int, [C.c_void_p, C.c_int64]),
+    "set_rollout_obs_record": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64]),
     "trig_selftest": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
     "step_autoreset": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_int32, C.c_int32]),
     "step_autoreset_n": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_int64, C.c_uint64, C.c_uint64, C.c_int32, C.c_int32]),
@@ -195,6 +206,7 @@ _PRODUCT_ONLY = {
     "mlp32_create": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]),
     "mlp32_destroy": (None, [C.c_void_p]),
     "mlp32_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
+    "mlp32_forward_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_int64, C.c_void_p]),
     "mlp32_set_mode": (C.c_int, [C.c_void_p, C.c_int32]),
     "mlp32_get_mode": (C.c_int, [C.c_void_p]),
     "actor_forward_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64,
@@ -208,6 +220,7 @@ _PRODUCT_ONLY = {
     "priority_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_int32]),
     "priority_rank": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "priority_random": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p]),
+    "gae": (C.c_int, [C.c_void_p, C.POINTER(GaeArgs)]),
 }
 
 

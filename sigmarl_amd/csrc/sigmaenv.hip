@@ -1742,6 +1742,9 @@ struct sigmaenv {
   DevConfig cfg_derived;
   uint32_t observe_calls = 0;      // stand-alone sigmaenv_observe calls so far (the salt of their sensor noise)
   size_t rollout_slab_stride = 0;  // floats between the record blocks of consecutive steps of sigmaenv_rollout* (0: B * W)
+  float* rollout_obs_rec = nullptr;   // root-observation record of sigmaenv_rollout* (sigmaenv_set_rollout_obs_record): step t copies SIGMAENV_BUF_OBS to base + t * stride
+  size_t rollout_obs_stride = 0;      // floats between its blocks (0: B * N * D)
+  uint32_t* learn_minmax = nullptr;   // [2] bits of the min / max of sigmaenv_gae's raw TD errors (sigmaenv_learn.inc), allocated by the first call that asks for priorities
   int grid = 1;
   void* bufs[SIGMAENV_BUF_COUNT] = {nullptr};
   size_t buf_bytes[SIGMAENV_BUF_COUNT] = {0};
@@ -2506,6 +2509,16 @@ extern "C" int sigmaenv_set_rollout_slab_stride(sigmaenv_t* h, int64_t stride_fl
   return SIGMAENV_OK;
 }
 
+// Root-observation record of sigmaenv_rollout* (NULL: off); see include/sigmaenv.h
+extern "C" int sigmaenv_set_rollout_obs_record(sigmaenv_t* h, float* base, int64_t stride_floats) {
+  if (!h) return SIGMAENV_EINVAL;
+  const int64_t own = (int64_t)h->B * h->N * h->D;
+  if (stride_floats != 0 && stride_floats < own) { h->err = "set_rollout_obs_record: stride below the handle's own observation block B * N * D"; return SIGMAENV_EINVAL; }
+  h->rollout_obs_rec = base;
+  h->rollout_obs_stride = (size_t)stride_floats;
+  return SIGMAENV_OK;
+}
+
 // Diagnostics: copies the per-workgroup phase timestamps of the LAST step launch to `out` ([n_groups][8] u64); returns the number of
 // workgroups, 0 when SIGMAENV_TIMESTAMPS was not set at create.
 extern "C" int sigmaenv_debug_timestamps(sigmaenv_t* h, unsigned long long* out, int32_t max_groups) {
@@ -2565,4 +2578,5 @@ extern "C" int sigmaenv_trig_selftest(sigmaenv_t* h, int32_t kind, int32_t n, co
 #include "sigmaenv_actor.inc"
 #include "sigmaenv_mlp32.inc"
 #include "sigmaenv_wrappers.inc"
+#include "sigmaenv_learn.inc"
 #include "sigmaenv_cbf.inc"

@@ -303,6 +303,11 @@ static int rollout_loop(sigmaenv_t* h, Policy policy, int32_t n_steps, float* ac
     float* act = actions_rec ? actions_rec + (size_t)t * BN * 2 : actions_buf;
     int rc = policy(t, act, logp_base ? logp_base + (size_t)t * BN : nullptr);
     if (rc) return rc;
+    if (h->rollout_obs_rec) {  // the rows the step's final actor forward read (sigmaenv_set_rollout_obs_record): the step overwrites them
+      const size_t own = BN * (size_t)h->D;
+      HIPCHK(h, hipMemcpyAsync(h->rollout_obs_rec + (size_t)t * (h->rollout_obs_stride ? h->rollout_obs_stride : own), h->buf.obs, own * sizeof(float), hipMemcpyDeviceToDevice,
+                               h->stream));
+    }
     const float* step_act = act;
     if ((h->cfg.rew_flags & SIGMAENV_REW_CBF) && h->cbf_seg4) {  // CBFQP.update_qp between policy and step (helper_training.py:1616-1627)
       rc = sigmaenv_cbf_rewards(h, act, nullptr);

@@ -40,6 +40,44 @@ struct Mlp32Weights {
 // 16-byte fragments (bank-conflict free; with the row in front of the k parity every ds_read_b128 had 2-way conflicts: 64 % conflict cycles)
 __device__ __forceinline__ int mlp32_act_idx(int k, int row) { return ((((k >> 3) * 2 + (k & 1)) * MLP32_ROWS + row) << 2) + ((k & 7) >> 1); }
 
+// Where the network's rows are (sigmaenv_mlp32_forward_rows): row r = t * rpb + b at in + t * block_stride + b * row_stride (floats), e.g. the observation part of the
+// rows of a [T, B_total, W] rollout record.  aligned (launch-uniform, decided on the host): base and both strides are multiples of 4 floats -- 16-byte loads as in the
+// dense kernels; otherwise the rows are only 4-byte aligned (W = N (D + 1) + 1 is odd) and the tile is read through the realigning loads below.
+struct Mlp32Rows {
+  int rpb, aligned;
+  long long row_stride, block_stride;
+};
+template <bool ROWS>
+__device__ __forceinline__ const float* mlp32_row_ptr(const float* __restrict__ in, int row, int in_dim, const Mlp32Rows& rw) {
+  if constexpr (ROWS) {
+    const int t = row / rw.rpb, b = row - t * rw.rpb;
+    return in + (long long)t * rw.block_stride + (long long)b * rw.row_stride;
+  } else {
+    return in + (size_t)row * in_dim;
+  }
+}
+// Four (eight) floats at a 4-byte-aligned address p from 16-byte-ALIGNED loads: the granule that holds p[0] and the following one (two), each only when it holds
+// one of the wanted floats -- so no load touches a granule without a valid float, and an aligned granule never crosses a page --, the wanted floats selected by
+// s = the offset of p in its granule.  A row's lanes read consecutive granules: the requests coalesce as those of the aligned path do (3 loads per 8 floats, not 2).
+__device__ __forceinline__ float mlp32_sel4(int s, float a, float b, float c, float d) { return s == 0 ? a : s == 1 ? b : s == 2 ? c : d; }
+__device__ __forceinline__ float4 mlp32_ld4_realign(const float* p) {
+  const uintptr_t a = reinterpret_cast<uintptr_t>(p);
+  const int s = (int)((a >> 2) & 3);
+  const float4* g = reinterpret_cast<const float4*>(a & ~(uintptr_t)15);
+  const float4 w0 = g[0];
+  const float4 w1 = s ? g[1] : w0;
+  return make_float4(mlp32_sel4(s, w0.x, w0.y, w0.z, w0.w), mlp32_sel4(s, w0.y, w0.z, w0.w, w1.x), mlp32_sel4(s, w0.z, w0.w, w1.x, w1.y), mlp32_sel4(s, w0.w, w1.x, w1.y, w1.z));
+}
+__device__ __forceinline__ void mlp32_ld8_realign(const float* p, float4& lo, float4& hi) {
+  const uintptr_t a = reinterpret_cast<uintptr_t>(p);
+  const int s = (int)((a >> 2) & 3);
+  const float4* g = reinterpret_cast<const float4*>(a & ~(uintptr_t)15);
+  const float4 w0 = g[0], w1 = g[1];
+  const float4 w2 = s ? g[2] : w1;
+  lo = make_float4(mlp32_sel4(s, w0.x, w0.y, w0.z, w0.w), mlp32_sel4(s, w0.y, w0.z, w0.w, w1.x), mlp32_sel4(s, w0.z, w0.w, w1.x, w1.y), mlp32_sel4(s, w0.w, w1.x, w1.y, w1.z));
+  hi = make_float4(mlp32_sel4(s, w1.x, w1.y, w1.z, w1.w), mlp32_sel4(s, w1.y, w1.z, w1.w, w2.x), mlp32_sel4(s, w1.z, w1.w, w2.x, w2.y), mlp32_sel4(s, w1.w, w2.x, w2.y, w2.z));
+}
+
 // tanh without branches (the library tanhf is ~35 instructions with divergent range branches, 192 of them per lane and forward were the kernel's
 // vector work): |x| < 0.3: the odd Taylor polynomial through x^9 (truncation < 6e-8 relative); else 1 - 2 / (exp(2 |x|) + 1) with the hardware exp2 /
 // rcp (1 ulp each), sign restored.  <= ~4 ulp (1.1e-7 absolute) against the correctly rounded tanh -- torch's own vectorised tanh is a 1-ulp routine --,
@@ -95,7 +133,12 @@ __device__ __forceinline__ void mlp32_tile_k256(const float4* __restrict__ wa, c
 #define MLP32_TS_ARG
 #define MLP32_TS(k) do { } while (0)
 #endif
-__global__ void __launch_bounds__(256, 2) sigmaenv_mlp32_kernel(Mlp32Weights mw, const float* __restrict__ in, int R, int in_dim, float* __restrict__ out MLP32_TS_ARG) {
+// ROWS = false: `in` is dense [R][in_dim], 16-byte aligned (sigmaenv_mlp32_forward, the actor forwards, the rollouts; rw is not read); ROWS = true: the rows of a
+// record (Mlp32Rows, sigmaenv_mlp32_forward_rows).  Only the row addresses and loads of stage() differ.  Two instantiations of the KERNEL, not one body inlined
+// into two kernels: the dense one then compiles to what it was before the strided one existed (236 VGPRs, no scratch; as an inlined body it took 256 VGPRs and
+// 128 bytes of scratch per lane -- tools/kernel_resources.sh)
+template <bool ROWS>
+__global__ void __launch_bounds__(256, 2) sigmaenv_mlp32_kernel(Mlp32Weights mw, const float* __restrict__ in, int R, int in_dim, float* __restrict__ out, Mlp32Rows rw MLP32_TS_ARG) {
   sigma_poison_lds();
   MLP32_TS(0);
 #ifdef SIGMAENV_PROFILE
@@ -138,7 +181,14 @@ __global__ void __launch_bounds__(256, 2) sigmaenv_mlp32_kernel(Mlp32Weights mw,
         const int n = e / Q, kl = (e - n * Q) << 2, k = c0 + kl;
         const int row = row0 + n;
         float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (row < R && k < in_dim) v = reinterpret_cast<const float4*>(in + (size_t)row * in_dim)[k >> 2];
+        if (row < R && k < in_dim) {
+          if constexpr (ROWS) {
+            const float* src = mlp32_row_ptr<true>(in, row, in_dim, rw) + k;
+            v = rw.aligned ? reinterpret_cast<const float4*>(src)[0] : mlp32_ld4_realign(src);
+          } else {
+            v = reinterpret_cast<const float4*>(in + (size_t)row * in_dim)[k >> 2];
+          }
+        }
         // columns k, k + 2 share a fragment (k parity 0), k + 1, k + 3 the one 64 fragments further (mlp32_act_idx)
         float* d = x + mlp32_act_idx(kl, n);
         *reinterpret_cast<float2*>(d) = make_float2(v.x, v.z);
@@ -148,7 +198,7 @@ __global__ void __launch_bounds__(256, 2) sigmaenv_mlp32_kernel(Mlp32Weights mw,
       for (int e = tid; e < cw * MLP32_ROWS; e += blockDim.x) {            // (coalesced along k within a row)
         const int n = e / cw, kl = e - n * cw, k = c0 + kl;
         const int row = row0 + n;
-        x[mlp32_act_idx(kl, n)] = (row < R && k < in_dim) ? in[(size_t)row * in_dim + k] : 0.0f;
+        x[mlp32_act_idx(kl, n)] = (row < R && k < in_dim) ? mlp32_row_ptr<ROWS>(in, row, in_dim, rw)[k] : 0.0f;
       }
     }
   };
@@ -405,10 +455,29 @@ extern "C" int sigmaenv_mlp32_set_mode(sigmaenv_mlp32* m, int32_t mode) {
 extern "C" int sigmaenv_mlp32_get_mode(const sigmaenv_mlp32* m) { return m ? m->mode : SIGMAENV_EINVAL; }
 
 // out[rows, out_dim] := mlp(in[rows, in_dim]) in fp32 (device pointers), enqueued on the handle's stream
-static int mlp32_forward_impl(sigmaenv_t* h, sigmaenv_mlp32* m, const float* in, int32_t rows, float* out, const Mlp32sHead* head, bool* head_done);
+static int mlp32_forward_impl(sigmaenv_t* h, sigmaenv_mlp32* m, const float* in, int32_t rows, float* out, const Mlp32sHead* head, bool* head_done, const Mlp32Rows* rw = nullptr);
 extern "C" int sigmaenv_mlp32_forward(sigmaenv_t* h, sigmaenv_mlp32* m, const float* in, int32_t rows, float* out) { return mlp32_forward_impl(h, m, in, rows, out, nullptr, nullptr); }
+// The network on rows that are not dense: row r = t * rows_per_block + b at in + t * block_stride + b * row_stride (floats), 4-byte alignment suffices; out is
+// dense.  The staging of the input tile is the only difference to sigmaenv_mlp32_forward (the *_rows_kernel instantiations): same bits per row in both modes.
+extern "C" int sigmaenv_mlp32_forward_rows(sigmaenv_t* h, sigmaenv_mlp32* m, const float* in, int32_t rows_per_block, int64_t row_stride, int32_t n_blocks, int64_t block_stride,
+                                           float* out) {
+  if (!h || !m || !in || !out || rows_per_block < 0 || n_blocks < 0) return SIGMAENV_EINVAL;
+  if ((int64_t)rows_per_block * n_blocks > INT32_MAX) { h->err = "mlp32_forward_rows: more than 2^31 - 1 rows"; return SIGMAENV_EINVAL; }
+  if (rows_per_block == 0 || n_blocks == 0) return SIGMAENV_OK;
+  if (row_stride < m->in_dim || ((uintptr_t)in & 3) || (n_blocks > 1 && block_stride < 0)) {
+    h->err = "mlp32_forward_rows: row_stride below the network's input width, a negative block_stride or an input that is not 4-byte aligned";
+    return SIGMAENV_EINVAL;
+  }
+  Mlp32Rows rw;
+  rw.rpb = rows_per_block;
+  rw.row_stride = row_stride;
+  rw.block_stride = block_stride;
+  rw.aligned = ((uintptr_t)in & 15) == 0 && (row_stride & 3) == 0 && (block_stride & 3) == 0;
+  return mlp32_forward_impl(h, m, in, rows_per_block * n_blocks, out, nullptr, nullptr, &rw);
+}
 // head: the actor's distribution head, run as the epilogue of the split-mode kernel (*head_done = true) -- the exact mode leaves it to the caller's head launch
-static int mlp32_forward_impl(sigmaenv_t* h, sigmaenv_mlp32* m, const float* in, int32_t rows, float* out, const Mlp32sHead* head, bool* head_done) {
+// rw: the rows' addresses (sigmaenv_mlp32_forward_rows); nullptr: dense
+static int mlp32_forward_impl(sigmaenv_t* h, sigmaenv_mlp32* m, const float* in, int32_t rows, float* out, const Mlp32sHead* head, bool* head_done, const Mlp32Rows* rw) {
   if (head_done) *head_done = false;
   if (!h || !m || !in || !out || rows < 0) return SIGMAENV_EINVAL;
   if (rows == 0) return SIGMAENV_OK;
@@ -416,12 +485,14 @@ static int mlp32_forward_impl(sigmaenv_t* h, sigmaenv_mlp32* m, const float* in,
   if (m->mode == SIGMAENV_MLP32_SPLIT) {
     // the dynamic-LDS limit is a per-kernel attribute -- PER DEVICE (ADVICE r5: a second GPU driven from the same process never got the opt-in beyond 64 KB): raised
     // when a model needs more than what was set for this device before (not once per forward); atomics: handles may be driven from several threads
-    static std::atomic<size_t> s_split_lds_set[64];
+    static std::atomic<size_t> s_split_lds_set[2][64];  // [dense | record rows]: two kernels
     const int dslot = h->device >= 0 && h->device < 64 ? h->device : 0;
-    if (m->smem_s > 64 * 1024 && m->smem_s > s_split_lds_set[dslot].load(std::memory_order_acquire)) {
-      HIPCHK(h, hipFuncSetAttribute(reinterpret_cast<const void*>(sigmaenv_mlp32s_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)m->smem_s));
-      size_t cur = s_split_lds_set[dslot].load(std::memory_order_relaxed);
-      while (cur < m->smem_s && !s_split_lds_set[dslot].compare_exchange_weak(cur, m->smem_s, std::memory_order_release)) {}
+    const void* kfn = rw ? reinterpret_cast<const void*>(sigmaenv_mlp32s_kernel<true>) : reinterpret_cast<const void*>(sigmaenv_mlp32s_kernel<false>);
+    std::atomic<size_t>& lds_set = s_split_lds_set[rw ? 1 : 0][dslot];
+    if (m->smem_s > 64 * 1024 && m->smem_s > lds_set.load(std::memory_order_acquire)) {
+      HIPCHK(h, hipFuncSetAttribute(kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)m->smem_s));
+      size_t cur = lds_set.load(std::memory_order_relaxed);
+      while (cur < m->smem_s && !lds_set.compare_exchange_weak(cur, m->smem_s, std::memory_order_release)) {}
     }
     Mlp32sHead hd_{};
     if (head && m->out_dim == 4) { hd_ = *head; hd_.on = 1; if (head_done) *head_done = true; }
@@ -438,18 +509,22 @@ static int mlp32_forward_impl(sigmaenv_t* h, sigmaenv_mlp32* m, const float* in,
     size_t smem_l = m->smem_s;
     if (getenv("SIGMAENV_MLP32_ONE_WG")) {  // diagnostic: one workgroup per CU (more LDS than two can share)
       smem_l = 100 * 1024 > smem_l ? 100 * 1024 : smem_l;
-      HIPCHK(h, hipFuncSetAttribute(reinterpret_cast<const void*>(sigmaenv_mlp32s_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem_l));
+      HIPCHK(h, hipFuncSetAttribute(kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem_l));
     }
-    hipLaunchKernelGGL(sigmaenv_mlp32s_kernel, dim3((rows + MLP32_ROWS - 1) / MLP32_ROWS), dim3(256), smem_l, h->stream, m->ws, in, (int)rows, m->in_dim, out, hd_, m->ts, getenv("SIGMAENV_MLP32_STAGGER") ? atoi(getenv("SIGMAENV_MLP32_STAGGER")) : 0);
+    const int stagger_l = getenv("SIGMAENV_MLP32_STAGGER") ? atoi(getenv("SIGMAENV_MLP32_STAGGER")) : 0;
+    if (rw) hipLaunchKernelGGL(sigmaenv_mlp32s_kernel<true>, dim3((rows + MLP32_ROWS - 1) / MLP32_ROWS), dim3(256), smem_l, h->stream, m->ws, in, (int)rows, m->in_dim, out, hd_, *rw, m->ts, stagger_l);
+    else hipLaunchKernelGGL(sigmaenv_mlp32s_kernel<false>, dim3((rows + MLP32_ROWS - 1) / MLP32_ROWS), dim3(256), smem_l, h->stream, m->ws, in, (int)rows, m->in_dim, out, hd_, Mlp32Rows{}, m->ts, stagger_l);
 #else
-    hipLaunchKernelGGL(sigmaenv_mlp32s_kernel, dim3((rows + MLP32_ROWS - 1) / MLP32_ROWS), dim3(256), m->smem_s, h->stream, m->ws, in, (int)rows, m->in_dim, out, hd_);
+    if (rw) hipLaunchKernelGGL(sigmaenv_mlp32s_kernel<true>, dim3((rows + MLP32_ROWS - 1) / MLP32_ROWS), dim3(256), m->smem_s, h->stream, m->ws, in, (int)rows, m->in_dim, out, hd_, *rw);
+    else hipLaunchKernelGGL(sigmaenv_mlp32s_kernel<false>, dim3((rows + MLP32_ROWS - 1) / MLP32_ROWS), dim3(256), m->smem_s, h->stream, m->ws, in, (int)rows, m->in_dim, out, hd_, Mlp32Rows{});
 #endif
     HIPCHK(h, hipGetLastError());
     timer_end(h, SIGMAENV_KERNEL_MLP32, slot);
     return SIGMAENV_OK;
   }
   // the dynamic-LDS limit is a per-kernel attribute: set for THIS model right before its launch (models of different input widths coexist)
-  if (m->smem > 64 * 1024) HIPCHK(h, hipFuncSetAttribute(reinterpret_cast<const void*>(sigmaenv_mlp32_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)m->smem));
+  const void* kfn = rw ? reinterpret_cast<const void*>(sigmaenv_mlp32_kernel<true>) : reinterpret_cast<const void*>(sigmaenv_mlp32_kernel<false>);
+  if (m->smem > 64 * 1024) HIPCHK(h, hipFuncSetAttribute(kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)m->smem));
   const int slot = timer_begin(h, SIGMAENV_KERNEL_MLP32);
 #ifdef SIGMAENV_PROFILE
   {
@@ -463,11 +538,14 @@ static int mlp32_forward_impl(sigmaenv_t* h, sigmaenv_mlp32* m, const float* in,
   size_t smem_l = m->smem;
   if (getenv("SIGMAENV_MLP32_ONE_WG")) {  // diagnostic: one workgroup per CU (more LDS than two can share)
     smem_l = 100 * 1024;
-    HIPCHK(h, hipFuncSetAttribute(reinterpret_cast<const void*>(sigmaenv_mlp32_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem_l));
+    HIPCHK(h, hipFuncSetAttribute(kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem_l));
   }
-  hipLaunchKernelGGL(sigmaenv_mlp32_kernel, dim3((rows + MLP32_ROWS - 1) / MLP32_ROWS), dim3(256), smem_l, h->stream, m->w, in, (int)rows, m->in_dim, out, m->ts, getenv("SIGMAENV_MLP32_STAGGER") ? atoi(getenv("SIGMAENV_MLP32_STAGGER")) : 0);
+  const int stagger_l = getenv("SIGMAENV_MLP32_STAGGER") ? atoi(getenv("SIGMAENV_MLP32_STAGGER")) : 0;
+  if (rw) hipLaunchKernelGGL(sigmaenv_mlp32_kernel<true>, dim3((rows + MLP32_ROWS - 1) / MLP32_ROWS), dim3(256), smem_l, h->stream, m->w, in, (int)rows, m->in_dim, out, *rw, m->ts, stagger_l);
+  else hipLaunchKernelGGL(sigmaenv_mlp32_kernel<false>, dim3((rows + MLP32_ROWS - 1) / MLP32_ROWS), dim3(256), smem_l, h->stream, m->w, in, (int)rows, m->in_dim, out, Mlp32Rows{}, m->ts, stagger_l);
 #else
-  hipLaunchKernelGGL(sigmaenv_mlp32_kernel, dim3((rows + MLP32_ROWS - 1) / MLP32_ROWS), dim3(256), m->smem, h->stream, m->w, in, (int)rows, m->in_dim, out);
+  if (rw) hipLaunchKernelGGL(sigmaenv_mlp32_kernel<true>, dim3((rows + MLP32_ROWS - 1) / MLP32_ROWS), dim3(256), m->smem, h->stream, m->w, in, (int)rows, m->in_dim, out, *rw);
+  else hipLaunchKernelGGL(sigmaenv_mlp32_kernel<false>, dim3((rows + MLP32_ROWS - 1) / MLP32_ROWS), dim3(256), m->smem, h->stream, m->w, in, (int)rows, m->in_dim, out, Mlp32Rows{});
 #endif
   HIPCHK(h, hipGetLastError());
   timer_end(h, SIGMAENV_KERNEL_MLP32, slot);

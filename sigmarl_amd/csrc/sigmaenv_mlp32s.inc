@@ -95,7 +95,11 @@ struct Mlp32sHead {
   uint64_t seed, counter;
   const int32_t* row_map;
 };
-__global__ void __launch_bounds__(256, 2) sigmaenv_mlp32s_kernel(Mlp32sWeights mw, const float* __restrict__ in, int R, int in_dim, float* __restrict__ out, Mlp32sHead hd MLP32_TS_ARG) {
+// ROWS: as sigmaenv_mlp32_kernel -- false: `in` is dense [R][in_dim], 16-byte aligned (rw is not read); true: the rows of a record (sigmaenv_mlp32_forward_rows).
+// Only the input-tile staging differs; the dense instantiation compiles to what the kernel was before the strided one existed (216 VGPRs, no scratch).
+template <bool ROWS>
+__global__ void __launch_bounds__(256, 2) sigmaenv_mlp32s_kernel(Mlp32sWeights mw, const float* __restrict__ in, int R, int in_dim, float* __restrict__ out, Mlp32sHead hd,
+                                                                 Mlp32Rows rw MLP32_TS_ARG) {
   sigma_poison_lds();
   MLP32_TS(0);
 #ifdef SIGMAENV_PROFILE
@@ -128,7 +132,14 @@ __global__ void __launch_bounds__(256, 2) sigmaenv_mlp32s_kernel(Mlp32sWeights m
       const int r = e / Q0, c8 = e - r * Q0, k = c8 << 3, row = row0 + r;
       f16x8_t vh, vl;
       if (row < R && k < in_dim) {
-        const float4 lo4 = reinterpret_cast<const float4*>(in + (size_t)row * in_dim + k)[0], hi4 = reinterpret_cast<const float4*>(in + (size_t)row * in_dim + k)[1];
+        float4 lo4, hi4;
+        if constexpr (ROWS) {
+          const float* src = mlp32_row_ptr<true>(in, row, in_dim, rw) + k;
+          if (rw.aligned) { lo4 = reinterpret_cast<const float4*>(src)[0]; hi4 = reinterpret_cast<const float4*>(src)[1]; }
+          else mlp32_ld8_realign(src, lo4, hi4);
+        } else {
+          lo4 = reinterpret_cast<const float4*>(in + (size_t)row * in_dim + k)[0]; hi4 = reinterpret_cast<const float4*>(in + (size_t)row * in_dim + k)[1];
+        }
         const float v[8] = {lo4.x, lo4.y, lo4.z, lo4.w, hi4.x, hi4.y, hi4.z, hi4.w};
 #pragma unroll
         for (int j = 0; j < 8; ++j) { _Float16 a16, b16; mlp32s_split(mlp32s_sat(v[j] * MLP32S_SX0), a16, b16); vh[j] = a16; vl[j] = b16; }
@@ -144,7 +155,7 @@ __global__ void __launch_bounds__(256, 2) sigmaenv_mlp32s_kernel(Mlp32sWeights m
     const int K0 = KB0 * 16;
     for (int e = tid; e < K0 * MLP32_ROWS; e += 256) {
       const int r = e / K0, k = e - r * K0, row = row0 + r;
-      const float v = (row < R && k < in_dim) ? mlp32s_sat(in[(size_t)row * in_dim + k] * MLP32S_SX0) : 0.0f;
+      const float v = (row < R && k < in_dim) ? mlp32s_sat(mlp32_row_ptr<ROWS>(in, row, in_dim, rw)[k] * MLP32S_SX0) : 0.0f;
       _Float16 a16, b16;
       mlp32s_split(v, a16, b16);
       const size_t f = (size_t)(k >> 4) * 256 + ((k >> 3) & 1) * 64 + r;

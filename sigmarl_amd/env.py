@@ -367,6 +367,17 @@ class SigmaEnv:
         a ``[T, B_total, W]`` buffer of the whole batch passes ``B_total * W`` here and the address of its first row as the rollout's slab pointer."""
         self._chk(self.lib.set_rollout_slab_stride(self.h, int(stride_floats)), "set_rollout_slab_stride")
 
+    def set_rollout_obs_record(self, rec=None, stride_floats: int = 0):
+        """Root-observation record of ``Actor.rollout`` (``sigmaenv_set_rollout_obs_record``): step t copies ``env.obs`` -- the rows the step's final actor forward
+        read -- to ``rec + t * stride_floats`` before the step.  ``rec``: ``None`` (off), a contiguous float32 CUDA tensor whose first ``T * B * N * D`` floats
+        are the record, or a raw device address (an env shard's first row inside a ``[T, B_total, N, D]`` buffer, with ``stride_floats = B_total * N * D``).
+        The setting stays until it is changed; ``Actor.rollout(obs_rec=...)`` sets it for one call."""
+        if isinstance(rec, torch.Tensor):
+            if not (rec.is_cuda and rec.dtype == torch.float32 and rec.is_contiguous()):
+                raise TypeError("the observation record must be a contiguous float32 CUDA tensor")
+            rec = rec.data_ptr()
+        self._chk(self.lib.set_rollout_obs_record(self.h, C.c_void_p(int(rec)) if rec else None, int(stride_floats)), "set_rollout_obs_record")
+
     # pointer-level variants for rollout loops that precompute their device addresses (no per-call tensor checks / views)
     def set_slab_ptr(self, ptr: int):
         self._chk(self.lib.set_slab(self.h, C.c_void_p(ptr)), "set_slab")
