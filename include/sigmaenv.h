@@ -330,6 +330,21 @@ int sigmaenv_step_time_ms(sigmaenv_t* h, double* avg_ms, int32_t* n_launches);
 #define SIGMAENV_KERNEL_COUNT 5
 int sigmaenv_kernel_time_ms(sigmaenv_t* h, int32_t kernel_id, double* avg_ms, int32_t* n_launches);
 
+/* What the handle launches (read-only; decided once in sigmaenv_create from the configuration, the device and the diagnostic switches of README.md): the step
+ * kernel's tiling -- wave_G envs per wavefront tile, wave_wpb tiles per workgroup, wave_grid workgroups, wave_spec = agents * 256 + envs of a fixed-shape
+ * instantiation or 0, wave_lds_bytes of LDS per workgroup -- and the template arguments of the sigmaenv_step_wave_kernel instantiation that sigmaenv_step* launch
+ * (kern_*: the very selection the launch uses); whether the map took the shared-reciprocal division and the pruned boundary scan; the tiling of the stand-alone
+ * observe / reset kernels (G envs per workgroup of `block` threads, `grid` workgroups, reset_block threads per reset workgroup, smem_bytes of LDS).
+ * Lets a test assert the tile shape it means to exercise instead of assuming it. */
+typedef struct sigmaenv_launch_shape {
+  int32_t wave_G, wave_wpb, wave_grid, wave_spec, wave_lds_bytes;
+  int32_t kern_fastdiv, kern_par, kern_sn, kern_sg, kern_var, kern_mtvs; /* <FASTDIV, PAR, SN, SG, VAR, MTVS> */
+  int32_t map_fast_div, pruned_scan;
+  int32_t G, block, grid, reset_block, smem_bytes;
+  int32_t reserved[2];
+} sigmaenv_launch_shape_t;
+int sigmaenv_launch_shape(const sigmaenv_t* h, sigmaenv_launch_shape_t* out);
+
 /* The device side of the arithmetic contract's trigonometry (include/sigma_trig_f32.h; torch.sin / cos / tan / atan as called by
  * sigmarl/dynamics.py:103-111,161-168 and helper_scenario.py:795-810), evaluated on arrays: kind 0 sin, 1 cos, 2 tan, 3 atan of
  * in[0..n) -> out[0..n) (device pointers, f32).  Lets the GPU test-suite hold the device functions to the same bits as the host's. */

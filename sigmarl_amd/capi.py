@@ -104,6 +104,14 @@ class GaeArgs(C.Structure):
     ]
 
 
+class LaunchShape(C.Structure):
+    """``sigmaenv_launch_shape_t`` (sigmaenv_launch_shape): the tilings the handle launches and the step kernel's instantiation."""
+
+    _fields_ = [(n, C.c_int32) for n in (
+        "wave_G", "wave_wpb", "wave_grid", "wave_spec", "wave_lds_bytes", "kern_fastdiv", "kern_par", "kern_sn", "kern_sg", "kern_var", "kern_mtvs",
+        "map_fast_div", "pruned_scan", "G", "block", "grid", "reset_block", "smem_bytes")] + [("reserved", C.c_int32 * 2)]
+
+
 # vehicle constants of the reference, sigmarl/constants.py:628-647
 AGENTS = {
     "width": 0.107, "length": 0.22, "l_f": 0.075, "l_r": 0.075, "l_wb": 0.15,
@@ -221,6 +229,7 @@ _PRODUCT_ONLY = {
     "priority_rank": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "priority_random": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p]),
     "gae": (C.c_int, [C.c_void_p, C.POINTER(GaeArgs)]),
+    "launch_shape": (C.c_int, [C.c_void_p, C.POINTER(LaunchShape)]),
 }
 
 

@@ -2358,6 +2358,53 @@ static void timer_end(sigmaenv* h, int id, int slot) {
   if (slot >= 0) (void)hipEventRecord(h->timers[id].pool[slot].second, h->stream);
 }
 
+// The step kernel's instantiation for a handle: the function to launch together with its template arguments, so that what sigmaenv_launch_shape reports
+// is what launch_step launches (one selection, two readers).
+using StepKernFn = void (*)(const sigmaenv_config_t*, StepKernArgs);
+struct StepKernChoice {
+  StepKernFn fn;
+  bool fastdiv, par;
+  int sn, sg;
+  bool var, mtvs;
+};
+template <bool FASTDIV, bool PAR, int SN = 0, int SG = 0, bool VAR = false, bool MTVS = false>
+static StepKernChoice step_kern() { return {sigmaenv_step_wave_kernel<FASTDIV, PAR, SN, SG, VAR, MTVS>, FASTDIV, PAR, SN, SG, VAR, MTVS}; }
+
+static StepKernChoice select_step_kernel(const sigmaenv* h) {
+  // instantiations: exact shared-reciprocal division or plain `/` in the scan (DevMap::fast_div), lane pair per agent in the dynamics or not
+  const bool par = 2 * h->wave_G * h->N <= 64;
+  StepKernChoice kern = h->map.fast_div ? (par ? step_kern<true, true>() : step_kern<true, false>()) : (par ? step_kern<false, true>() : step_kern<false, false>());
+  if (h->cfg.obs_flags != 0 && h->map.fast_div && h->wave_spec == 16 * 256 + 1) kern = step_kern<true, true, 16, 1, true>();
+  else if (h->cfg.obs_flags != 0)  // the instantiations that carry the non-default observation rows
+    kern = h->map.fast_div ? (par ? step_kern<true, true, 0, 0, true>() : step_kern<true, false, 0, 0, true>())
+                           : (par ? step_kern<false, true, 0, 0, true>() : step_kern<false, false, 0, 0, true>());
+  if (h->map.fast_div && h->cfg.obs_flags == 0) {  // fixed-shape instantiations (the plain-division variant of a map with degenerate segments stays generic)
+    switch (h->wave_spec) {
+      case 16 * 256 + 1: kern = step_kern<true, true, 16, 1>(); break;
+      case 32 * 256 + 1: kern = step_kern<true, true, 32, 1>(); break;
+      case 8 * 256 + 2: kern = step_kern<true, true, 8, 2>(); break;
+      case 4 * 256 + 4: kern = step_kern<true, true, 4, 4>(); break;
+      default: break;
+    }
+  }
+  if (h->cfg.distance_type != SIGMAENV_DIST_C2C && h->map.fast_div && h->wave_spec == 16 * 256 + 1)  // mtv at the metric's shape: per-rectangle records staged per agent
+    kern = h->cfg.obs_flags != 0 ? step_kern<true, true, 16, 1, true, true>() : step_kern<true, true, 16, 1, false, true>();
+  return kern;
+}
+
+extern "C" int sigmaenv_launch_shape(const sigmaenv_t* h, sigmaenv_launch_shape_t* out) {
+  if (!h || !out) return SIGMAENV_EINVAL;
+  const StepKernChoice k = select_step_kernel(h);
+  *out = sigmaenv_launch_shape_t{};
+  out->wave_G = h->wave_G; out->wave_wpb = h->wave_wpb; out->wave_grid = h->wave_grid; out->wave_spec = h->wave_spec;
+  out->wave_lds_bytes = (int32_t)(h->wave_tile_lds * h->wave_wpb);
+  out->kern_fastdiv = k.fastdiv; out->kern_par = k.par; out->kern_sn = k.sn; out->kern_sg = k.sg; out->kern_var = k.var; out->kern_mtvs = k.mtvs;
+  out->map_fast_div = h->map.fast_div ? 1 : 0;
+  out->pruned_scan = h->map.nch != 0;
+  out->G = h->G; out->block = h->block; out->grid = h->grid; out->reset_block = h->reset_block; out->smem_bytes = (int32_t)h->smem_bytes;
+  return SIGMAENV_OK;
+}
+
 // n_steps launches' worth of fused steps in ONE launch when n_steps > 1 (sigmaenv_step_autoreset_n): step t reads actions + t * act_stride, draws its
 // resets from counter + t and records into slab + t * slab_stride (floats)
 static int launch_step(sigmaenv* h, const float* actions, uint64_t seed, uint64_t counter, int path_first, int path_count, int n_steps = 1, size_t act_stride = 0,
@@ -2367,25 +2414,7 @@ static int launch_step(sigmaenv* h, const float* actions, uint64_t seed, uint64_
   HIPCHK(h, hipSetDevice(h->device));  // handles on several GPUs may live in one process: every entry point that enqueues work selects its device
   const int slot = timer_begin(h, SIGMAENV_KERNEL_STEP);
   {
-    // instantiations: exact shared-reciprocal division or plain `/` in the scan (DevMap::fast_div), lane pair per agent in the dynamics or not
-    const bool par = 2 * h->wave_G * h->N <= 64;
-    auto kern = h->map.fast_div ? (par ? sigmaenv_step_wave_kernel<true, true> : sigmaenv_step_wave_kernel<true, false>)
-                                : (par ? sigmaenv_step_wave_kernel<false, true> : sigmaenv_step_wave_kernel<false, false>);
-    if (h->cfg.obs_flags != 0 && h->map.fast_div && h->wave_spec == 16 * 256 + 1) kern = sigmaenv_step_wave_kernel<true, true, 16, 1, true>;
-    else if (h->cfg.obs_flags != 0)  // the instantiations that carry the non-default observation rows
-      kern = h->map.fast_div ? (par ? sigmaenv_step_wave_kernel<true, true, 0, 0, true> : sigmaenv_step_wave_kernel<true, false, 0, 0, true>)
-                             : (par ? sigmaenv_step_wave_kernel<false, true, 0, 0, true> : sigmaenv_step_wave_kernel<false, false, 0, 0, true>);
-    if (h->map.fast_div && h->cfg.obs_flags == 0) {  // fixed-shape instantiations (the plain-division variant of a map with degenerate segments stays generic)
-      switch (h->wave_spec) {
-        case 16 * 256 + 1: kern = sigmaenv_step_wave_kernel<true, true, 16, 1>; break;
-        case 32 * 256 + 1: kern = sigmaenv_step_wave_kernel<true, true, 32, 1>; break;
-        case 8 * 256 + 2: kern = sigmaenv_step_wave_kernel<true, true, 8, 2>; break;
-        case 4 * 256 + 4: kern = sigmaenv_step_wave_kernel<true, true, 4, 4>; break;
-        default: break;
-      }
-    }
-    if (h->cfg.distance_type != SIGMAENV_DIST_C2C && h->map.fast_div && h->wave_spec == 16 * 256 + 1)  // mtv at the metric's shape: per-rectangle records staged per agent
-      kern = h->cfg.obs_flags != 0 ? sigmaenv_step_wave_kernel<true, true, 16, 1, true, true> : sigmaenv_step_wave_kernel<true, true, 16, 1, false, true>;
+    const StepKernFn kern = select_step_kernel(h).fn;
     const StepKernArgs ka{h->map, h->buf, actions, slab, act_stride, slab_stride, seed, counter, h->wave_G, (int)h->wave_tile_lds, path_first, path_count, n_steps};
     hipLaunchKernelGGL(kern, dim3(h->wave_grid), dim3(64 * h->wave_wpb), h->wave_tile_lds * h->wave_wpb, h->stream, (const sigmaenv_config_t*)h->d_cfg, ka);
   }

@@ -388,6 +388,16 @@ class SigmaEnv:
     def sync(self):
         self._chk(self.lib.sync(self.h), "sync")
 
+    def launch_shape(self) -> dict:
+        """What the handle launches (``sigmaenv_launch_shape``): the step kernel's tiling (``wave_G`` envs per wavefront tile, ``wave_wpb`` tiles per workgroup,
+        ``wave_grid``, ``wave_spec``, ``wave_lds_bytes``), its instantiation (``kern_*``: the template arguments, and ``instantiation``: them as a tuple
+        ``(FASTDIV, PAR, SN, SG, VAR, MTVS)``), ``map_fast_div``, ``pruned_scan`` and the stand-alone kernels' ``G``, ``block``, ``grid``, ``reset_block``."""
+        ls = capi.LaunchShape()
+        self._chk(self.lib.launch_shape(self.h, C.byref(ls)), "launch_shape")
+        d = {n: int(getattr(ls, n)) for n, _ in capi.LaunchShape._fields_ if n != "reserved"}
+        d["instantiation"] = (bool(d["kern_fastdiv"]), bool(d["kern_par"]), d["kern_sn"], d["kern_sg"], bool(d["kern_var"]), bool(d["kern_mtvs"]))
+        return d
+
     def kernel_time_ms(self, kernel_id: int):
         """(average ms, launches) of the HIP-event brackets of kernel ``capi.KERNEL_*`` since the last call; the first call arms the bracketing."""
         avg = C.c_double()

@@ -27,6 +27,26 @@ def test_fuzz_parity_64_configurations_fixed_seed():
     assert steps > 50_000 and diff == 0
 
 
+def test_fuzz_parity_32_configurations_with_random_tilings():
+    """The same random configurations machinery with a tiling of the step kernel drawn per case by a second generator (envs per wavefront tile through
+    cfg.envs_per_group, tiles per workgroup, fixed-shape or generic instantiation), applied and read back with launch_shape() -- the same assertions."""
+    import fuzz_parity as fp
+
+    rng, tiling_rng = np.random.default_rng(20261016), np.random.default_rng(16102026)
+    steps = diff = multi = 0
+    for k in range(32):
+        tag, n, d = fp.one_case(rng, k, tiling_rng)
+        print(tag.split(" is_use_mtv")[0])
+        steps += n
+        diff += d
+        multi += " x 1," not in tag
+        assert d == 0, f"{d} differing non-observation fp32 words in {tag}"
+    assert steps > 25_000 and diff == 0  # (half the cases of the test above, half its bound)
+    # envs_per_group is uniform in 1 .. 64 // N: one env per wavefront has probability <= N / 64 for N <= 32, and most agent counts are below 20 -- a quarter of the
+    # cases with several envs on a wavefront is a loose lower bound that only a broken draw (or a tiling that is not applied) misses
+    assert multi >= 8
+
+
 def _run_cbf(seed, n_cases, cpm_agents, forced=()):
     import fuzz_cbf as fc
 

@@ -782,12 +782,21 @@ def test_compiled_custom_map_runs_through_both_paths():
 ])
 def test_soak_other_tile_shapes(scen, N, B, T, mtv, rew, testing):
     """The one-launch path at the other tile shapes (fixed-shape instantiations 4 x 4, 8 x 2, 32 x 1 and the generic kernel) against the
-    oracle over long mixed-action runs, every buffer after every step."""
+    oracle over long mixed-action runs, every buffer after every step.  At these batch sizes the library's own rule gives one env per wavefront, so the
+    4 x 4 / 8 x 2 / 32 x 1 tiles are asked for through cfg.envs_per_group, and every row asserts with launch_shape() the instantiation it names."""
     p = Parameters(n_agents=N, scenario_type=scen, is_use_mtv_distance=mtv, rew_method=rew, dt=0.05, is_apply_mask=False, is_obs_noise=False, max_steps=30,
                    is_testing_mode=testing)
     mp = load_map(scen)
     cfg = make_config(p, mp, B)
+    wave_g = {4: 4, 8: 2, 32: 1}.get(N, 0)
+    cfg.envs_per_group = wave_g
     dev, ora = _hip_env(cfg, mp), ob.OracleEnv(cfg, mp)
+    ls = dev.env.launch_shape()
+    print(f"soak {scen} N={N}: launch_shape {ls}")
+    if wave_g:
+        assert (ls["wave_G"], ls["wave_spec"], ls["instantiation"]) == (wave_g, N * 256 + wave_g, (True, True, N, wave_g, False, False)), ls
+    else:  # the generic kernel
+        assert (ls["wave_spec"], ls["instantiation"]) == (0, (True, 2 * ls["wave_G"] * N <= 64, 0, 0, False, False)), ls
     dev.env.buffer(capi.BUF_DONE).fill_(1)
     ora.get(capi.BUF_DONE, copy=False)[:] = 1
     pf, pc = mp.list_first[0], mp.list_count[0]

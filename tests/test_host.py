@@ -126,6 +126,33 @@ def test_hip_library_exports_the_declared_abi():
         assert rc == capi_err("ENODEV") and not h.value
 
 
+def test_launch_shape_layout_matches_the_header(tmp_path):
+    """capi.LaunchShape == sigmaenv_launch_shape_t as the host C compiler lays it out; the entry point refuses NULL arguments without touching a device."""
+    import shutil
+
+    fields = [f[0] for f in capi.LaunchShape._fields_]
+    assert fields[:11] == ["wave_G", "wave_wpb", "wave_grid", "wave_spec", "wave_lds_bytes", "kern_fastdiv", "kern_par", "kern_sn", "kern_sg", "kern_var", "kern_mtvs"]
+    if shutil.which("cc") is not None:
+        src = tmp_path / "layout.c"
+        src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "sigmaenv.h"\nint main(void) {\n'
+                       '  printf("size %zu\\n", sizeof(sigmaenv_launch_shape_t));\n'
+                       + "".join(f'  printf("{f} %zu\\n", offsetof(sigmaenv_launch_shape_t, {f}));\n' for f in fields)
+                       + '  printf("abi %d\\n", SIGMAENV_ABI_VERSION);\n  return 0;\n}\n')
+        exe = tmp_path / "layout"
+        subprocess.check_call(["cc", "-std=c99", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)])
+        got = dict(line.split(" ", 1) for line in subprocess.check_output([str(exe)], text=True).splitlines())
+        assert int(got["size"]) == ctypes.sizeof(capi.LaunchShape) == 80
+        for f in fields:
+            assert int(got[f]) == getattr(capi.LaunchShape, f).offset, f
+        assert int(got["abi"]) == capi.ABI_VERSION  # a new read-only entry point: no existing structure changed
+    assert "sigmaenv_launch_shape" in capi.exported_symbols()
+    import torch  # noqa: F401  (HIP runtime load order, see capi.load_library)
+
+    lib = capi.Library(capi.DEFAULT_LIB, "sigmaenv_", capi._PRODUCT_ONLY)
+    out = capi.LaunchShape()
+    assert lib.launch_shape(None, ctypes.byref(out)) == capi_err("EINVAL")
+
+
 def capi_err(name):
     return {"EINVAL": -22, "ENOMEM": -12, "EHIP": -5, "ENODEV": -19}[name]
 

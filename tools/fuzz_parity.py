@@ -23,7 +23,48 @@ MAPS = ["cpm_entire", "cpm_entire", "cpm_entire", "intersection_1", "on_ramp_1",
 REW = ["distance", "ttc", "sparse", "distance_sparse", "ttc_sparse"]
 
 
-def one_case(rng, k):
+LDS_LIMIT = 64 * 1024  # a drawn tiling whose workgroups would need more LDS than every device grants without the opt-in attribute is shrunk, not requested
+TILING_SWITCHES = ("SIGMAENV_WPB", "SIGMAENV_WAVE_SPEC")
+
+
+def _hip_env_with_tiling(cfg, mp, N, tiling_rng):
+    """The HIP handle at a tiling drawn from `tiling_rng` (a generator of its own: the case's stream is untouched): cfg.envs_per_group anywhere in 1 .. 64 // N
+    (divisors of the batch or not), SIGMAENV_WPB in {1, 2, 4}, and now and then SIGMAENV_WAVE_SPEC=0.  The tiling is applied, read back with launch_shape() and
+    asserted; one that does not fit the LDS is shrunk (first one tile per workgroup, then half the envs per tile)."""
+    epg, wpb, spec0 = int(tiling_rng.integers(1, 64 // N + 1)), int(tiling_rng.choice([1, 2, 4])), bool(tiling_rng.integers(3) == 0)
+    saved = {k: os.environ.get(k) for k in TILING_SWITCHES}
+    try:
+        while True:
+            os.environ["SIGMAENV_WPB"] = str(wpb)
+            os.environ.pop("SIGMAENV_WAVE_SPEC", None)
+            if spec0:
+                os.environ["SIGMAENV_WAVE_SPEC"] = "0"
+            cfg.envs_per_group = epg
+            dev = tp._hip_env(cfg, mp)
+            ls = dev.env.launch_shape()
+            assert (ls["wave_G"], ls["G"], ls["wave_wpb"]) == (epg, epg, wpb), (epg, wpb, ls)
+            assert ls["wave_grid"] == ((cfg.n_envs + epg - 1) // epg + wpb - 1) // wpb, ls
+            if spec0:
+                assert ls["wave_spec"] == 0 and ls["kern_sn"] == 0 and ls["kern_sg"] == 0, ls
+            assert ls["kern_par"] == int(2 * epg * N <= 64), ls
+            if max(ls["wave_lds_bytes"], ls["smem_bytes"]) <= LDS_LIMIT or (wpb == 1 and epg == 1):
+                return dev, f"tiling {N} x {epg}, {wpb} per workgroup, instantiation {ls['instantiation']}"
+            dev.close()
+            if wpb > 1:
+                wpb = 1
+            else:
+                epg = max(1, epg // 2)
+    finally:
+        for k, v in saved.items():
+            if v is None:
+                os.environ.pop(k, None)
+            else:
+                os.environ[k] = v
+
+
+def one_case(rng, k, tiling_rng=None):
+    """One random configuration.  `tiling_rng` (optional, a second generator) also draws a tiling of the step kernel; without it the function consumes exactly
+    the random numbers it always did, and the library chooses the tiling."""
     scen = MAPS[rng.integers(len(MAPS))]
     mp = load_map(scen)
     n_max = 20 if scen == "cpm_entire" else 6
@@ -50,7 +91,12 @@ def one_case(rng, k):
                     kw.update(is_partial_observation=True, n_nearing_agents_observed=2)
     p = Parameters(**kw)
     cfg = make_config(p, mp, B)
-    dev, ora = tp._hip_env(cfg, mp), ob.OracleEnv(cfg, mp)
+    tiling = ""
+    if tiling_rng is None:
+        dev = tp._hip_env(cfg, mp)
+    else:
+        dev, tiling = _hip_env_with_tiling(cfg, mp, N, tiling_rng)
+    ora = ob.OracleEnv(cfg, mp)
     dev.env.buffer(capi.BUF_DONE).fill_(1)
     ora.get(capi.BUF_DONE, copy=False)[:] = 1
     lst = int(rng.integers(len(mp.list_first)))
@@ -66,7 +112,7 @@ def one_case(rng, k):
     seed = int(rng.integers(1 << 30))
     dev.auto_reset(seed, 0, pf, pc)
     ora.auto_reset(seed, 0, pf, pc)
-    tag = f"case {k}: {scen} N={N} B={B} " + " ".join(f"{a}={b}" for a, b in kw.items() if a not in ("n_agents", "scenario_type"))
+    tag = f"case {k}: {scen} N={N} B={B} " + (tiling + " " if tiling else "") + " ".join(f"{a}={b}" for a, b in kw.items() if a not in ("n_agents", "scenario_type"))
     n_diff = tp._compare_all(dev, ora, tag + " | initial reset")
     T = int(rng.integers(8, 40))
     for t in range(T):
