@@ -365,7 +365,9 @@ void sigmaenv_actor_destroy(sigmaenv_actor_t* a);
 
 /* actions := policy(observation) for every agent row.  obs: device f32 [B*N, obs_dim] or NULL for the handle's SIGMAENV_BUF_OBS;
  * actions: device f32 [B,N,2]; log_prob (optional) device f32 [B,N]; loc_scale (optional) device f32 [B,N,4] = loc0, loc1, scale0,
- * scale1.  deterministic != 0: action = squash(loc).  seed / counter select the counter-based random stream (draws 7000, 7001). */
+ * scale1.  deterministic != 0: action = squash(loc).  seed / counter select the counter-based random stream (draws 7000, 7001).
+ * Everywhere in this header the generator takes `seed` with both 32-bit words and `counter` with its LOW 32 bits only: counter and counter + 2^32
+ * give the same draws (2^32 + 5 draws what 5 draws), so a stream repeats after 2^32 steps of one seed (tests/policy_head_check.py restates it). */
 int sigmaenv_actor_forward(sigmaenv_t* h, sigmaenv_actor_t* a, const float* obs, float* actions, float* log_prob, float* loc_scale, uint64_t seed,
                            uint64_t counter, int32_t deterministic);
 

@@ -815,6 +815,10 @@ static inline uint32_t rng_u32(uint64_t seed, uint64_t counter, uint32_t env, ui
   h ^= h >> 16; h *= 0x85EBCA6Bu; h ^= h >> 13; h *= 0xC2B2AE35u; h ^= h >> 16;
   return h;
 }
+/* the generator itself on arrays of keys (tests/test_policy_head_check.py holds the Python restatement of the policy heads' draws to it) */
+void sigmaenv_oracle_rng_u32(int64_t n, const uint64_t* seed, const uint64_t* counter, const uint32_t* env, const uint32_t* agent, const uint32_t* draw, uint32_t* out) {
+  for (int64_t k = 0; k < n; ++k) out[k] = rng_u32(seed[k], counter[k], env[k], agent[k], draw[k]);
+}
 #define AUTO_RESET_MAX_TRIES 64
 /* Exclusive upper end of the centre-line points try `t` (0-based) may draw from (world_state_rt_sim.py:253-263): the first half of the
  * path in training; in testing mode the range starts at the path's beginning and grows with the tries -- end_point_idx starts at 3 and

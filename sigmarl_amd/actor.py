@@ -13,6 +13,11 @@ collector's opponent-modelling or prioritized-propagation policy in the fp32 dev
 ``Actor.rollout(obs_rec=...)`` records the observation every step's policy acted on, ``Mlp32.forward_rows`` / ``Critic.rollout_values`` run a network on the
 rollout's records where they lie (``sigmaenv_mlp32_forward_rows``); ``sigmarl_amd.learn`` builds the learner's batch from them.
 Weights come from any ``torch.nn.Sequential`` of four ``Linear`` layers (the parameter layout torchrl's shared-parameter MLP has).
+
+The distribution heads (actor, priority actor) and ``random_ranks``: the draw of every row -- the counter-based generator keyed by (seed, the low 32 bits of
+counter, env_index_base + env, agent), Box-Muller with z0 the cosine and z1 the sine branch -- the action and the log-probability are pinned against fp64 on every
+path (``tests/test_gpu_policy_head.py``, restated in ``tests/policy_head_check.py``).  The log-probability is that of the unclamped ``x = loc + scale z``, never
+of ``atanh`` of the clamped action.  Whether torchrl's own ``TanhNormal.log_prob`` does the same for a saturated sample is not verified (torchrl is absent here).
 """
 from __future__ import annotations
 

@@ -6,8 +6,11 @@
 // agent row  Linear(D,256) Tanh Linear(256,256) Tanh Linear(256,256) Tanh Linear(256,4);  NormalParamExtractor: loc = out[0:2],
 // scale = max(softplus(out[2:4] + ln(e^0.99 - 1)) + 0.01, 1e-4) ("biased_softplus_1.0");  TanhNormal(loc, scale, low, high): x = loc + scale * z,
 // y = tanh(x), action = low + (y + 1) / 2 * (high - low), log-probability summed over the two action dimensions (actor_distribution).
-// torchrl / tensordict are third-party and absent here: the distribution details are restated from their documented behaviour
-// ("parity unpinned" for the sampler and the log-probability); the MLP itself is pinned against torch.nn in tests/test_gpu_actor.py.
+// torchrl / tensordict are third-party and absent here: the distribution details are restated from their documented behaviour.  Pinned: the draw of every
+// row (generator key, uniforms, Box-Muller branch), the action and the log-probability against fp64 on all four head paths (tests/test_gpu_policy_head.py,
+// with the host restatement tests/policy_head_check.py); the MLP against torch.nn / fp64 (tests/test_gpu_actor.py, tests/test_gpu_networks.py).  The kernel
+// takes the log-probability from the UNCLAMPED x = loc + scale z (never from atanh of the clamped y).  Not pinned (no torchrl here): whether torchrl's
+// TanhNormal.log_prob of a saturated sample uses x (its cache) or atanh(clamped y).
 //
 // MI355X mapping.  This is the one GEMM-shaped piece next to the env step: B*N = 65536 rows x (D*256 + 2*256*256 + 256*4) MACs per
 // step = 18 GFLOP -> matrix cores (v_mfma_f32_16x16x32_bf16, fp32 accumulate), bf16 weights and activations.

@@ -56,6 +56,7 @@ def load_oracle(n_short_term: int = capi.N_SHORT_TERM) -> capi.Library:
             "fn_qp_vanish_tol": (C.c_double, [C.c_double]),
             "env0_reset_side_effect": (C.c_int, [C.c_void_p, C.c_int32]),
             "path_table": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(_f32p), C.POINTER(_f32p), C.POINTER(_f32p)]),
+            "rng_u32": (None, [C.c_int64] + [C.c_void_p] * 6),  # oracle only: the HIP library has and needs no such entry point
         }
         _lib = capi.Library(oracle_path(n_short_term), "sigmaenv_oracle_", extra)
         assert _lib.n_short_term() == n_short_term
