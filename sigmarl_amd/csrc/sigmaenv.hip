@@ -2405,17 +2405,22 @@ extern "C" int sigmaenv_launch_shape(const sigmaenv_t* h, sigmaenv_launch_shape_
   return SIGMAENV_OK;
 }
 
-// n_steps launches' worth of fused steps in ONE launch when n_steps > 1 (sigmaenv_step_autoreset_n): step t reads actions + t * act_stride, draws its
-// resets from counter + t and records into slab + t * slab_stride (floats)
-static int launch_step(sigmaenv* h, const float* actions, uint64_t seed, uint64_t counter, int path_first, int path_count, int n_steps = 1, size_t act_stride = 0,
-                       float* slab = nullptr, size_t slab_stride = 0, bool slab_from_handle = true) {
-  if (!h || !actions) return SIGMAENV_EINVAL;
-  if (slab_from_handle) slab = h->buf.slab;
+// One launch of the step kernel: n_steps fused steps (sigmaenv_step_autoreset_n: n_steps launches' worth in ONE launch when n_steps > 1)
+struct StepLaunch {
+  const float* actions;            // device f32 [B, N, 2]; step t reads actions + t * act_stride
+  float* slab;                     // record target of the launch (nullptr: no record), never taken from the handle here; step t records into slab + t * slab_stride (floats)
+  uint64_t seed, counter;          // step t draws its resets from counter + t
+  int path_first, path_count;
+  int n_steps = 1;
+  size_t act_stride = 0, slab_stride = 0;
+};
+static int launch_step(sigmaenv* h, const StepLaunch& l) {
+  if (!h || !l.actions) return SIGMAENV_EINVAL;
   HIPCHK(h, hipSetDevice(h->device));  // handles on several GPUs may live in one process: every entry point that enqueues work selects its device
   const int slot = timer_begin(h, SIGMAENV_KERNEL_STEP);
   {
     const StepKernFn kern = select_step_kernel(h).fn;
-    const StepKernArgs ka{h->map, h->buf, actions, slab, act_stride, slab_stride, seed, counter, h->wave_G, (int)h->wave_tile_lds, path_first, path_count, n_steps};
+    const StepKernArgs ka{h->map, h->buf, l.actions, l.slab, l.act_stride, l.slab_stride, l.seed, l.counter, h->wave_G, (int)h->wave_tile_lds, l.path_first, l.path_count, l.n_steps};
     hipLaunchKernelGGL(kern, dim3(h->wave_grid), dim3(64 * h->wave_wpb), h->wave_tile_lds * h->wave_wpb, h->stream, (const sigmaenv_config_t*)h->d_cfg, ka);
   }
   HIPCHK(h, hipGetLastError());
@@ -2423,15 +2428,35 @@ static int launch_step(sigmaenv* h, const float* actions, uint64_t seed, uint64_
   return SIGMAENV_OK;
 }
 
-extern "C" int sigmaenv_step(sigmaenv_t* h, const float* actions) { return launch_step(h, actions, 0, 0, 0, 0); }
+extern "C" int sigmaenv_step(sigmaenv_t* h, const float* actions) {
+  if (!h) return SIGMAENV_EINVAL;
+  return launch_step(h, {actions, h->buf.slab, 0, 0, 0, 0});
+}
 
 extern "C" int sigmaenv_step_autoreset(sigmaenv_t* h, const float* actions, uint64_t seed, uint64_t counter, int32_t path_first, int32_t path_count) {
   if (!h || !paths_ok(h, path_first, path_count)) return SIGMAENV_EINVAL;
-  return launch_step(h, actions, seed, counter, path_first, path_count);
+  return launch_step(h, {actions, h->buf.slab, seed, counter, path_first, path_count});
 }
 
 extern "C" int sigmaenv_cbf_rewards(sigmaenv_t* h, const float* actions, double* margins);  // sigmaenv_cbf.inc
 extern "C" int sigmaenv_cbf_qp(sigmaenv_t* h, const float* actions, float* actions_safe, double* u_opt, int32_t* info);
+
+// One step of "policy -> CBFQP.update_qp -> env.step" (helper_training.py:1616-1627) with l.actions the POLICY's action: the CBF launch on it if the handle's
+// rew_method asks for one (the margin rewards, or the QP into h->cbf_safe), then the fused step l on the action the rule selects -- the grouped update ALWAYS
+// replaces the action by the safe one (cbf_qp.py:2211-2222), the centralized one only with is_apply_cbf_action.  A handle without sigmaenv_cbf_attach steps without
+// a CBF launch: sigmaenv_rollout* tolerate it; sigmaenv_step_autoreset_n refuses such a handle before it gets here.
+static int launch_cbf_then_step(sigmaenv* h, StepLaunch l) {
+  if (!h || !l.actions) return SIGMAENV_EINVAL;
+  if ((h->cfg.rew_flags & SIGMAENV_REW_CBF) && h->cbf_seg4) {
+    const int rc = sigmaenv_cbf_rewards(h, l.actions, nullptr);
+    if (rc) return rc;
+  } else if ((h->cfg.rew_flags & SIGMAENV_REW_CBF_QP) && h->cbf_seg4) {
+    const int rc = sigmaenv_cbf_qp(h, l.actions, (float*)h->cbf_safe, nullptr, nullptr);
+    if (rc) return rc;
+    if (h->cbf_cfg.is_apply_cbf_action || h->cbf_cfg.is_grouping) l.actions = (const float*)h->cbf_safe;
+  }
+  return launch_step(h, l);
+}
 
 // n_steps fused steps (step + rollout record + device-side resets) of every env in ONE launch: the reference's rollout loop over a chunk of steps
 // (helper_training.py:687-788: policy -> env.step -> step_mdp, T times) for actions that are already on the device.  Same end state, same record
@@ -2455,22 +2480,13 @@ extern "C" int sigmaenv_step_autoreset_n(sigmaenv_t* h, const float* actions, in
       return SIGMAENV_EINVAL;
     }
     for (int t = 0; t < n_steps; ++t) {
-      const float* act = actions + (size_t)t * (size_t)action_stride;
-      const float* step_act = act;
-      int rc;
-      if (h->cfg.rew_flags & SIGMAENV_REW_CBF) {
-        rc = sigmaenv_cbf_rewards(h, act, nullptr);
-      } else {
-        rc = sigmaenv_cbf_qp(h, act, (float*)h->cbf_safe, nullptr, nullptr);
-        if (h->cbf_cfg.is_apply_cbf_action || h->cbf_cfg.is_grouping) step_act = (const float*)h->cbf_safe;  // (as sigmaenv_rollout: cbf_qp.py:2211-2222)
-      }
-      if (rc) return rc;
-      rc = launch_step(h, step_act, seed, counter0 + (uint64_t)t, path_first, path_count, 1, 0, slab ? slab + (size_t)t * (size_t)slab_stride : nullptr, 0, false);
+      const int rc = launch_cbf_then_step(h, {actions + (size_t)t * (size_t)action_stride, slab ? slab + (size_t)t * (size_t)slab_stride : nullptr, seed, counter0 + (uint64_t)t,
+                                              path_first, path_count});
       if (rc) return rc;
     }
     return SIGMAENV_OK;
   }
-  return launch_step(h, actions, seed, counter0, path_first, path_count, n_steps, (size_t)action_stride, slab, (size_t)slab_stride, false);
+  return launch_step(h, {actions, slab, seed, counter0, path_first, path_count, n_steps, (size_t)action_stride, (size_t)slab_stride});
 }
 
 // One call for several handles (env shards of one GPU on their own streams): slab_ptrs[k] (may be NULL) becomes handle k's record
@@ -2482,7 +2498,7 @@ extern "C" int sigmaenv_step_autoreset_many(sigmaenv_t** hs, int32_t n, const fl
     sigmaenv* h = hs[k];
     if (!h || !paths_ok(h, path_first, path_count)) return SIGMAENV_EINVAL;
     if (slab_ptrs) h->buf.slab = slab_ptrs[k];
-    const int rc = launch_step(h, actions[k], seeds[k], counter, path_first, path_count);
+    const int rc = launch_step(h, {actions[k], h->buf.slab, seeds[k], counter, path_first, path_count});
     if (rc) return rc;
   }
   return SIGMAENV_OK;

@@ -290,9 +290,6 @@ extern "C" int sigmaenv_actor_forward(sigmaenv_t* h, sigmaenv_actor* a, const fl
 
 // T steps of (policy -> fused step + record + resets) without returning to the caller: actions_buf device f32 [B, N, 2] (scratch),
 // slab_base (optional) device f32 [T, B, W]: row block t receives the record of step t; logp_base (optional) device f32 [T, B, N].
-extern "C" int sigmaenv_cbf_rewards(sigmaenv_t* h, const float* actions, double* margins);  // sigmaenv_cbf.inc
-extern "C" int sigmaenv_cbf_qp(sigmaenv_t* h, const float* actions, float* actions_safe, double* u_opt, int32_t* info);
-
 // the loop shared by sigmaenv_rollout (bf16 actor) and sigmaenv_rollout_f32 (the reference's fp32 actor): policy(t) enqueues the actor forward
 // of step t writing the actions (and log-probabilities) to the given pointers
 template <class Policy>
@@ -301,7 +298,7 @@ static int rollout_loop(sigmaenv_t* h, Policy policy, int32_t n_steps, float* ac
   if (!h || !actions_buf || n_steps < 1) return SIGMAENV_EINVAL;
   if (path_count != 0 && !paths_ok(h, path_first, path_count)) { h->err = "rollout: path range outside the table (or no scenario lists set)"; return SIGMAENV_EINVAL; }
   const size_t W = (size_t)h->N * (h->D + 1) + 1, BN = (size_t)h->B * h->N;
-  float* saved = h->buf.slab;
+  const size_t slab_stride = h->rollout_slab_stride ? h->rollout_slab_stride : (size_t)h->B * W;
   for (int t = 0; t < n_steps; ++t) {
     float* act = actions_rec ? actions_rec + (size_t)t * BN * 2 : actions_buf;
     int rc = policy(t, act, logp_base ? logp_base + (size_t)t * BN : nullptr);
@@ -311,21 +308,10 @@ static int rollout_loop(sigmaenv_t* h, Policy policy, int32_t n_steps, float* ac
       HIPCHK(h, hipMemcpyAsync(h->rollout_obs_rec + (size_t)t * (h->rollout_obs_stride ? h->rollout_obs_stride : own), h->buf.obs, own * sizeof(float), hipMemcpyDeviceToDevice,
                                h->stream));
     }
-    const float* step_act = act;
-    if ((h->cfg.rew_flags & SIGMAENV_REW_CBF) && h->cbf_seg4) {  // CBFQP.update_qp between policy and step (helper_training.py:1616-1627)
-      rc = sigmaenv_cbf_rewards(h, act, nullptr);
-      if (rc) return rc;
-    } else if ((h->cfg.rew_flags & SIGMAENV_REW_CBF_QP) && h->cbf_seg4) {  // the centralized QP; the safe action is applied when asked for
-      rc = sigmaenv_cbf_qp(h, act, (float*)h->cbf_safe, nullptr, nullptr);
-      if (rc) return rc;
-      // the grouped update ALWAYS replaces the action by the safe one (cbf_qp.py:2211-2222); the centralized one only when asked to
-      if (h->cbf_cfg.is_apply_cbf_action || h->cbf_cfg.is_grouping) step_act = (const float*)h->cbf_safe;
-    }
-    if (slab_base) h->buf.slab = slab_base + (size_t)t * (h->rollout_slab_stride ? h->rollout_slab_stride : (size_t)h->B * W);
-    rc = launch_step(h, step_act, seed, counter0 + (uint64_t)t, path_first, path_count);
-    if (rc) { h->buf.slab = saved; return rc; }
+    // step t records into row block t of slab_base, or -- without one -- wherever the handle records (sigmaenv_set_slab); the handle's target is only read
+    rc = launch_cbf_then_step(h, {act, slab_base ? slab_base + (size_t)t * slab_stride : h->buf.slab, seed, counter0 + (uint64_t)t, path_first, path_count});
+    if (rc) return rc;
   }
-  h->buf.slab = saved;
   return SIGMAENV_OK;
 }
 

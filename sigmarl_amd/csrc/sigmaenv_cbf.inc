@@ -58,27 +58,50 @@ __device__ inline double pair_margin(const sigmaenv_cbf_config_t& cc, const Kin&
 __device__ __forceinline__ double clip_d(double x, double lo, double hi) { return x < lo ? lo : (x > hi ? hi : x); }  // NaN stays NaN
 
 // ---- kernel A: per vehicle -- circle centres, nominal action, linearised centre kinematics (cbf_qp.py:2586-2615, 2283-2335) --------
-// One lane per vehicle (the float64 trigonometry is the expensive part: every distinct value is evaluated once).  kin_vehicle: one vehicle (bi = env * N + vehicle); its
-// C circle centres and centre kinematics go to out_cxy[0 .. C) / out_kin[0 .. C) -- global memory for sigmaenv_cbf_kin_kernel (the margin rewards' launch, and the QP's
-// when circle centres are injected), the workgroup's LDS when sigmaenv_cbf_qp_kernel evaluates them itself.
-__device__ __forceinline__ void kin_vehicle(const sigmaenv_config_t& c, const sigmaenv_cbf_config_t& cc, const DevBufs& g, const float* __restrict__ actions, size_t bi,
+template <int CTRL>
+__device__ __forceinline__ double dpp_f64(double x) {
+  const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(x), CTRL, 0xF, 0xF, true);
+  const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(x), CTRL, 0xF, 0xF, true);
+  return __hiloint2double(hi, lo);
+}
+// kin_vehicle: one vehicle (bi = env * N + vehicle); its C circle centres and centre kinematics go to out_cxy[0 .. C) / out_kin[0 .. C) -- global memory for
+// sigmaenv_cbf_kin_kernel (the margin rewards' launch, and the QP's when circle centres are injected), the workgroup's LDS when sigmaenv_cbf_qp_kernel evaluates them itself.
+// The float64 trigonometry is the expensive part (every distinct value is evaluated once): a chain of three dependent rounds -- sincos(yaw) | sincos(steering), then the two
+// arctangents of the slip angle, then three sincos of (yaw + slip, float32 and float64) and of the slip angle.  LANES says where the evaluations run:
+//   LANES == 1 (sigmaenv_cbf_kin_kernel): all seven in the vehicle's one lane, which then takes every circle;
+//   LANES == 4 (the QP kernel's prologue: 16 vehicles = one wavefront): the evaluations of a round are independent, so each runs in a lane of its own (same function, other
+//   argument) and the results cross the quad by DPP -- seven evaluations deep -> three; after that lane `sub` of the quad takes circle `sub`.  All four lanes of a quad must
+//   be active.
+// Only the two `if constexpr` places and the range of the two circle loops depend on LANES; everything else is one statement of the operations, so both forms return
+// the same bits (tests/test_gpu_cbf.py: test_cbf_qp_one_lane_and_four_lane_kinematics_agree_bitwise).
+template <int LANES>
+__device__ __forceinline__ void kin_vehicle(const sigmaenv_config_t& c, const sigmaenv_cbf_config_t& cc, const DevBufs& g, const float* __restrict__ actions, size_t bi, int sub,
                                             float2* __restrict__ out_cxy, double2& out_u, Kin* __restrict__ out_kin, double2& out_clf) {
+  static_assert(LANES == 1 || LANES == 4, "one lane per vehicle, or a quad");
   const int C = cc.n_circles;
+  constexpr bool QUAD = LANES == 4;  // the two circle loops below: every circle, or -- in a quad -- circle `sub` if there is one
   const float4 s0 = reinterpret_cast<const float4*>(g.state + bi * 8)[0];
   const float delta_f = g.state[bi * 8 + 4];
   const float2 a = reinterpret_cast<const float2*>(actions)[bi];
   const float px = s0.x, py = s0.y, psi_f = s0.z, v_f = s0.w;
   const double psi = psi_f, v = v_f, delta = delta_f;
   // the trigonometric values every formula below shares (same function, same argument: same value as evaluating them in place)
-  double sin_psi, cos_psi;
   // (the float64 kernels of the contract's sin / cos / atan -- fdlibm's, below 1 ulp -- instead of the device library's: a third of the instructions, and their
   // float32 roundings ARE cr_sin / cr_cos / cr_tan)
-  sigma_sincos_f64(psi, &sin_psi, &cos_psi);
-  double sin_delta, cos_delta;
-  sigma_sincos_f64(delta, &sin_delta, &cos_delta);
+  double sin_psi, cos_psi, sin_delta, cos_delta;
+  if constexpr (LANES == 1) {
+    sigma_sincos_f64(psi, &sin_psi, &cos_psi);
+    sigma_sincos_f64(delta, &sin_delta, &cos_delta);
+  } else {  // round 1: lane 0 sincos(psi), lane 1 sincos(delta)
+    double r1s, r1c;
+    sigma_sincos_f64(sub == 1 ? delta : psi, &r1s, &r1c);
+    sin_psi = dpp_f64<0x00>(r1s); cos_psi = dpp_f64<0x00>(r1c);
+    sin_delta = dpp_f64<0x55>(r1s); cos_delta = dpp_f64<0x55>(r1c);
+  }
   const double tan_delta = sin_delta / cos_delta;
   const float sn = (float)sin_psi, cs = (float)cos_psi;  // cr_sin / cr_cos of the yaw
-  for (int ci = 0; ci < C; ++ci) {  // get_circle_centers, cbf_qp.py:527-573 (float32)
+  // get_circle_centers, cbf_qp.py:527-573 (float32).  QUAD: the loop is `if (sub < C)` on circle sub -- it starts at sub and steps by C >= 1, so one pass at most
+  for (int ci = QUAD ? sub : 0; ci < C; ci += QUAD ? C : 1) {
     const float lx = (float)cc.circle_x[ci];
     out_cxy[ci] = make_float2((cs * lx + (-sn) * 0.0f) + px, (sn * lx + cs * 0.0f) + py);
   }
@@ -104,112 +127,28 @@ __device__ __forceinline__ void kin_vehicle(const sigmaenv_config_t& c, const si
   const float l_wb_f = (float)((double)c.l_f + (double)c.l_r);
   const float kf = (float)((double)c.l_r / ((double)c.l_f + (double)c.l_r));
   const float td = (float)tan_delta;  // cr_tan
-  const float beta_f = cr_atan(kf * td);
-  float sb_f, cb_f;
-  cr_sincos(psi_f + beta_f, sb_f, cb_f);
-  const float d0 = v_f * cb_f;
-  const float d1 = v_f * sb_f;
-  const float d2 = (v_f / l_wb_f) * td * cr_cos(beta_f);
-  const double dpsi = d2, dx = d0, dy = d1;
-  // compute_dstate_2nd_time for u = (0,0), (1,0), (0,1), cbf_qp.py:667-695, 2295-2303
   const double k = cc.l_r / cc.l_wb;
-  const double beta = sigma_atan_f64(k * tan_delta);
-  const double sec_delta_sq = 1.0 / (cos_delta * cos_delta);
-  const double tan_beta = k * tan_delta;
-  const double cos_beta = 1.0 / sqrt(1.0 + tan_beta * tan_beta);
-  const double sin_beta = tan_beta * cos_beta;
-  const double kt = k * tan_delta;
+  // the slip angle in float32 (beta_f) and float64, then sin / cos of yaw + slip in both precisions and the float32 cos of the slip angle
+  float sb_f, cb_f, cos_beta_f;
   double sin_pb, cos_pb;
-  sigma_sincos_f64(psi + beta, &sin_pb, &cos_pb);
-  double ddx[3], ddy[3], ddp[3];
-#pragma unroll
-  for (int q = 0; q < 3; ++q) {
-    const double u1 = (q == 1) ? 1.0 : 0.0, u2 = (q == 2) ? 1.0 : 0.0;
-    const double dbeta = (k * sec_delta_sq * u2) / (1.0 + kt * kt);
-    ddx[q] = u1 * cos_pb - v * sin_pb * (dpsi + dbeta);
-    ddy[q] = u1 * sin_pb + v * cos_pb * (dpsi + dbeta);
-    ddp[q] = (u1 / cc.l_wb) * cos_beta * tan_delta + (v / cc.l_wb) * cos_beta * sec_delta_sq * u2 - (v / cc.l_wb) * sin_beta * tan_delta * dbeta;
-  }
-  // compute_center_state_time_derivatives per circle, cbf_qp.py:697-727 (delta_y = 0: the terms are kept, they evaluate to +-0)
-  for (int ci = 0; ci < C; ++ci) {
-    const double delta_x = cc.circle_x[ci], delta_y = 0.0;
-    Kin kn;
-    kn.dx = dx - delta_x * sin_psi * dpsi - delta_y * cos_psi * dpsi;
-    kn.dy = dy + delta_x * cos_psi * dpsi - delta_y * sin_psi * dpsi;
-    double ax[3], ay[3];
-#pragma unroll
-    for (int q = 0; q < 3; ++q) {
-      ax[q] = ddx[q] - delta_x * (sin_psi * ddp[q] + cos_psi * dpsi * dpsi) - delta_y * (cos_psi * ddp[q] - sin_psi * dpsi * dpsi);
-      ay[q] = ddy[q] + delta_x * (cos_psi * ddp[q] - sin_psi * dpsi * dpsi) - delta_y * (sin_psi * ddp[q] + cos_psi * dpsi * dpsi);
-    }
-    kn.ax0 = ax[1] - ax[0]; kn.ax1 = ax[2] - ax[0]; kn.cx = ax[0];
-    kn.ay0 = ay[1] - ay[0]; kn.ay1 = ay[2] - ay[0]; kn.cy = ay[0];
-    out_kin[ci] = kn;
-  }
-}
-// kin_vehicle over FOUR lanes per vehicle (the QP kernel's prologue: 16 vehicles = one wavefront): the float64 trigonometry is a chain of three dependent rounds --
-// sincos(yaw) | sincos(steering), then the two arctangents of the slip angle, then three sincos of (yaw + slip, float32 and float64) and of the slip angle -- and
-// the evaluations of a round are independent: each runs in a lane of its own (same function, other argument), the results cross the quad by DPP.  Seven evaluations
-// deep -> three.  After that lane ci of the quad evaluates circle ci.  Same operations on the same operands as kin_vehicle: the same bits (tests/test_gpu_cbf.py holds
-// the QP kernel, which uses this form, and sigmaenv_cbf_kin_kernel, which uses the other, to the same oracle values).  All four lanes of a quad must be active.
-template <int CTRL>
-__device__ __forceinline__ double kin_dpp(double x) {
-  const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(x), CTRL, 0xF, 0xF, true);
-  const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(x), CTRL, 0xF, 0xF, true);
-  return __hiloint2double(hi, lo);
-}
-__device__ __forceinline__ void kin_vehicle4(const sigmaenv_config_t& c, const sigmaenv_cbf_config_t& cc, const DevBufs& g, const float* __restrict__ actions, size_t bi, int sub,
-                                             float2* __restrict__ out_cxy, double2& out_u, Kin* __restrict__ out_kin, double2& out_clf) {
-  const int C = cc.n_circles;
-  const float4 s0 = reinterpret_cast<const float4*>(g.state + bi * 8)[0];
-  const float delta_f = g.state[bi * 8 + 4];
-  const float2 a = reinterpret_cast<const float2*>(actions)[bi];
-  const float px = s0.x, py = s0.y, psi_f = s0.z, v_f = s0.w;
-  const double psi = psi_f, v = v_f, delta = delta_f;
-  // round 1: lane 0 sincos(psi), lane 1 sincos(delta)
-  double r1s, r1c;
-  sigma_sincos_f64(sub == 1 ? delta : psi, &r1s, &r1c);
-  const double sin_psi = kin_dpp<0x00>(r1s), cos_psi = kin_dpp<0x00>(r1c);
-  const double sin_delta = kin_dpp<0x55>(r1s), cos_delta = kin_dpp<0x55>(r1c);
-  const double tan_delta = sin_delta / cos_delta;
-  const float sn = (float)sin_psi, cs = (float)cos_psi;  // cr_sin / cr_cos of the yaw
-  if (sub < C) {  // get_circle_centers, cbf_qp.py:527-573 (float32)
-    const float lx = (float)cc.circle_x[sub];
-    out_cxy[sub] = make_float2((cs * lx + (-sn) * 0.0f) + px, (sn * lx + cs * 0.0f) + py);
-  }
-  if (cc.nominal == 0) {
-    // rl_action_to_u (float32), cbf_qp.py:461-497
-    const float r0 = clampf(a.x, cc.min_speed, c.max_speed), r1 = clampf(a.y, cc.min_steering, c.max_steering);
-    const float ua = clampf((r0 - v_f) / c.dt, c.min_acc, c.max_acc);
-    const float us = clampf((r1 - delta_f) / c.dt, c.min_steering_rate, c.max_steering_rate);
-    out_u = make_double2((double)ua, (double)us);
-    out_clf = make_double2(0.0, 0.0);
+  if constexpr (LANES == 1) {
+    const float beta_f = cr_atan(kf * td);
+    cr_sincos(psi_f + beta_f, sb_f, cb_f);
+    cos_beta_f = cr_cos(beta_f);
+    const double beta = sigma_atan_f64(k * tan_delta);
+    sigma_sincos_f64(psi + beta, &sin_pb, &cos_pb);
   } else {
-    // "clf" nominal controller (cbf_qp.py:2616-2628, 442-459, Python floats): heading towards the third short-term reference point
-    const float2 ref = reinterpret_cast<const float2*>(g.short_term + bi * NS * 2)[2];
-    const double desired = atan2((double)ref.y - (double)py, (double)ref.x - (double)px);
-    double r = fmod(desired - psi + M_PI, 2.0 * M_PI);  // Python float %: sign of the divisor
-    if (r != 0.0 && r < 0.0) r += 2.0 * M_PI;
-    const double e_h = r - M_PI, e_v = cc.ref_speed - v;
-    out_u = make_double2(clip_d(cc.k_clf_speed * e_v, (double)c.min_acc, (double)c.max_acc),
-                             clip_d(cc.k_clf_heading * e_h, -cc.steering_rate_max, cc.steering_rate_max));
-    out_clf = make_double2(e_v, e_h);  // CLF rows of the QP (cbf_qp.py:1088-1091): speed error, heading error
+    // round 2: lane 0 cr_atan(kf * td) = (float) atan((double)(kf * td)), lane 1 atan(k * tan_delta)
+    const double r2 = sigma_atan_f64(sub == 1 ? k * tan_delta : (double)(kf * td));
+    const float beta_f = (float)dpp_f64<0x00>(r2);
+    const double beta = dpp_f64<0x55>(r2);
+    // round 3: lane 0 cr_sincos(psi_f + beta_f), lane 1 sincos(psi + beta), lane 2 cr_cos(beta_f)
+    double r3s, r3c;
+    sigma_sincos_f64(sub == 1 ? psi + beta : (sub == 2 ? (double)beta_f : (double)(psi_f + beta_f)), &r3s, &r3c);
+    sb_f = (float)dpp_f64<0x00>(r3s); cb_f = (float)dpp_f64<0x00>(r3c);
+    sin_pb = dpp_f64<0x55>(r3s); cos_pb = dpp_f64<0x55>(r3c);
+    cos_beta_f = (float)dpp_f64<0xAA>(r3c);
   }
-  // kbm.ode(None, state, [0, 0]) in float32, dynamics.py:103-111
-  const float l_wb_f = (float)((double)c.l_f + (double)c.l_r);
-  const float kf = (float)((double)c.l_r / ((double)c.l_f + (double)c.l_r));
-  const float td = (float)tan_delta;  // cr_tan
-  const double k = cc.l_r / cc.l_wb;
-  // round 2: lane 0 cr_atan(kf * td) = (float) atan((double)(kf * td)), lane 1 atan(k * tan_delta)
-  const double r2 = sigma_atan_f64(sub == 1 ? k * tan_delta : (double)(kf * td));
-  const float beta_f = (float)kin_dpp<0x00>(r2);
-  const double beta = kin_dpp<0x55>(r2);
-  // round 3: lane 0 cr_sincos(psi_f + beta_f), lane 1 sincos(psi + beta), lane 2 cr_cos(beta_f)
-  double r3s, r3c;
-  sigma_sincos_f64(sub == 1 ? psi + beta : (sub == 2 ? (double)beta_f : (double)(psi_f + beta_f)), &r3s, &r3c);
-  const float sb_f = (float)kin_dpp<0x00>(r3s), cb_f = (float)kin_dpp<0x00>(r3c);
-  const double sin_pb = kin_dpp<0x55>(r3s), cos_pb = kin_dpp<0x55>(r3c);
-  const float cos_beta_f = (float)kin_dpp<0xAA>(r3c);
   const float d0 = v_f * cb_f;
   const float d1 = v_f * sb_f;
   const float d2 = (v_f / l_wb_f) * td * cos_beta_f;
@@ -229,9 +168,9 @@ __device__ __forceinline__ void kin_vehicle4(const sigmaenv_config_t& c, const s
     ddy[q] = u1 * sin_pb + v * cos_pb * (dpsi + dbeta);
     ddp[q] = (u1 / cc.l_wb) * cos_beta * tan_delta + (v / cc.l_wb) * cos_beta * sec_delta_sq * u2 - (v / cc.l_wb) * sin_beta * tan_delta * dbeta;
   }
-  // compute_center_state_time_derivatives, cbf_qp.py:697-727 (delta_y = 0: the terms are kept, they evaluate to +-0): lane ci takes circle ci
-  if (sub < C) {
-    const double delta_x = cc.circle_x[sub], delta_y = 0.0;
+  // compute_center_state_time_derivatives, cbf_qp.py:697-727 (delta_y = 0: the terms are kept, they evaluate to +-0).  QUAD: again `if (sub < C)` on circle sub, as above
+  for (int ci = QUAD ? sub : 0; ci < C; ci += QUAD ? C : 1) {
+    const double delta_x = cc.circle_x[ci], delta_y = 0.0;
     Kin kn;
     kn.dx = dx - delta_x * sin_psi * dpsi - delta_y * cos_psi * dpsi;
     kn.dy = dy + delta_x * cos_psi * dpsi - delta_y * sin_psi * dpsi;
@@ -243,7 +182,7 @@ __device__ __forceinline__ void kin_vehicle4(const sigmaenv_config_t& c, const s
     }
     kn.ax0 = ax[1] - ax[0]; kn.ax1 = ax[2] - ax[0]; kn.cx = ax[0];
     kn.ay0 = ay[1] - ay[0]; kn.ay1 = ay[2] - ay[0]; kn.cy = ay[0];
-    out_kin[sub] = kn;
+    out_kin[ci] = kn;
   }
 }
 __global__ void __launch_bounds__(256) sigmaenv_cbf_kin_kernel(sigmaenv_config_t c, sigmaenv_cbf_config_t cc, DevBufs g, const float* __restrict__ actions,
@@ -254,7 +193,7 @@ __global__ void __launch_bounds__(256) sigmaenv_cbf_kin_kernel(sigmaenv_config_t
   const size_t BN = (size_t)c.n_envs * c.n_agents;
   if (bi >= BN) return;
   double2 u, clf;
-  kin_vehicle(c, cc, g, actions, bi, out_cxy + bi * cc.n_circles, u, out_kin + bi * cc.n_circles, clf);
+  kin_vehicle<1>(c, cc, g, actions, bi, 0, out_cxy + bi * cc.n_circles, u, out_kin + bi * cc.n_circles, clf);
   out_u[bi] = u;
   out_clf[bi] = clf;
 }
@@ -1078,21 +1017,15 @@ __device__ __noinline__ void qp_newton_direction(double* __restrict__ H, double*
 // gradient / Hessian over the vehicles they touch (at most 8), which those vehicles add to their registers and which, completed with
 // their own blocks, is the Newton system qp_newton_direction factorises; every other vehicle solves its 2 x 2 system in closed form.
 // Lanes: vehicle v owns LPV = 4 / 2 / 1 adjacent lanes (N <= 16 / 32 / 64), which share its 2 C lane rows.
-template <int CTRL>
-__device__ __forceinline__ double qp_dpp(double x) {
-  const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(x), CTRL, 0xF, 0xF, true);
-  const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(x), CTRL, 0xF, 0xF, true);
-  return __hiloint2double(hi, lo);
-}
 __device__ __forceinline__ double qp_uniform(double x) {  // a wavefront-uniform value, moved to scalar registers (the vector registers are the scarce ones here)
   return __hiloint2double(__builtin_amdgcn_readfirstlane(__double2hiint(x)), __builtin_amdgcn_readfirstlane(__double2loint(x)));
 }
 __device__ __forceinline__ double qp_wave_sum(double x) {  // (fixed order: the same value on every run and in every lane)
-  x += qp_dpp<0xB1>(x); x += qp_dpp<0x4E>(x); x += qp_dpp<0x141>(x); x += qp_dpp<0x140>(x);  // quad_perm [1,0,3,2], [2,3,0,1], row_half_mirror, row_mirror
+  x += dpp_f64<0xB1>(x); x += dpp_f64<0x4E>(x); x += dpp_f64<0x141>(x); x += dpp_f64<0x140>(x);  // quad_perm [1,0,3,2], [2,3,0,1], row_half_mirror, row_mirror
   return qp_uniform(((qp_bcast(x, 0) + qp_bcast(x, 16)) + qp_bcast(x, 32)) + qp_bcast(x, 48));
 }
 __device__ __forceinline__ double qp_wave_max(double x) {
-  x = fmax(x, qp_dpp<0xB1>(x)); x = fmax(x, qp_dpp<0x4E>(x)); x = fmax(x, qp_dpp<0x141>(x)); x = fmax(x, qp_dpp<0x140>(x));
+  x = fmax(x, dpp_f64<0xB1>(x)); x = fmax(x, dpp_f64<0x4E>(x)); x = fmax(x, dpp_f64<0x141>(x)); x = fmax(x, dpp_f64<0x140>(x));
   return qp_uniform(fmax(fmax(qp_bcast(x, 0), qp_bcast(x, 16)), fmax(qp_bcast(x, 32), qp_bcast(x, 48))));
 }
 struct __attribute__((aligned(16))) QpCand { double a[4], b0, h; int k0, k2, pad[2]; };  // a candidate pair row: coefficients; first unknown | compact index << 8 (| unknowns << 16) of its vehicle(s)
@@ -1186,8 +1119,8 @@ struct QpVehicle {
         }
       }
     }
-    if (lpv >= 2) { g0 += qp_dpp<0xB1>(g0); g1 += qp_dpp<0xB1>(g1); h00 += qp_dpp<0xB1>(h00); h01 += qp_dpp<0xB1>(h01); h11 += qp_dpp<0xB1>(h11); }
-    if (lpv == 4) { g0 += qp_dpp<0x4E>(g0); g1 += qp_dpp<0x4E>(g1); h00 += qp_dpp<0x4E>(h00); h01 += qp_dpp<0x4E>(h01); h11 += qp_dpp<0x4E>(h11); }
+    if (lpv >= 2) { g0 += dpp_f64<0xB1>(g0); g1 += dpp_f64<0xB1>(g1); h00 += dpp_f64<0xB1>(h00); h01 += dpp_f64<0xB1>(h01); h11 += dpp_f64<0xB1>(h11); }
+    if (lpv == 4) { g0 += dpp_f64<0x4E>(g0); g1 += dpp_f64<0x4E>(g1); h00 += dpp_f64<0x4E>(h00); h01 += dpp_f64<0x4E>(h01); h11 += dpp_f64<0x4E>(h11); }
     if (n_cand > 0) {
       QP_WSYNC();
       if (pos2 >= 0) {  // the candidate rows' share of the vehicle's gradient and block
@@ -1416,11 +1349,11 @@ __global__ void __launch_bounds__(256, BIG ? 1 : 4) sigmaenv_cbf_qp_kernel(sigma
     s.cxy[i] = in_cxy[(size_t)b * N * C + i];
   }
   stencil_prologue(m, g, s, b, N, C);
-  for (int i4 = tid; i4 < 4 * N; i4 += blockDim.x) {  // four lanes per vehicle (kin_vehicle4); lane 0 of the quad keeps the per-vehicle values
+  for (int i4 = tid; i4 < 4 * N; i4 += blockDim.x) {  // four lanes per vehicle (kin_vehicle<4>); lane 0 of the quad keeps the per-vehicle values
     const int i = i4 >> 2, sub = i4 & 3;
     double2 un, ce;
     if (in_kin) { un = in_u[(size_t)b * N + i]; ce = in_clf[(size_t)b * N + i]; }
-    else kin_vehicle4(c, cc, g, actions, (size_t)b * N + i, sub, s.cxy + i * C, un, s.kin + i * C, ce);
+    else kin_vehicle<4>(c, cc, g, actions, (size_t)b * N + i, sub, s.cxy + i * C, un, s.kin + i * C, ce);
     if (sub == 0) {
       s.path[i] = g.path[((size_t)b * N + i) * 4];
       q.sv[i] = make_float2(g.state[((size_t)b * N + i) * 8 + 3], g.state[((size_t)b * N + i) * 8 + 4]);
@@ -2003,9 +1936,13 @@ extern "C" int sigmaenv_cbf_inject_centers(sigmaenv_t* h, const float* centers) 
   h->cbf_centers_inject = centers;
   return SIGMAENV_OK;
 }
-static int cbf_apply_injected_centers(sigmaenv* h) {
+// sigmaenv_cbf_kin_kernel on `actions` into the handle's cbf_cxy / cbf_u / cbf_kin / cbf_clf, then the injected circle centres (if any) over the computed ones
+static int cbf_launch_kin(sigmaenv* h, const float* actions) {
+  const size_t BN = (size_t)h->B * h->N;
+  hipLaunchKernelGGL(cbf::sigmaenv_cbf_kin_kernel, dim3((unsigned)((BN + 255) / 256)), dim3(256), 0, h->stream, h->cfg, h->cbf_cfg, h->buf, actions,
+                     (float2*)h->cbf_cxy, (double2*)h->cbf_u, (cbf::Kin*)h->cbf_kin, (double2*)h->cbf_clf);
   if (!h->cbf_centers_inject) return SIGMAENV_OK;
-  HIPCHK(h, hipMemcpyAsync(h->cbf_cxy, h->cbf_centers_inject, (size_t)h->B * h->N * h->cbf_cfg.n_circles * sizeof(float2), hipMemcpyDeviceToDevice, h->stream));
+  HIPCHK(h, hipMemcpyAsync(h->cbf_cxy, h->cbf_centers_inject, BN * h->cbf_cfg.n_circles * sizeof(float2), hipMemcpyDeviceToDevice, h->stream));
   return SIGMAENV_OK;
 }
 
@@ -2014,10 +1951,7 @@ extern "C" int sigmaenv_cbf_rewards(sigmaenv_t* h, const float* actions, double*
   if (!actions) { h->err = "cbf_rewards: null actions"; return SIGMAENV_EINVAL; }
   if (!h->cbf_seg4) { h->err = "cbf_rewards: sigmaenv_cbf_attach has not been called"; return SIGMAENV_EINVAL; }
   HIPCHK(h, hipSetDevice(h->device));
-  const size_t BN = (size_t)h->B * h->N;
-  hipLaunchKernelGGL(cbf::sigmaenv_cbf_kin_kernel, dim3((unsigned)((BN + 255) / 256)), dim3(256), 0, h->stream, h->cfg, h->cbf_cfg, h->buf, actions,
-                     (float2*)h->cbf_cxy, (double2*)h->cbf_u, (cbf::Kin*)h->cbf_kin, (double2*)h->cbf_clf);
-  { const int rci = cbf_apply_injected_centers(h); if (rci) return rci; }
+  { const int rck = cbf_launch_kin(h, actions); if (rck) return rck; }
   const int slot = timer_begin(h, SIGMAENV_KERNEL_CBF_MARGIN);
   hipLaunchKernelGGL(cbf::sigmaenv_cbf_kernel, dim3(h->B), dim3(256), cbf::Smem::bytes(h->N, h->cbf_cfg.n_circles), h->stream, h->cfg, h->cbf_cfg, h->map,
                      h->buf, (const float4*)h->cbf_seg4, (const float*)h->cbf_segl, h->cbf_seg_stride, (const float2*)h->cbf_cxy, (const double2*)h->cbf_u,
@@ -2033,7 +1967,6 @@ extern "C" int sigmaenv_cbf_qp(sigmaenv_t* h, const float* actions, float* actio
   if (!h->cbf_seg4) { h->err = "cbf_qp: sigmaenv_cbf_attach has not been called"; return SIGMAENV_EINVAL; }
   if (h->N > cbf::QP_MAX_AGENTS) { h->err = "cbf_qp: more than 64 agents"; return SIGMAENV_EINVAL; }
   HIPCHK(h, hipSetDevice(h->device));
-  const size_t BN = (size_t)h->B * h->N;
   const int Cc = h->cbf_cfg.n_circles;
   // up to 32 vehicles: the LEAN instantiation (register-path Newton iterations only) for every env, then the full-layout one (Hessian and candidate list in LDS) for the
   // envs the first launch flagged; 33 .. 64: packed Hessian in LDS, candidate list in HBM (one workgroup per CU)
@@ -2065,11 +1998,7 @@ extern "C" int sigmaenv_cbf_qp(sigmaenv_t* h, const float* actions, float* actio
   }
   // the per-vehicle kinematics are evaluated inside the QP kernel; only with injected circle centres (test hook) they come from a launch of their own
   const bool own_kin = h->cbf_centers_inject != nullptr;
-  if (own_kin) {
-    hipLaunchKernelGGL(cbf::sigmaenv_cbf_kin_kernel, dim3((unsigned)((BN + 255) / 256)), dim3(256), 0, h->stream, h->cfg, h->cbf_cfg, h->buf, actions,
-                       (float2*)h->cbf_cxy, (double2*)h->cbf_u, (cbf::Kin*)h->cbf_kin, (double2*)h->cbf_clf);
-    { const int rci = cbf_apply_injected_centers(h); if (rci) return rci; }
-  }
+  if (own_kin) { const int rck = cbf_launch_kin(h, actions); if (rck) return rck; }
   const int slot = timer_begin(h, SIGMAENV_KERNEL_CBF_QP);
 #define SIGMA_QP_ARGS h->cfg, h->cbf_cfg, h->map, h->buf, (const float4*)h->cbf_seg4, (const float*)h->cbf_segl, h->cbf_seg_stride, (const float2*)(own_kin ? h->cbf_cxy : nullptr), \
                       (const double2*)(own_kin ? h->cbf_u : nullptr), (const cbf::Kin*)(own_kin ? h->cbf_kin : nullptr), (const double2*)(own_kin ? h->cbf_clf : nullptr), actions, actions_safe, u_opt, info, \

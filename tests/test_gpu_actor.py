@@ -251,6 +251,38 @@ def test_rollout_with_cbf_qp_equals_stepwise_calls():
     actor2.close()
 
 
+def test_rollout_leaves_the_handles_record_target_alone():
+    """sigmaenv_rollout hands every step's record target to the launch and never stores it in the handle: after a rollout into Y the next step records into the X of
+    the set_slab before it -- the row a twin env that never saw Y records -- and Y is not written again."""
+    from sigmarl_amd.shard import slab_width
+    torch, env, mlp, actor = _setup(B=4, N=4, seed=6)
+    _, env2, _, actor2 = _setup(B=4, N=4, seed=6)  # same seed: the twin's policy has the same weights
+    W = slab_width(env.N, env.D)
+    X, X2 = torch.zeros((env.B, W), device="cuda"), torch.zeros((env.B, W), device="cuda")
+    Y = torch.zeros((2, env.B, W), device="cuda")
+    env.set_slab(X)
+    actor.rollout(env, 2, slab=Y, seed=4, counter0=30)
+    env.sync()
+    assert Y[0].any() and Y[1].any() and not X.any()
+    Y_after_rollout = Y.clone()
+    a = torch.zeros((env.B, env.N, 2), device="cuda")
+    for t in range(2):  # the twin takes the same two steps and records nowhere
+        actor2.forward(env2, a, seed=4, counter=30 + t)
+        env2.step_autoreset(a, seed=4, counter=30 + t)
+    env2.set_slab(X2)
+    actor2.forward(env2, a, seed=4, counter=32)
+    for e in (env, env2):
+        e.step_autoreset(a, seed=4, counter=32)
+        e.sync()
+    assert X.any() and torch.equal(X, X2)
+    assert torch.equal(Y, Y_after_rollout)
+    assert torch.equal(env.state, env2.state)
+    for e in (env, env2):
+        e.close()
+    actor.close()
+    actor2.close()
+
+
 def test_fp32_rollout_equals_stepwise_fp32_calls_with_observation_noise():
     """sigmaenv_rollout_f32 (the reference's precision AND its default observation noise, both on the device) == the same T steps issued one by one:
     sigmaenv_actor_forward_f32 on the (noisy) observation buffer, then the fused step / record / reset -- bit for bit."""

@@ -454,6 +454,55 @@ def test_cbf_qp_is_bitwise_repeatable():
     dev.close()
 
 
+@pytest.mark.parametrize("nominal", ["rl", "clf"])
+@pytest.mark.parametrize("Cc", [1, 3, capi.CBF_MAX_CIRCLES])  # the smallest count (three lanes of a quad own no circle), the default, the largest (every lane owns one)
+@pytest.mark.parametrize("N", [3, 16])  # quads in a part of one wavefront; one full wavefront of quads
+def test_cbf_qp_one_lane_and_four_lane_kinematics_agree_bitwise(N, Cc, nominal):
+    """kin_vehicle<4> (the QP kernel's prologue) == kin_vehicle<1> (sigmaenv_cbf_kin_kernel) to the bit: the QP on the same states and actions, once plain and once
+    with the library's own circle centres injected -- then the one-lane kernel supplies kinematics, nominal action and CLF errors, and the centres are the same
+    values -- returns identical u_opt, safe action and info.  The centres in numpy float32 (cbf_qp.py:527-573) on the device's cr_sin / cr_cos of the yaw."""
+    import ctypes as C
+
+    import torch
+
+    B = 8
+    mp = load_map("cpm_entire")
+    p = Parameters(n_agents=N, scenario_type="cpm_entire", dt=0.05, rew_method="cbf", is_solve_qp=False, is_using_cbf_training=True, is_obs_noise=False,
+                   is_apply_mask=False, nom_controller_type=nominal, n_circles_approximate_vehicle=Cc)
+    dev = _hip_env(make_config(p, mp, B), mp)
+    seg_l, seg_r = cbf.load_segment_tables(mp)
+    dev.cbf_attach(cbf.make_cbf_config(p), seg_l, seg_r)
+    dev.env.reset_random(seed=5)
+    rng = np.random.default_rng(100 * N + Cc)
+    for _ in range(3):  # moving, steered vehicles: yaw, speed, steering and slip angle away from zero
+        dev.step(np.stack([rng.uniform(0.2, 1.2, (B, N)), rng.uniform(-0.5, 0.5, (B, N))], axis=-1).astype(np.float32))
+    st = dev.get(capi.BUF_STATE)
+    assert np.count_nonzero(st[..., 2:5]) >= 0.9 * st[..., 2:5].size
+
+    def cr(kind, x):
+        xd = torch.from_numpy(np.ascontiguousarray(x)).cuda()
+        out = torch.empty_like(xd)
+        assert dev.env.lib.trig_selftest(dev.env.h, kind, x.size, C.c_void_p(xd.data_ptr()), C.c_void_p(out.data_ptr())) == 0
+        dev.env.sync()
+        return out.cpu().numpy()
+
+    px, py, psi = st[..., 0:1], st[..., 1:2], st[..., 2]
+    sn, cs = cr(0, psi)[..., None], cr(1, psi)[..., None]
+    lx = np.array(list(dev.env.cbf_cfg.circle_x)[:Cc], np.float32)
+    zero = np.float32(0.0)
+    centers = np.stack([(cs * lx + (-sn) * zero) + px, (sn * lx + cs * zero) + py], axis=-1)
+    assert centers.dtype == np.float32 and centers.shape == (B, N, Cc, 2)
+    act = rng.uniform(-0.6, 1.2, (B, N, 2)).astype(np.float32)
+    four = dev.cbf_qp(act)
+    dev.cbf_inject_centers(centers)
+    one = dev.cbf_qp(act)
+    dev.cbf_inject_centers(None)
+    for name, x, y in zip(("safe action", "u_opt", "info"), four, one):  # every env, converged or not
+        bx, by = x.view(f"u{x.itemsize}"), y.view(f"u{y.itemsize}")
+        assert np.array_equal(bx, by), f"{name}: {int((bx != by).sum())} of {bx.size} values differ between the four-lane and the one-lane kinematics"
+    dev.close()
+
+
 def test_cbf_qp_hip_minimiser_vs_independent_solver_of_the_original_problem():
     """u of the HIP kernel == the interior-point solution of the ORIGINAL 2416-variable problem (tests/qp_original.py) within 1e-5 on the 48
     envs of the set-state fixture (16 agents, 3 circles, lambda penalty)."""
