@@ -409,6 +409,24 @@ int sigmaenv_actor_forward_f32(sigmaenv_t* h, sigmaenv_mlp32_t* m, const float* 
 int sigmaenv_mlp32_forward_rows(sigmaenv_t* h, sigmaenv_mlp32_t* m, const float* in, int32_t rows_per_block, int64_t row_stride, int32_t n_blocks, int64_t block_stride,
                                 float* out);
 
+/* ---- weights refreshed on the device (sigmaenv_load.inc) ------------------------------------------------------------------------------
+ * The learner's new parameters go into an EXISTING network handle without visiting the host: weights_dev / biases_dev are HOST arrays of DEVICE pointers, one per
+ * layer (sigmaenv_mlp32: the handle's n_layers; sigmaenv_actor: 4), tensors in torch.nn.Linear layout ([dims[l+1], dims[l]] row-major fp32, [dims[l+1]]) with the
+ * dimensions the handle was created with; 4-byte alignment suffices.  `h` supplies the device, the stream and sigmaenv_last_error.  The pack kernels (one launch
+ * per layer, one lane per destination slot) are enqueued on h's stream and rewrite the handle's buffers IN PLACE -- every slot, padding included; no allocation,
+ * no free, no host copy of a weight -- so launches enqueued on that stream before the call read the old weights, launches enqueued after it the new ones; work on
+ * OTHER streams that uses the handle must be ordered against the call by the caller.  The packed words are those sigmaenv_mlp32_create / sigmaenv_actor_create
+ * make from the same numbers (the host packers' integer roundings restated on the device): a loaded handle computes bit for bit what a fresh one does.
+ * sigmaenv_mlp32_load_device rewrites BOTH forms (exact and split; a network that is exact-only by its input width, dims[0] > 592, only the exact one) and reduces
+ * the split form's range predicate (!(|w| < 255): a NaN is outside) into one device word, copies those 4 bytes back on h's stream and waits for them -- the call's
+ * only host wait -- and then sets the mode in force: the mode last accepted by sigmaenv_mlp32_set_mode (SPLIT by default) when the weights allow it, else EXACT.
+ * A SPLIT network loaded with an out-of-range weight therefore runs EXACT and returns to SPLIT with the next in-range load; sigmaenv_mlp32_get_mode reports the
+ * mode in force; sigmaenv_mlp32_set_mode(SPLIT) is refused as before (SIGMAENV_EINVAL) while the weights are outside the range, but remembered for the next load.
+ * sigmaenv_actor_load_device rewrites the bf16 weights and the biases; low / high stay.  It does not wait.
+ * A null handle, pointer array or tensor, or a tensor that is not 4-byte aligned: SIGMAENV_EINVAL with sigmaenv_last_error set, before any launch. */
+int sigmaenv_mlp32_load_device(sigmaenv_t* h, sigmaenv_mlp32_t* m, const float* const* weights_dev, const float* const* biases_dev);
+int sigmaenv_actor_load_device(sigmaenv_t* h, sigmaenv_actor_t* a, const float* const* weights_dev, const float* const* biases_dev);
+
 /* n_steps x (sigmaenv_actor_forward; sigmaenv_step_autoreset) enqueued back to back (SyncDataCollectorCustom.rollout,
  * sigmarl/helper_training.py:687-788, without its per-step Python): actions_buf device f32 [B,N,2] scratch; optional records:
  * slab_base device f32 [n_steps, B, N*(D+1)+1], logp_base device f32 [n_steps, B, N], actions_rec device f32 [n_steps, B, N, 2].

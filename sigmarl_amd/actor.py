@@ -13,6 +13,8 @@ collector's opponent-modelling or prioritized-propagation policy in the fp32 dev
 ``Actor.rollout(obs_rec=...)`` records the observation every step's policy acted on, ``Mlp32.forward_rows`` / ``Critic.rollout_values`` run a network on the
 rollout's records where they lie (``sigmaenv_mlp32_forward_rows``); ``sigmarl_amd.learn`` builds the learner's batch from them.
 Weights come from any ``torch.nn.Sequential`` of four ``Linear`` layers (the parameter layout torchrl's shared-parameter MLP has).
+``Mlp32.load`` / ``Actor.load`` put a learner's updated CUDA parameters into the existing device networks (``sigmaenv_mlp32_load_device`` /
+``sigmaenv_actor_load_device``: packed by a kernel, no weight visits the host), so that collect -> torch update -> load -> collect stays on the device.
 
 The distribution heads (actor, priority actor) and ``random_ranks``: the draw of every row -- the counter-based generator keyed by (seed, the low 32 bits of
 counter, env_index_base + env, agent), Box-Muller with z0 the cosine and z1 the sine branch -- the action and the log-probability are pinned against fp64 on every
@@ -37,6 +39,47 @@ def make_mlp(obs_dim: int = 32, hidden: int = 256, n_out: int = 4) -> torch.nn.S
                                torch.nn.Linear(hidden, hidden), torch.nn.Tanh(), torch.nn.Linear(hidden, n_out))
 
 
+def load_source(dims, source, device):
+    """The parameters ``load`` takes, checked before any device call: ``source`` is a ``torch.nn.Module`` with the network's ``Linear`` stack or a sequence of
+    ``(weight, bias)`` tensors; float32 CUDA tensors on ``device`` (``TypeError`` otherwise) of the shapes ``[dims[l + 1], dims[l]]`` / ``[dims[l + 1]]`` and
+    ``len(dims) - 1`` layers (``ValueError`` otherwise).  Returns ``(weights, biases)``, detached."""
+    if isinstance(source, torch.nn.Module):
+        pairs = [(m.weight, m.bias) for m in source.modules() if isinstance(m, torch.nn.Linear)]
+    else:
+        try:
+            pairs = [tuple(q) for q in source]
+        except TypeError:
+            raise TypeError("load: source must be a torch.nn.Module or a sequence of (weight, bias) tensors") from None
+    n = len(dims) - 1
+    if len(pairs) != n or any(len(q) != 2 for q in pairs):
+        raise ValueError(f"load: the network has {n} Linear layers, the source {len(pairs)} (weight, bias) pairs")
+    ws, bs = [], []
+    for l, (w, b) in enumerate(pairs):
+        for t, shape, what, to in ((w, (int(dims[l + 1]), int(dims[l])), "weight", ws), (b, (int(dims[l + 1]),), "bias", bs)):
+            if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float32 or t.device != device:
+                raise TypeError(f"load: layer {l} {what} must be a float32 CUDA tensor on {device}")
+            if tuple(t.shape) != shape:
+                raise ValueError(f"load: layer {l} {what} has shape {list(t.shape)}, the network's is {list(shape)} (torch.nn.Linear layout)")
+            to.append(t.detach())
+    return ws, bs
+
+
+def _env_list(env):
+    envs = list(env) if isinstance(env, (list, tuple)) else [env]
+    if not envs:
+        raise ValueError("load: no env given")
+    if any(e.device != envs[0].device for e in envs):
+        raise ValueError("load: the envs must be on one device")
+    return envs
+
+
+def _by_library(envs):
+    groups = {}
+    for e in envs:
+        groups.setdefault(e.lib.path, []).append(e)
+    return list(groups.values())
+
+
 class Mlp32:
     """``sigmaenv_mlp32_*``: a Tanh MLP with hidden width 256 in fp32 on the matrix cores; ``forward(env, x[rows, in_dim]) -> [rows, out_dim]``.
     ``mode``: ``"split"`` (default: every fp32 operand as two fp16 numbers, three exact-product MFMAs per fp32 product, 3/16 of the fp32 matrix time; falls back
@@ -46,8 +89,11 @@ class Mlp32:
     def __init__(self, mlp: torch.nn.Module, lib: capi.Library | None = None, mode: str = "split"):
         if mode not in ("split", "exact"):
             raise ValueError("mode must be 'split' or 'exact'")
-        self.mode = mode
+        self.mode = mode          # the mode in force (after a ``load``: what the weights allow)
+        self._requested = mode    # the mode asked for
         self._handles = {}
+        self._handle_version = {}  # library path -> the version of the weights its handle holds (0: those of the constructor)
+        self._version, self._loaded = 0, None  # ``load``: count, and (weights, biases, ready event, stream) of the device snapshot
         lin = [m for m in mlp.modules() if isinstance(m, torch.nn.Linear)]
         if not (2 <= len(lin) <= 4) or any(m.out_features != 256 for m in lin[:-1]) or lin[-1].out_features > 32:
             raise ValueError("expected 2-4 Linear layers with hidden width 256 and at most 32 outputs")
@@ -63,8 +109,9 @@ class Mlp32:
         self._keep = (dims, ws, bs)
         self.h = self.handle(self.lib)
 
-    def handle(self, lib: capi.Library):
-        """The network's handle in ``lib`` (created on first use)."""
+    def handle(self, lib: capi.Library, env: SigmaEnv | None = None):
+        """The network's handle in ``lib`` (created on first use).  With ``env`` (an env of ``lib``, as every forward passes it): a handle that does not hold the
+        weights of the last ``load`` yet -- one of another library, or one created after it -- is brought up to date on ``env``'s stream first."""
         ent = self._handles.get(lib.path)
         if ent is None:
             dims, ws, bs = self._keep
@@ -74,16 +121,99 @@ class Mlp32:
             rc = lib.mlp32_create(len(ws), dims.ctypes.data_as(C.c_void_p), wp, bp, C.byref(h))
             if rc != 0:
                 raise RuntimeError(f"sigmaenv_mlp32_create failed with code {rc}")
-            if self.mode == "exact":
+            if self._requested == "exact":
                 lib.mlp32_set_mode(h, capi.MLP32_EXACT)
             ent = self._handles[lib.path] = (lib, h)
+            self._handle_version[lib.path] = 0
+        if env is not None and self._handle_version[lib.path] != self._version:
+            self._pack([env])
         return ent[1]
+
+    def _ordered_pack(self, group, call):
+        """``call(env)`` enqueues pack kernels on ``group[0]``'s stream; the envs of ``group`` share the handle they rewrite.  Before: that stream waits for the
+        snapshot and for what the other envs' streams hold (forwards that read the old weights).  After: the other streams wait for the pack."""
+        ws, bs, ready, made_on = self._loaded
+        first = group[0]
+        with torch.cuda.device(first.device):
+            first.stream.wait_event(ready)
+            if first.stream != made_on:
+                for t in ws + bs:
+                    t.record_stream(first.stream)
+            for e in group[1:]:
+                first.stream.wait_stream(e.stream)
+            call(first)
+            for e in group[1:]:
+                e.stream.wait_stream(first.stream)
+
+    def _device_pointers(self):
+        ws, bs = self._loaded[0], self._loaded[1]
+        PA = C.c_void_p * len(ws)
+        return PA(*[w.data_ptr() for w in ws]), PA(*[b.data_ptr() for b in bs])
+
+    def _pack(self, group):
+        """The snapshot of the last ``load`` into the handle of ``group``'s library."""
+        lib = group[0].lib
+        h = self.handle(lib)
+        wp, bp = self._device_pointers()
+
+        def call(env):
+            rc = lib.mlp32_load_device(env.h, h, wp, bp)
+            if rc != 0:
+                raise RuntimeError(f"sigmaenv_mlp32_load_device failed with code {rc}: {lib.last_error(env.h).decode()}")
+
+        self._ordered_pack(group, call)
+        self._handle_version[lib.path] = self._version
+
+    def _snapshot(self, envs, ws, bs):
+        """A device copy of the parameters (contiguous; ~1 MB) on the first env's stream, after what torch's current stream holds (the optimiser's kernels)."""
+        first = envs[0]
+        with torch.cuda.device(first.device):
+            first.stream.wait_stream(torch.cuda.current_stream(first.device))
+            with torch.cuda.stream(first.stream):
+                ws = [w.clone(memory_format=torch.contiguous_format) for w in ws]
+                bs = [b.clone(memory_format=torch.contiguous_format) for b in bs]
+                ready = torch.cuda.Event()
+                ready.record(first.stream)
+        self._loaded = (ws, bs, ready, first.stream)
+        self._version += 1
+
+    def _mode_in_force(self, lib) -> str:
+        return "split" if lib.mlp32_get_mode(self.handle(lib)) == capi.MLP32_SPLIT else "exact"
+
+    def load(self, env, source) -> str:
+        """New weights for the network, from the learner's tensors on the device: ``source`` is a ``torch.nn.Module`` with the same ``Linear`` stack or a sequence
+        of ``(weight, bias)`` float32 CUDA tensors on the env's device, in ``torch.nn.Linear`` layout (a CPU tensor, another dtype: ``TypeError``; another layer
+        count or shape: ``ValueError``; both before any device call; non-contiguous tensors are made contiguous on the device).  A kernel packs them into the
+        network's buffers in place (``sigmaenv_mlp32_load_device``): no weight visits the host, no buffer is allocated or freed, every handle stays valid, and
+        the network afterwards computes bit for bit what a new ``Mlp32`` made from the same numbers computes.  Returns the mode in force, which ``mode`` then
+        holds too: a network asked to run ``"split"`` runs ``"exact"`` while a weight is outside +-255 (or is a NaN) and returns to ``"split"`` with the next
+        load that is inside -- the call waits for the 4 bytes that say so, its only host wait.
+
+        Every handle: the parameters are first copied on the device (a snapshot); the handle of each given env's library is created if there is none and
+        rewritten now, a handle of another library -- or one made later -- when it is next used with an env of its library, on that env's stream.
+
+        Streams: ``env`` is one env or a sequence of envs that share this network on their own streams (the shards of ``bench.py --policy``).  The parameters are
+        read after everything torch's CURRENT stream holds at the call (the optimiser's kernels, in the common case where that is also the env's stream).  The
+        pack runs on the first env's stream after everything the other given envs' streams hold, so a forward enqueued on any of them before the call reads the
+        old weights whole; every forward enqueued on any of them after ``load`` returns reads the new ones.  A caller with FURTHER streams orders them itself:
+        parameters produced on another stream -- make torch's current stream wait for it before ``load``; forwards of this network on a stream of an env that was
+        not passed -- pass that env, or make that stream wait for ``envs[0].stream`` after ``load`` and ``envs[0].stream`` for it before."""
+        envs = _env_list(env)
+        ws, bs = load_source(self._keep[0], source, envs[0].device)
+        return self._load(envs, ws, bs)
+
+    def _load(self, envs, ws, bs) -> str:
+        self._snapshot(envs, ws, bs)
+        for group in _by_library(envs):
+            self._pack(group)
+        self.mode = self._mode_in_force(envs[0].lib)
+        return self.mode
 
     def set_mode(self, mode: str) -> str:
         """Switch every handle to ``"split"`` / ``"exact"``; returns the mode in force (a network outside the split form's range stays exact)."""
         if mode not in ("split", "exact"):
             raise ValueError("mode must be 'split' or 'exact'")
-        self.mode = mode
+        self.mode = self._requested = mode
         got = mode
         for lib, h in self._handles.values():
             lib.mlp32_set_mode(h, capi.MLP32_SPLIT if mode == "split" else capi.MLP32_EXACT)
@@ -93,7 +223,7 @@ class Mlp32:
     def close(self):
         for lib, h in getattr(self, "_handles", {}).values():
             lib.mlp32_destroy(h)
-        self._handles = {}
+        self._handles, self._handle_version = {}, {}
         self.h = None
 
     def __del__(self):  # pragma: no cover
@@ -112,7 +242,7 @@ class Mlp32:
             out = torch.empty((*x.shape[:-1], self.out_dim), dtype=torch.float32, device=x.device)
         if rows == 0:
             return out
-        rc = env.lib.mlp32_forward(env.h, self.handle(env.lib), C.c_void_p(x.data_ptr()), rows, C.c_void_p(out.data_ptr()))
+        rc = env.lib.mlp32_forward(env.h, self.handle(env.lib, env), C.c_void_p(x.data_ptr()), rows, C.c_void_p(out.data_ptr()))
         if rc != 0:
             raise RuntimeError(f"sigmaenv_mlp32_forward failed with code {rc}: {env.lib.last_error(env.h).decode()}")
         return out
@@ -135,7 +265,7 @@ class Mlp32:
             raise TypeError(f"out must be a contiguous float32 CUDA tensor of {nb * rpb * self.out_dim} elements")
         if rpb == 0 or nb == 0:
             return out
-        rc = env.lib.mlp32_forward_rows(env.h, self.handle(env.lib), C.c_void_p(base.data_ptr() + 4 * offset), rpb, rs, nb, bs, C.c_void_p(out.data_ptr()))
+        rc = env.lib.mlp32_forward_rows(env.h, self.handle(env.lib, env), C.c_void_p(base.data_ptr() + 4 * offset), rpb, rs, nb, bs, C.c_void_p(out.data_ptr()))
         if rc != 0:
             raise RuntimeError(f"sigmaenv_mlp32_forward_rows failed with code {rc}: {env.lib.last_error(env.h).decode()}")
         return out
@@ -205,7 +335,7 @@ class PriorityNet(Mlp32):
         scratch, sc, lp = torch.empty((env.B * env.N, 2), **kw), torch.empty((env.B, env.N), **kw), torch.empty((env.B, env.N), **kw)
         ranks = torch.empty((env.B, env.N), dtype=torch.int32, device=env.device)
         p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
-        rc = env.lib.priority_forward(env.h, self.handle(env.lib), p(obs), p(scratch), p(sc), p(lp), p(ranks), int(seed), int(counter), int(bool(deterministic)))
+        rc = env.lib.priority_forward(env.h, self.handle(env.lib, env), p(obs), p(scratch), p(sc), p(lp), p(ranks), int(seed), int(counter), int(bool(deterministic)))
         if rc != 0:
             raise RuntimeError(f"sigmaenv_priority_forward failed with code {rc}: {env.lib.last_error(env.h).decode()}")
         return sc, lp, ranks
@@ -249,10 +379,11 @@ class Actor:
         # the bf16 kernel handle exists only for the widths its MFMA tiling takes (sigmaenv_actor_create: obs_dim in {8, 16, 24, 32}); other
         # observation switches (e.g. is_obs_steering: 35) run the fp32 network, which takes any width
         self._bf16 = {}  # library path -> (library, handle): see Mlp32
+        self._bf16_version = {}  # library path -> the version of the weights the handle holds (Mlp32._version)
         if precision == "bf16":
             self._bf16_handle(self.lib)
 
-    def _bf16_handle(self, lib: capi.Library):
+    def _bf16_handle(self, lib: capi.Library, env: SigmaEnv | None = None):
         ent = self._bf16.get(lib.path)
         if ent is None:
             if self.obs_dim not in (8, 16, 24, 32):
@@ -262,12 +393,40 @@ class Actor:
             if rc != 0:
                 raise RuntimeError(f"sigmaenv_actor_create failed with code {rc}")
             ent = self._bf16[lib.path] = (lib, h)
+            self._bf16_version[lib.path] = 0
+        if env is not None and self._bf16_version[lib.path] != self._mlp32._version:
+            self._pack_bf16([env])
         return ent[1]
+
+    def _pack_bf16(self, group):
+        lib = group[0].lib
+        h = self._bf16_handle(lib)
+        wp, bp = self._mlp32._device_pointers()
+
+        def call(env):
+            rc = lib.actor_load_device(env.h, h, wp, bp)
+            if rc != 0:
+                raise RuntimeError(f"sigmaenv_actor_load_device failed with code {rc}: {lib.last_error(env.h).decode()}")
+
+        self._mlp32._ordered_pack(group, call)
+        self._bf16_version[lib.path] = self._mlp32._version
+
+    def load(self, env, source) -> str:
+        """New weights for the actor from the learner's tensors on the device (``Mlp32.load``: the same ``source``, refusals, stream order and host wait; ``env``
+        is one env or the shards that share this actor).  Refreshes the fp32 network and the bf16 one wherever it exists (an actor of ``precision="bf16"`` gets
+        it for every given env's library); ``low`` / ``high`` stay.  Returns the fp32 network's mode in force."""
+        envs = _env_list(env)
+        ws, bs = load_source([self.obs_dim, 256, 256, 256, 4], source, envs[0].device)
+        mode = self._mlp32._load(envs, ws, bs)
+        for group in _by_library(envs):
+            if self.precision == "bf16" or group[0].lib.path in self._bf16:
+                self._pack_bf16(group)
+        return mode
 
     def close(self):
         for lib, h in getattr(self, "_bf16", {}).values():
             lib.actor_destroy(h)
-        self._bf16 = {}
+        self._bf16, self._bf16_version = {}, {}
         if getattr(self, "_mlp32", None) is not None:
             self._mlp32.close()
 
@@ -301,12 +460,12 @@ class Actor:
         p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
         if (precision or self.precision) == "fp32":
             lo, hi = self._keep[-2], self._keep[-1]
-            rc = env.lib.actor_forward_f32(env.h, self._mlp32.handle(env.lib), p(obs), p(self._scratch_out4(env)), lo.ctypes.data_as(C.c_void_p), hi.ctypes.data_as(C.c_void_p),
+            rc = env.lib.actor_forward_f32(env.h, self._mlp32.handle(env.lib, env), p(obs), p(self._scratch_out4(env)), lo.ctypes.data_as(C.c_void_p), hi.ctypes.data_as(C.c_void_p),
                                             p(actions), p(log_prob), p(loc_scale), int(seed), int(counter), int(bool(deterministic)))
             if rc != 0:
                 raise RuntimeError(f"sigmaenv_actor_forward_f32 failed with code {rc}: {env.lib.last_error(env.h).decode()}")
             return actions
-        rc = env.lib.actor_forward(env.h, self._bf16_handle(env.lib), p(obs), p(actions), p(log_prob), p(loc_scale), int(seed), int(counter), int(bool(deterministic)))
+        rc = env.lib.actor_forward(env.h, self._bf16_handle(env.lib, env), p(obs), p(actions), p(log_prob), p(loc_scale), int(seed), int(counter), int(bool(deterministic)))
         if rc != 0:
             raise RuntimeError(f"sigmaenv_actor_forward failed with code {rc}: {env.lib.last_error(env.h).decode()}")
         return actions
@@ -349,7 +508,7 @@ class Actor:
                 raise ValueError("the rollout wrappers run the fp32 actor (precision='fp32')")
             opts = self._wrapper_opts(env, int(n_steps), wrapper, priority, tentative, ranks, scores, score_log_prob)
             lo, hi = self._keep[-2], self._keep[-1]
-            rc = env.lib.rollout_f32_ex(env.h, self._mlp32.handle(env.lib), lo.ctypes.data_as(C.c_void_p), hi.ctypes.data_as(C.c_void_p), p(self._scratch_out4(env)),
+            rc = env.lib.rollout_f32_ex(env.h, self._mlp32.handle(env.lib, env), lo.ctypes.data_as(C.c_void_p), hi.ctypes.data_as(C.c_void_p), p(self._scratch_out4(env)),
                                          int(n_steps), p(scratch), p_slab, p(log_prob), p(actions), int(seed), int(counter0), int(path_first), int(path_count),
                                          int(bool(deterministic)), C.byref(opts))
             if rc != 0:
@@ -357,13 +516,13 @@ class Actor:
             return
         if (precision or self.precision) == "fp32":
             lo, hi = self._keep[-2], self._keep[-1]
-            rc = env.lib.rollout_f32(env.h, self._mlp32.handle(env.lib), lo.ctypes.data_as(C.c_void_p), hi.ctypes.data_as(C.c_void_p), p(self._scratch_out4(env)), int(n_steps),
+            rc = env.lib.rollout_f32(env.h, self._mlp32.handle(env.lib, env), lo.ctypes.data_as(C.c_void_p), hi.ctypes.data_as(C.c_void_p), p(self._scratch_out4(env)), int(n_steps),
                                       p(scratch), p_slab, p(log_prob), p(actions), int(seed), int(counter0), int(path_first), int(path_count),
                                       int(bool(deterministic)))
             if rc != 0:
                 raise RuntimeError(f"sigmaenv_rollout_f32 failed with code {rc}: {env.lib.last_error(env.h).decode()}")
             return
-        rc = env.lib.rollout(env.h, self._bf16_handle(env.lib), int(n_steps), p(scratch), p_slab, p(log_prob), p(actions), int(seed), int(counter0), int(path_first),
+        rc = env.lib.rollout(env.h, self._bf16_handle(env.lib, env), int(n_steps), p(scratch), p_slab, p(log_prob), p(actions), int(seed), int(counter0), int(path_first),
                               int(path_count), int(bool(deterministic)))
         if rc != 0:
             raise RuntimeError(f"sigmaenv_rollout failed with code {rc}: {env.lib.last_error(env.h).decode()}")
@@ -387,7 +546,7 @@ class Actor:
         opts.rank_rec = rec(ranks, (T, env.B, env.N), torch.int32, "ranks")
         if isinstance(priority, PriorityNet):
             opts.priority_source = capi.PRIORITY_NET
-            opts.priority_net = priority.handle(env.lib)
+            opts.priority_net = priority.handle(env.lib, env)
             opts.score_rec = rec(scores, (T, env.B, env.N), torch.float32, "scores")
             opts.score_logp_rec = rec(score_log_prob, (T, env.B, env.N), torch.float32, "score_log_prob")
         else:

@@ -362,8 +362,12 @@ __global__ void sigmaenv_actor_head_kernel(const float* __restrict__ out4, int R
 struct sigmaenv_mlp32 {
   Mlp32Weights w{};
   Mlp32sWeights ws{};   // the split-fp16 form of the same network (sigmaenv_mlp32s.inc)
-  int mode = SIGMAENV_MLP32_SPLIT;
-  bool split_ok = true;  // every weight inside the split form's range
+  int mode = SIGMAENV_MLP32_SPLIT;       // the mode in force
+  int requested = SIGMAENV_MLP32_SPLIT;  // the mode asked for (sigmaenv_mlp32_set_mode): in force again when sigmaenv_mlp32_load_device brings the weights back into range
+  bool split_ok = true;    // the split form may run: every weight inside its range and split_fits
+  bool split_fits = true;  // the split kernel's LDS takes the input width (dims[0] <= 592)
+  int dims[MLP32_MAX_LAYERS + 1] = {};
+  uint32_t* range_word = nullptr;  // device word of sigmaenv_mlp32_load_device's range reduction
   size_t smem_s = 0;
   std::vector<void*> allocs;
   int in_dim = 0, out_dim = 0;
@@ -388,6 +392,9 @@ extern "C" int sigmaenv_mlp32_create(int32_t n_layers, const int32_t* dims, cons
   m->in_dim = dims[0];
   m->out_dim = dims[n_layers];
   m->w.n_layers = n_layers;
+  for (int l = 0; l <= n_layers; ++l) m->dims[l] = dims[l];
+  if (hipMalloc((void**)&m->range_word, 4) != hipSuccess) { sigmaenv_mlp32_destroy(m); return SIGMAENV_ENOMEM; }
+  m->allocs.push_back(m->range_word);
   for (int l = 0; l < n_layers; ++l) {
     const int K = dims[l], F = dims[l + 1];
     const int Kp = (K + 7) / 8 * 8, Fp = (F + 31) / 32 * 32, KQ = Kp / 8;
@@ -419,7 +426,8 @@ extern "C" int sigmaenv_mlp32_create(int32_t n_layers, const int32_t* dims, cons
   for (int l = 0; l < n_layers && m->split_ok; ++l)
     for (size_t i = 0, n = (size_t)dims[l] * dims[l + 1]; i < n; ++i)
       if (!(std::fabs(weights[l][i]) < 255.0f)) { m->split_ok = false; break; }
-  for (int l = 0; l < n_layers && m->split_ok; ++l) {
+  // (the split buffers exist for a network outside the range as well -- never read while split_ok is false --: sigmaenv_mlp32_load_device may bring it into range)
+  for (int l = 0; l < n_layers; ++l) {
     const int K = dims[l], F = dims[l + 1];
     const bool last = l + 1 == n_layers;
     const std::vector<uint16_t> pk = mlp32s_pack(weights[l], F, K, l > 0, last);
@@ -440,7 +448,8 @@ extern "C" int sigmaenv_mlp32_create(int32_t n_layers, const int32_t* dims, cons
     m->ws.KB[l] = (K + 15) / 16; m->ws.F[l] = F;
   }
   m->smem_s = (size_t)(m->ws.KB[0] > 16 ? m->ws.KB[0] : 16) * 256 * 16 + (2 * 16 * 64 + (MLP32_MAX_LAYERS - 1) * MLP32_H + 32) * sizeof(float);
-  if (!m->split_ok || m->smem_s > 160 * 1024) { m->split_ok = false; m->mode = SIGMAENV_MLP32_EXACT; }
+  m->split_fits = m->smem_s <= 160 * 1024;
+  if (!m->split_ok || !m->split_fits) { m->split_ok = false; m->mode = SIGMAENV_MLP32_EXACT; }
   *out = m;
   return SIGMAENV_OK;
 }
@@ -448,8 +457,11 @@ extern "C" int sigmaenv_mlp32_create(int32_t n_layers, const int32_t* dims, cons
 // SIGMAENV_MLP32_EXACT / SIGMAENV_MLP32_SPLIT (include/sigmaenv.h); a network with a weight outside the split form's range stays exact
 extern "C" int sigmaenv_mlp32_set_mode(sigmaenv_mlp32* m, int32_t mode) {
   if (!m || (mode != SIGMAENV_MLP32_EXACT && mode != SIGMAENV_MLP32_SPLIT)) return SIGMAENV_EINVAL;
-  if (mode == SIGMAENV_MLP32_SPLIT && !m->split_ok) return SIGMAENV_EINVAL;
-  m->mode = mode;
+  if (mode == SIGMAENV_MLP32_SPLIT && !m->split_ok) {
+    if (m->split_fits) m->requested = mode;  // (refused for the weights the handle holds: in force with the next sigmaenv_mlp32_load_device inside the range)
+    return SIGMAENV_EINVAL;
+  }
+  m->mode = m->requested = mode;
   return SIGMAENV_OK;
 }
 extern "C" int sigmaenv_mlp32_get_mode(const sigmaenv_mlp32* m) { return m ? m->mode : SIGMAENV_EINVAL; }
