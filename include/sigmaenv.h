@@ -427,6 +427,38 @@ int sigmaenv_mlp32_forward_rows(sigmaenv_t* h, sigmaenv_mlp32_t* m, const float*
 int sigmaenv_mlp32_load_device(sigmaenv_t* h, sigmaenv_mlp32_t* m, const float* const* weights_dev, const float* const* biases_dev);
 int sigmaenv_actor_load_device(sigmaenv_t* h, sigmaenv_actor_t* a, const float* const* weights_dev, const float* const* biases_dev);
 
+/* ---- the fp32 network differentiated (sigmaenv_grad.inc) -------------------------------------------------------------------------------
+ * Layers l = 0 .. n - 1 of the handle, z_l = W_l a_l + b_l, a_{l+1} = tanh(z_l) for l < n - 1, a_0 = the input rows.  The rows are addressed as in
+ * sigmaenv_mlp32_forward_rows (row r = t * rows_per_block + b at in + t * block_stride + b * row_stride floats, 4-byte alignment suffices; a dense [rows, dims[0]]
+ * input is rows_per_block = rows, row_stride = dims[0], n_blocks = 1), so a minibatch of whole time slices of a rollout record is read where it lies.  The weights
+ * are the handle's own (what sigmaenv_mlp32_create / sigmaenv_mlp32_load_device put there): forward and gradient cannot disagree about them.  Everything is
+ * enqueued on h's stream; nothing waits.
+ *   sigmaenv_mlp32_forward_save   out [rows, dims[n]] := the network, bit for bit what sigmaenv_mlp32_forward_rows writes with the handle in EXACT mode -- the
+ *       EXACT chain runs whatever mode is in force --, and acts [n - 1][rows][256] := every hidden layer's tanh output as the next layer consumed it
+ *       (device f32, 16-byte aligned).
+ *   sigmaenv_mlp32_backward_workspace   *n_floats := the floats of `workspace` for `rows` rows (0 for rows = 0).
+ *   sigmaenv_mlp32_backward   with g_{n-1} = dout [rows, dims[n]] (device f32):
+ *           g_{l-1} = (g_l W_l) (.) (1 - a_l^2)  for l = n - 1 .. 1;     grad_w[l] := g_l^T a_l  ([dims[l+1], dims[l]], torch.nn.Linear layout);     grad_b[l] := sum_rows g_l
+ *       grad_w / grad_b: HOST arrays of DEVICE pointers, one per layer, as sigmaenv_mlp32_load_device takes the weights; OVERWRITTEN, not accumulated.  `in` and the
+ *       four row arguments, and `acts`, are those of the sigmaenv_mlp32_forward_save call; workspace: device f32, 16-byte aligned; after the call its first
+ *       (n - 1) * rows * 256 floats hold g_l, l = 0 .. n - 2, as [n - 1][rows][256] (the rest: the ranges' partial sums).  The gradient with respect to the input is
+ *       not computed.
+ * Arithmetic and summation order.  fp32 throughout; every sum is an fma chain (v_mfma_f32_32x32x2_f32: one rounding per term) or a chain of fp32 additions:
+ *   g_{l-1}[r, k]  the chain over the features f = 0, 1, .. of g_l[r, f] W_l[f, k] from 0, times fl(1 - a^2) formed with ONE rounding (fma(-a, a, 1)), rounded once more;
+ *   grad_w[l][f, k]  the rows are cut into ranges of len = max(256, ceil(rows / 64) rounded up to a multiple of 64) rows: range i = [i len, min(rows, (i + 1) len));
+ *       per range the chain over its rows in order from 0, then the ranges' partial sums added in range order;
+ *   grad_b[l][f]  per range the chain of additions over its even rows (by offset in the range) and the one over its odd rows, added, then the ranges in order.
+ * The partition depends on `rows` alone -- not on the device, the environment or the order in which workgroups arrive -- and no atomics are used: the same inputs give
+ * the same bits on every run.  Rows past the end of a tile or a range and padded columns contribute exact zeros.  rows = 0: the gradients are written as zeros and
+ * no row is read (in / acts / dout / workspace may be NULL).
+ * A null handle, gradient array or tensor, a misaligned pointer, a row_stride below dims[0], negative counts: SIGMAENV_EINVAL with sigmaenv_last_error set, before
+ * any launch. */
+int sigmaenv_mlp32_forward_save(sigmaenv_t* h, sigmaenv_mlp32_t* m, const float* in, int32_t rows_per_block, int64_t row_stride, int32_t n_blocks, int64_t block_stride,
+                                float* out, float* acts);
+int sigmaenv_mlp32_backward_workspace(const sigmaenv_mlp32_t* m, int64_t rows, uint64_t* n_floats);
+int sigmaenv_mlp32_backward(sigmaenv_t* h, sigmaenv_mlp32_t* m, const float* in, int32_t rows_per_block, int64_t row_stride, int32_t n_blocks, int64_t block_stride,
+                            const float* acts, const float* dout, float* workspace, float* const* grad_w, float* const* grad_b);
+
 /* n_steps x (sigmaenv_actor_forward; sigmaenv_step_autoreset) enqueued back to back (SyncDataCollectorCustom.rollout,
  * sigmarl/helper_training.py:687-788, without its per-step Python): actions_buf device f32 [B,N,2] scratch; optional records:
  * slab_base device f32 [n_steps, B, N*(D+1)+1], logp_base device f32 [n_steps, B, N], actions_rec device f32 [n_steps, B, N, 2].

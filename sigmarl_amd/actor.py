@@ -64,6 +64,34 @@ def load_source(dims, source, device):
     return ws, bs
 
 
+def source_pairs(source):
+    """The ``(weight, bias)`` tensors of a ``load`` source as they are (not detached): what ``apply`` credits the gradients to."""
+    if isinstance(source, torch.nn.Module):
+        return [(m.weight, m.bias) for m in source.modules() if isinstance(m, torch.nn.Linear)]
+    return [tuple(q) for q in source]
+
+
+class _Mlp32Function(torch.autograd.Function):
+    """``Mlp32.apply``: ``sigmaenv_mlp32_forward_save`` forwards, ``sigmaenv_mlp32_backward`` backwards; the inputs are the network's parameters (weight, bias per
+    layer), the rows are a constant."""
+
+    @staticmethod
+    def forward(ctx, net, env, spec, shape, *params):
+        y, acts = net._forward_save(env, spec)
+        ctx.net, ctx.env, ctx.spec, ctx.acts = net, env, spec, acts
+        ctx.version = net._version
+        return y.view(shape)
+
+    @staticmethod
+    def backward(ctx, dy):
+        net = ctx.net
+        if net._version != ctx.version:
+            raise RuntimeError("Mlp32.apply: load() replaced the network's weights between this forward and its backward")
+        gw, gb = net._backward(ctx.env, ctx.spec, ctx.acts, dy)
+        ctx.acts = None
+        return (None, None, None, None, *[t for q in zip(gw, gb) for t in q])
+
+
 def _env_list(env):
     envs = list(env) if isinstance(env, (list, tuple)) else [env]
     if not envs:
@@ -107,7 +135,13 @@ class Mlp32:
         ws = [np.ascontiguousarray(m.weight.detach().cpu().numpy(), np.float32) for m in lin]
         bs = [np.ascontiguousarray(m.bias.detach().cpu().numpy(), np.float32) for m in lin]
         self._keep = (dims, ws, bs)
+        self._remember([(m.weight, m.bias) for m in lin])
         self.h = self.handle(self.lib)
+
+    def _remember(self, pairs):
+        """The tensors ``apply`` differentiates with respect to -- those the packed weights were last made from -- and their versions then."""
+        self._params = [t for q in pairs for t in q]
+        self._param_versions = [t._version for t in self._params]
 
     def handle(self, lib: capi.Library, env: SigmaEnv | None = None):
         """The network's handle in ``lib`` (created on first use).  With ``env`` (an env of ``lib``, as every forward passes it): a handle that does not hold the
@@ -200,7 +234,9 @@ class Mlp32:
         not passed -- pass that env, or make that stream wait for ``envs[0].stream`` after ``load`` and ``envs[0].stream`` for it before."""
         envs = _env_list(env)
         ws, bs = load_source(self._keep[0], source, envs[0].device)
-        return self._load(envs, ws, bs)
+        mode = self._load(envs, ws, bs)
+        self._remember(source_pairs(source))
+        return mode
 
     def _load(self, envs, ws, bs) -> str:
         self._snapshot(envs, ws, bs)
@@ -271,6 +307,98 @@ class Mlp32:
         return out
 
 
+    # ---- the network differentiated (sigmaenv_mlp32_forward_save / sigmaenv_mlp32_backward) ----
+    def _rows_spec(self, x, rows):
+        if (x is None) == (rows is None):
+            raise TypeError("apply: either x [rows, in_dim] or rows = (base, offset, rows_per_block, row_stride, n_blocks, block_stride)")
+        if x is not None:
+            if not (isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.float32 and x.is_contiguous() and x.dim() >= 1 and x.shape[-1] == self.in_dim):
+                raise TypeError(f"input must be a contiguous float32 CUDA tensor [..., {self.in_dim}]")
+            if x.requires_grad:
+                raise NotImplementedError("apply: the gradient with respect to the input is not built (x.requires_grad)")
+            return (x, 0, x.numel() // self.in_dim, self.in_dim, 1, 0), (*x.shape[:-1], self.out_dim)
+        base, offset, rpb, rs, nb, bs = rows
+        if not (isinstance(base, torch.Tensor) and base.is_cuda and base.dtype == torch.float32 and base.is_contiguous()):
+            raise TypeError("the rows must lie in a contiguous float32 CUDA tensor")
+        if base.requires_grad:
+            raise NotImplementedError("apply: the gradient with respect to the input is not built (rows base requires_grad)")
+        offset, rpb, rs, nb, bs = int(offset), int(rpb), int(rs), int(nb), int(bs)
+        if rpb < 0 or nb < 0 or offset < 0 or rs < self.in_dim or bs < 0:
+            raise ValueError(f"apply: counts and offsets must be >= 0 and row_stride >= the input width {self.in_dim}")
+        if rpb and nb and offset + (nb - 1) * bs + (rpb - 1) * rs + self.in_dim > base.numel():
+            raise ValueError("apply: the last row ends beyond the tensor")
+        return (base, offset, rpb, rs, nb, bs), (nb, rpb, self.out_dim)
+
+    def _chk_grad(self, env, rc, what):
+        if rc != 0:
+            raise RuntimeError(f"sigmaenv_{what} failed with code {rc}: {env.lib.last_error(env.h).decode()}")
+
+    def _forward_save(self, env, spec):
+        """(y [rows, out_dim], acts [n_layers - 1, rows, 256]) on the env's stream, ordered after and before torch's current stream."""
+        base, offset, rpb, rs, nb, bs = spec
+        n, dev = rpb * nb, env.device
+        cur = torch.cuda.current_stream(dev)
+        y = torch.empty((n, self.out_dim), dtype=torch.float32, device=dev)
+        acts = torch.empty((len(self._keep[1]) - 1, n, 256), dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            h = self.handle(env.lib, env)
+            env.stream.wait_stream(cur)
+            self._chk_grad(env, env.lib.mlp32_forward_save(env.h, h, C.c_void_p(base.data_ptr() + 4 * offset), rpb, rs, nb, bs, C.c_void_p(y.data_ptr()),
+                                                          C.c_void_p(acts.data_ptr())), "mlp32_forward_save")
+            cur.wait_stream(env.stream)
+        for t in (base, y, acts):
+            t.record_stream(env.stream)
+        return y, acts
+
+    def _backward(self, env, spec, acts, dout):
+        """(grad_w, grad_b) lists in ``torch.nn.Linear`` layout: ``sigmaenv_mlp32_backward`` on the env's stream, ordered as ``_forward_save``."""
+        base, offset, rpb, rs, nb, bs = spec
+        n, dev = rpb * nb, env.device
+        dims = [int(d) for d in self._keep[0]]
+        cur = torch.cuda.current_stream(dev)
+        dout = dout.reshape(n, self.out_dim).to(torch.float32).contiguous()
+        nf = C.c_uint64()
+        h = self.handle(env.lib)
+        rc = env.lib.mlp32_backward_workspace(h, n, C.byref(nf))
+        if rc != 0:
+            raise RuntimeError(f"sigmaenv_mlp32_backward_workspace failed with code {rc}")
+        ws = torch.empty((max(int(nf.value), 4),), dtype=torch.float32, device=dev)
+        gw = [torch.empty((dims[l + 1], dims[l]), dtype=torch.float32, device=dev) for l in range(len(dims) - 1)]
+        gb = [torch.empty((dims[l + 1],), dtype=torch.float32, device=dev) for l in range(len(dims) - 1)]
+        PA = C.c_void_p * len(gw)
+        with torch.cuda.device(dev):
+            env.stream.wait_stream(cur)
+            self._chk_grad(env, env.lib.mlp32_backward(env.h, h, C.c_void_p(base.data_ptr() + 4 * offset), rpb, rs, nb, bs, C.c_void_p(acts.data_ptr()),
+                                                      C.c_void_p(dout.data_ptr()), C.c_void_p(ws.data_ptr()), PA(*[t.data_ptr() for t in gw]),
+                                                      PA(*[t.data_ptr() for t in gb])), "mlp32_backward")
+            cur.wait_stream(env.stream)
+        for t in [base, acts, dout, ws] + gw + gb:
+            t.record_stream(env.stream)
+        return gw, gb
+
+    def apply(self, env: SigmaEnv, x: torch.Tensor | None = None, *, rows=None) -> torch.Tensor:
+        """The network with a ``grad_fn``: ``y = apply(env, x)`` for dense ``x [..., in_dim]`` (``y [..., out_dim]``) or ``apply(env, rows=(base, offset,
+        rows_per_block, row_stride, n_blocks, block_stride))`` for rows read where they lie, as ``forward_rows`` addresses them (``y [n_blocks, rows_per_block,
+        out_dim]``) -- a minibatch of whole time slices of a rollout record.  A ``torch.autograd.Function`` whose inputs are the parameters of the module the
+        network was built or last ``load``ed from (float32 CUDA tensors on the env's device): ``loss.backward()`` fills their ``.grad``, so ``clip_grad_norm_`` and
+        ``torch.optim.Adam`` work unchanged.  The forward is the EXACT fp32 chain whatever mode the network runs in (``sigmaenv_mlp32_forward_save``); the gradient
+        with respect to the input is not built (``x.requires_grad``: ``NotImplementedError``).
+
+        Stale weights: the packed weights on the device are those of construction / the last ``load``.  If a parameter has been modified in place since (the
+        optimiser stepped and ``load`` was not called) ``apply`` raises ``RuntimeError``: the forward would use the old numbers and credit the gradient to the new.
+
+        Streams: the kernels run on the env's stream after everything torch's current stream holds, and torch's current stream then waits for them -- forwards
+        and backwards alike (``load``'s discipline)."""
+        spec, shape = self._rows_spec(x, rows)
+        for t in self._params:
+            if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.device == env.device):
+                raise TypeError(f"apply: the network's parameters must be float32 CUDA tensors on {env.device}: load(env, module) with the module on the device first")
+        if any(t._version != v for t, v in zip(self._params, self._param_versions)):
+            raise RuntimeError("apply: a parameter changed since the network was built or last loaded (an optimiser step?): call load(env, module) first -- the device "
+                               "holds the old weights")
+        return _Mlp32Function.apply(self, env, spec, shape, *self._params)
+
+
 def check_record(t, shape, what: str):
     """A rollout record the device loop writes: a contiguous float32 CUDA tensor of exactly ``shape``."""
     if not isinstance(t, torch.Tensor) or not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == tuple(shape)):
@@ -310,6 +438,24 @@ class Critic(Mlp32):
         sv = self.forward_rows(env, obs_rec, e0 * N * D, B, N * D, T, Bt * N * D, out=state_value)
         nv = self.forward_rows(env, slab, e0 * W, B, W, T, Bt * W, out=next_state_value)
         return sv.view(T, B), nv.view(T, B)
+
+
+    def apply(self, env: SigmaEnv, record: torch.Tensor, T: int | None = None, env_first: int = 0, t_first: int = 0) -> torch.Tensor:  # noqa: D102
+        """``[T, B]`` state values with a ``grad_fn`` (``Mlp32.apply``) of the time slices ``[t_first, t_first + T)`` of a rollout record, read where they lie as
+        ``rollout_values`` reads them: ``record`` is the root-observation record ``obs_rec [>= t_first + T, Bt, N, D]`` or the record rows ``slab [.., Bt, W]``
+        (their observation part: the next observations); ``env`` owns the envs ``[env_first, env_first + env.B)`` of the buffer."""
+        B, N, D = env.B, env.N, env.D
+        if self.in_dim != N * D or self.out_dim != 1:
+            raise ValueError(f"the critic maps n_agents * obs_dim = {N * D} inputs to 1 value, not {self.in_dim} to {self.out_dim}")
+        if not isinstance(record, torch.Tensor) or record.dim() < 3:
+            raise TypeError("record must be obs_rec [T, Bt, N, D] or slab [T, Bt, W]")
+        Bt, width = record.shape[1], record[0, 0].numel()
+        if width not in (N * D, N * (D + 1) + 1):
+            raise TypeError(f"record rows of {width} floats: neither [N, D] observations nor record rows of {N * (D + 1) + 1}")
+        T, e0, t0 = int(record.shape[0] - t_first if T is None else T), int(env_first), int(t_first)
+        if T < 0 or t0 < 0 or t0 + T > record.shape[0] or not 0 <= e0 <= Bt - B:
+            raise ValueError(f"time slices [{t0}, {t0 + T}) / envs [{e0}, {e0 + B}) are not inside the record {list(record.shape)}")
+        return super().apply(env, rows=(record, (t0 * Bt + e0) * width, B, width, T, Bt * width)).view(T, B)
 
 
 def make_priority_mlp(obs_dim: int, hidden: int = 256) -> torch.nn.Sequential:
@@ -418,10 +564,16 @@ class Actor:
         envs = _env_list(env)
         ws, bs = load_source([self.obs_dim, 256, 256, 256, 4], source, envs[0].device)
         mode = self._mlp32._load(envs, ws, bs)
+        self._mlp32._remember(source_pairs(source))
         for group in _by_library(envs):
             if self.precision == "bf16" or group[0].lib.path in self._bf16:
                 self._pack_bf16(group)
         return mode
+
+    def apply(self, env: SigmaEnv, x: torch.Tensor | None = None, *, rows=None) -> torch.Tensor:
+        """The fp32 network's four outputs per row with a ``grad_fn`` (``Mlp32.apply``: same arguments, stale-weight guard and stream order).  The distribution head
+        -- log-probability of the recorded action, ratio, clip, entropy -- stays in torch on top of it."""
+        return self._mlp32.apply(env, x, rows=rows)
 
     def close(self):
         for lib, h in getattr(self, "_bf16", {}).values():

@@ -2623,6 +2623,7 @@ extern "C" int sigmaenv_trig_selftest(sigmaenv_t* h, int32_t kind, int32_t n, co
 #include "sigmaenv_actor.inc"
 #include "sigmaenv_mlp32.inc"
 #include "sigmaenv_load.inc"
+#include "sigmaenv_grad.inc"
 #include "sigmaenv_wrappers.inc"
 #include "sigmaenv_learn.inc"
 #include "sigmaenv_cbf.inc"

@@ -69,6 +69,15 @@ SIGMA_HD int load_exact_src(int F, int K, int d) {
   const int f = 32 * ft + mm, k = 8 * kq + 2 * u + hh;
   return f < F && k < K ? f * K + k : -1;
 }
+// the exact form of the TRANSPOSED weight (sigmaenv_grad.inc: delta W contracts over the features): [Kp / 32][FQ][2][32][4], Fp = F padded to 8, Kp = K padded to 32;
+// slot ((((kt FQ + fq) 2 + hh) 32 + mm) 4 + u holds weight (feature f = 8 fq + 2 u + hh, k = 32 kt + mm) -- load_exact_src with the two indices' roles exchanged
+SIGMA_HD int load_exact_t_slots(int F, int K) { return ((F + 7) / 8 * 8) * ((K + 31) / 32 * 32); }
+SIGMA_HD int load_exact_t_src(int F, int K, int d) {
+  const int FQ = (F + 7) / 8;
+  const int u = d & 3, mm = (d >> 2) & 31, hh = (d >> 7) & 1, q = d >> 8, kt = q / FQ, fq = q - kt * FQ;
+  const int k = 32 * kt + mm, f = 8 * fq + 2 * u + hh;
+  return f < F && k < K ? f * K + k : -1;
+}
 // split form: (hi, lo) PAIRS.  Pair p = ((tile KB + kb) 64 + lane) 8 + j8 (output layer: tile = 0) has its hi half at 16-bit slot load_split_hi_slot(p), its lo half
 // 512 slots (64 fragments) further; feature 32 tile + (lane & 31), k slot (kb, hh = lane >> 5, j8) -> input feature as mlp32s_feature_of_slot
 SIGMA_HD int load_split_rows(int F, bool output_layer) { return output_layer ? 32 : (F + 63) / 64 * 64; }
@@ -160,6 +169,8 @@ static inline int grid_for(int total) { return (total + 255) / 256 < 1024 ? (tot
 
 }  // namespace load
 
+static int mlp32_grad_load(sigmaenv_t* h, sigmaenv_mlp32* m, const float* const* weights_dev);  // sigmaenv_grad.inc: the transposed forms, same stream
+
 extern "C" int sigmaenv_mlp32_load_device(sigmaenv_t* h, sigmaenv_mlp32* m, const float* const* weights_dev, const float* const* biases_dev) {
   if (!h) return SIGMAENV_EINVAL;
   if (!m || !m->range_word) { h->err = "mlp32_load_device: null network handle"; return SIGMAENV_EINVAL; }
@@ -184,6 +195,7 @@ extern "C" int sigmaenv_mlp32_load_device(sigmaenv_t* h, sigmaenv_mlp32* m, cons
     hipLaunchKernelGGL(load::sigmaenv_load_mlp32_kernel, dim3(load::grid_for(a.n_exact + a.n_pairs + a.fp_exact + a.fp_split)), dim3(256), 0, h->stream, a);
     HIPCHK(h, hipGetLastError());
   }
+  if (const int rc = mlp32_grad_load(h, m, weights_dev)) return rc;
   // the one host wait: the range word decides which form the next forward launches
   uint32_t bad = 0;
   HIPCHK(h, hipMemcpyAsync(&bad, m->range_word, 4, hipMemcpyDeviceToHost, h->stream));

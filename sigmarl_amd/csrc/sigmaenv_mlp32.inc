@@ -137,8 +137,11 @@ __device__ __forceinline__ void mlp32_tile_k256(const float4* __restrict__ wa, c
 // record (Mlp32Rows, sigmaenv_mlp32_forward_rows).  Only the row addresses and loads of stage() differ.  Two instantiations of the KERNEL, not one body inlined
 // into two kernels: the dense one then compiles to what it was before the strided one existed (236 VGPRs, no scratch; as an inlined body it took 256 VGPRs and
 // 128 bytes of scratch per lane -- tools/kernel_resources.sh)
-template <bool ROWS>
-__global__ void __launch_bounds__(256, 2) sigmaenv_mlp32_kernel(Mlp32Weights mw, const float* __restrict__ in, int R, int in_dim, float* __restrict__ out, Mlp32Rows rw MLP32_TS_ARG) {
+// SAVE (sigmaenv_mlp32_forward_save, sigmaenv_grad.inc): a third instantiation that also writes every hidden layer's post-tanh tile -- the registers the LDS store
+// below takes -- to acts [n_layers - 1][R][256]; the other two never read `acts` and compile to what they were (profiles/learn_kernel_resources.txt).
+template <bool ROWS, bool SAVE = false>
+__global__ void __launch_bounds__(256, 2) sigmaenv_mlp32_kernel(Mlp32Weights mw, const float* __restrict__ in, int R, int in_dim, float* __restrict__ out, Mlp32Rows rw,
+                                                                float* __restrict__ acts MLP32_TS_ARG) {
   sigma_poison_lds();
   MLP32_TS(0);
 #ifdef SIGMAENV_PROFILE
@@ -287,6 +290,11 @@ __global__ void __launch_bounds__(256, 2) sigmaenv_mlp32_kernel(Mlp32Weights mw,
             float* d = x + ((((size_t)kq2 * 2) * MLP32_ROWS + row) << 2) + 2 * h;  // k parity 0; parity 1 is 64 fragments further
             *reinterpret_cast<float2*>(d) = make_float2(acc[ft][rt][4 * q + 0], acc[ft][rt][4 * q + 2]);
             *reinterpret_cast<float2*>(d + MLP32_ROWS * 4) = make_float2(acc[ft][rt][4 * q + 1], acc[ft][rt][4 * q + 3]);
+            if constexpr (SAVE) {  // the same four features, consecutive in the saved row (64-bit row offsets: 2 M rows x 1 KB)
+              if (row0 + row < R)
+                *reinterpret_cast<float4*>(acts + ((size_t)l * (size_t)R + (size_t)(row0 + row)) * MLP32_H + (size_t)(kq2 * 8 + 4 * h)) =
+                    make_float4(acc[ft][rt][4 * q + 0], acc[ft][rt][4 * q + 1], acc[ft][rt][4 * q + 2], acc[ft][rt][4 * q + 3]);
+            }
           }
       __syncthreads();
       MLP32_TS(4 + 3 * l);
@@ -362,6 +370,7 @@ __global__ void sigmaenv_actor_head_kernel(const float* __restrict__ out4, int R
 struct sigmaenv_mlp32 {
   Mlp32Weights w{};
   Mlp32sWeights ws{};   // the split-fp16 form of the same network (sigmaenv_mlp32s.inc)
+  float* wt[MLP32_MAX_LAYERS] = {};  // the exact form of the TRANSPOSED weights of layers 1 .. n_layers - 1, for the backward pass (sigmaenv_grad.inc)
   int mode = SIGMAENV_MLP32_SPLIT;       // the mode in force
   int requested = SIGMAENV_MLP32_SPLIT;  // the mode asked for (sigmaenv_mlp32_set_mode): in force again when sigmaenv_mlp32_load_device brings the weights back into range
   bool split_ok = true;    // the split form may run: every weight inside its range and split_fits
@@ -375,6 +384,8 @@ struct sigmaenv_mlp32 {
   unsigned long long* ts = nullptr;  // profile build: [workgroups][16] shader-clock stamps of the last forward
   int ts_groups = 0;
 };
+
+static int mlp32_grad_create(sigmaenv_mlp32* m, const float* const* weights);  // sigmaenv_grad.inc: allocates and fills wt
 
 extern "C" void sigmaenv_mlp32_destroy(sigmaenv_mlp32* m) {
   if (!m) return;
@@ -450,6 +461,7 @@ extern "C" int sigmaenv_mlp32_create(int32_t n_layers, const int32_t* dims, cons
   m->smem_s = (size_t)(m->ws.KB[0] > 16 ? m->ws.KB[0] : 16) * 256 * 16 + (2 * 16 * 64 + (MLP32_MAX_LAYERS - 1) * MLP32_H + 32) * sizeof(float);
   m->split_fits = m->smem_s <= 160 * 1024;
   if (!m->split_ok || !m->split_fits) { m->split_ok = false; m->mode = SIGMAENV_MLP32_EXACT; }
+  if (const int rc = mlp32_grad_create(m, weights)) { sigmaenv_mlp32_destroy(m); return rc; }
   *out = m;
   return SIGMAENV_OK;
 }
@@ -553,11 +565,11 @@ static int mlp32_forward_impl(sigmaenv_t* h, sigmaenv_mlp32* m, const float* in,
     HIPCHK(h, hipFuncSetAttribute(kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem_l));
   }
   const int stagger_l = getenv("SIGMAENV_MLP32_STAGGER") ? atoi(getenv("SIGMAENV_MLP32_STAGGER")) : 0;
-  if (rw) hipLaunchKernelGGL(sigmaenv_mlp32_kernel<true>, dim3((rows + MLP32_ROWS - 1) / MLP32_ROWS), dim3(256), smem_l, h->stream, m->w, in, (int)rows, m->in_dim, out, *rw, m->ts, stagger_l);
-  else hipLaunchKernelGGL(sigmaenv_mlp32_kernel<false>, dim3((rows + MLP32_ROWS - 1) / MLP32_ROWS), dim3(256), smem_l, h->stream, m->w, in, (int)rows, m->in_dim, out, Mlp32Rows{}, m->ts, stagger_l);
+  if (rw) hipLaunchKernelGGL(sigmaenv_mlp32_kernel<true>, dim3((rows + MLP32_ROWS - 1) / MLP32_ROWS), dim3(256), smem_l, h->stream, m->w, in, (int)rows, m->in_dim, out, *rw, (float*)nullptr, m->ts, stagger_l);
+  else hipLaunchKernelGGL(sigmaenv_mlp32_kernel<false>, dim3((rows + MLP32_ROWS - 1) / MLP32_ROWS), dim3(256), smem_l, h->stream, m->w, in, (int)rows, m->in_dim, out, Mlp32Rows{}, (float*)nullptr, m->ts, stagger_l);
 #else
-  if (rw) hipLaunchKernelGGL(sigmaenv_mlp32_kernel<true>, dim3((rows + MLP32_ROWS - 1) / MLP32_ROWS), dim3(256), m->smem, h->stream, m->w, in, (int)rows, m->in_dim, out, *rw);
-  else hipLaunchKernelGGL(sigmaenv_mlp32_kernel<false>, dim3((rows + MLP32_ROWS - 1) / MLP32_ROWS), dim3(256), m->smem, h->stream, m->w, in, (int)rows, m->in_dim, out, Mlp32Rows{});
+  if (rw) hipLaunchKernelGGL(sigmaenv_mlp32_kernel<true>, dim3((rows + MLP32_ROWS - 1) / MLP32_ROWS), dim3(256), m->smem, h->stream, m->w, in, (int)rows, m->in_dim, out, *rw, (float*)nullptr);
+  else hipLaunchKernelGGL(sigmaenv_mlp32_kernel<false>, dim3((rows + MLP32_ROWS - 1) / MLP32_ROWS), dim3(256), m->smem, h->stream, m->w, in, (int)rows, m->in_dim, out, Mlp32Rows{}, (float*)nullptr);
 #endif
   HIPCHK(h, hipGetLastError());
   timer_end(h, SIGMAENV_KERNEL_MLP32, slot);

@@ -1,0 +1,250 @@
+"""The backward pass's yardstick (tests/gradient_check.py) on the host: a numpy float32 twin of sigmaenv_grad.inc -- the same formulas, the same tile- and
+range-ordered sums, every product rounded separately -- passes both layers of the criterion, the planted defects fail it; the row partition is what the header
+states; the transposed packed form of the weights (load_exact_t_src) is held word for word across its packers.  No GPU needed."""
+import copy
+import os
+import shutil
+import subprocess
+
+import numpy as np
+import pytest
+import torch
+
+import gradient_check as gc
+from sigmarl_amd import capi
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "sigmarl_amd", "csrc")
+F32 = np.float32
+
+DIMS = [35, 256, 256, 4]  # K padded (35 -> 40), a square layer, an output layer padded 4 -> 8
+ROWS = 838                # len = 256: three full ranges and a short one of 70 rows, whose last row tile has 6 rows
+
+
+def make_net(dims, seed):
+    torch.manual_seed(seed)
+    layers = []
+    for l in range(len(dims) - 1):
+        layers += [torch.nn.Linear(dims[l], dims[l + 1])] + ([torch.nn.Tanh()] if l + 2 < len(dims) else [])
+    return torch.nn.Sequential(*layers)
+
+
+def forward_twin(mlp, x):
+    """(y, acts) in float32: what the saving forward writes, up to the summation order."""
+    lin = gc.linears(mlp)
+    a, acts = x, []
+    for i, m in enumerate(lin):
+        z = (a @ m.weight.detach().numpy().T + m.bias.detach().numpy()).astype(F32)
+        if i + 1 < len(lin):
+            a = np.tanh(z).astype(F32)
+            acts.append(a)
+    return z, np.stack(acts)
+
+
+def backward_twin(weights, x, acts, dout, defect=None):
+    """sigmaenv_grad.inc in numpy float32.  g_{l-1}: one chain over f = 0, 1, .. per element (product rounded, then added), times fl(1 - a^2) rounded once, rounded
+    product.  dW: per range of ``partition`` one chain over the rows, partials added in range order.  db: even-row and odd-row chains per range.  ``defect``: one of
+    the planted faults of DEFECTS."""
+    n, rows = len(weights), x.shape[0]
+    a = [x.astype(F32)] + [acts[l] for l in range(n - 1)]
+    g = [None] * n
+    g[n - 1] = dout.astype(F32).reshape(rows, -1)
+    for l in range(n - 1, 0, -1):
+        Wl = weights[l].T if (defect == "untransposed" and weights[l].shape[0] == weights[l].shape[1]) else weights[l]
+        acc = np.zeros((rows, weights[l].shape[1]), F32)
+        for f in range(weights[l].shape[0]):
+            acc = acc + g[l][:, f:f + 1] * Wl[f:f + 1, :]
+        if defect == "pad_column" and l == n - 1:  # a padded feature column of the contraction (4 -> 8) carrying a value: one more, spurious, term
+            rng = np.random.default_rng(5)
+            acc = acc + (np.abs(g[l]).max(1, keepdims=True) * F32(2e-3)) * rng.standard_normal((1, acc.shape[1])).astype(F32) * np.abs(Wl).max()
+        v = (1.0 - a[l].astype(np.float64) ** 2).astype(F32)  # fma(-a, a, 1): one rounding
+        g[l - 1] = acc if (defect == "no_dtanh" and l == 1) else acc * v
+        if defect == "drop_tile":
+            g[l - 1][rows // 64 * 64:] = 0
+    length, nr = gc.partition(rows)
+    dW, db = [], []
+    for l in range(n):
+        gl = g[l].copy()
+        if defect == "drop_tile":
+            gl[rows // 64 * 64:] = 0
+        if defect == "row63":
+            gl[100] = 0  # one row of the second tile is never added
+        pw, pb = [], []
+        for r in range(nr):
+            lo, hi = r * length, min(rows, (r + 1) * length)
+            acc = np.zeros((gl.shape[1], a[l].shape[1]), F32)
+            for row in range(lo, hi):
+                acc = acc + gl[row][:, None] * a[l][row][None, :]
+            pw.append(acc)
+            gb = g[l] if defect == "row63" else gl  # (row63 is a fault of the dW chain alone)
+            if defect == "db_one_tile":
+                hi = min(hi, lo + 64) if r == 0 else lo
+            even, odd = np.zeros(gl.shape[1], F32), np.zeros(gl.shape[1], F32)
+            for row in range(lo, hi):
+                if (row - lo) % 2 == 0:
+                    even = even + gb[row]
+                else:
+                    odd = odd + gb[row]
+            pb.append(even + odd)
+        if defect == "missing_partial" and l == 1:
+            del pw[2]
+        sw, sb = np.zeros_like(pw[0]) if not pw else pw[0], np.zeros(gl.shape[1], F32) if not pb else pb[0]
+        for t in pw[1:]:
+            sw = sw + t
+        for t in pb[1:]:
+            sb = sb + t
+        dW.append(sw)
+        db.append(sb)
+    return dW, db, g[:-1]
+
+
+DEFECTS = ["drop_tile", "row63", "no_dtanh", "untransposed", "db_one_tile", "pad_column", "missing_partial"]
+
+
+@pytest.fixture(scope="module")
+def case():
+    mlp = make_net(DIMS, 3)
+    rng = np.random.default_rng(7)
+    x = ((rng.random((ROWS, DIMS[0])) * 2 - 1) * 1.5).astype(F32)
+    x[7] = 0.0
+    y, acts = forward_twin(mlp, x)
+    dout = (rng.standard_normal((ROWS, DIMS[-1])) / ROWS).astype(F32)  # the scale of a mean loss
+    dout[11] = 0.0
+    refs = gc.references(mlp, x, dout)
+    return mlp, gc.weights_of(mlp), x, acts, dout, refs
+
+
+def both_layers(case, defect):
+    mlp, weights, x, acts, dout, refs = case
+    dW, db, g = backward_twin(weights, x, acts, dout, defect)
+    l1 = gc.measure_backward(weights, x, acts, dout, dW, db, g)
+    l2 = gc.measure_end_to_end([t for q in zip(dW, db) for t in q], *refs)
+    return l1, l2
+
+
+def test_the_partition_is_the_stated_function_of_rows():
+    assert gc.partition(0) == (256, 0) and gc.partition(1) == (256, 1) and gc.partition(256) == (256, 1) and gc.partition(257) == (256, 2)
+    assert gc.partition(ROWS) == (256, 4) and ROWS - 3 * 256 == 70
+    assert gc.partition(64 * 256) == (256, 64) and gc.partition(64 * 256 + 1) == (320, 52)
+    assert gc.partition(32 * 4096 * 16) == (32768, 64)
+    for rows in (1, 63, 64, 65, 130, 200, 838, 16385, 2 ** 21, 2 ** 31 - 1):
+        length, n = gc.partition(rows)
+        assert length % 64 == 0 and length >= 256 and 1 <= n <= 64 and (n - 1) * length < rows <= n * length
+    src = open(os.path.join(CSRC, "sigmaenv_grad.inc")).read()
+    assert "#define GRAD_MIN_RANGE 256" in src and "#define GRAD_MAX_RANGES 64" in src
+
+
+def test_the_float32_twin_passes_both_layers(case):
+    mlp, weights, x, acts, dout, refs = case
+    gc.check_acts(acts, mlp, x, what="twin")
+    l1, l2 = both_layers(case, None)
+    print(l1["ratios"], l2["ratios"])
+    assert l1["ok"], l1["ratios"]
+    assert l2["ok"], l2["ratios"]
+    # the float64 restatement of the formulas is what torch's autograd computes (on the float64 module's own activations)
+    m64 = copy.deepcopy(mlp).double()
+    h, acts64 = torch.from_numpy(x).double(), []
+    with torch.no_grad():
+        for q in gc.linears(m64)[:-1]:
+            h = torch.tanh(q(h))
+            acts64.append(h.numpy())
+    b = gc.backward64([q.weight.detach().numpy() for q in gc.linears(m64)], x, acts64, dout)
+    for l in range(len(weights)):
+        for got, ref, scale in ((b["dW"][l], refs[0][2 * l], refs[2][2 * l]), (b["db"][l], refs[0][2 * l + 1], refs[2][2 * l + 1])):
+            assert np.abs(got - ref).max() <= 1e-12 * scale
+
+
+@pytest.mark.parametrize("defect", DEFECTS)
+def test_planted_defects_fail(case, defect):
+    l1, l2 = both_layers(case, defect)
+    print(defect, l1["ratios"], l2["ratios"])
+    assert not l1["ok"], f"{defect} passes the backward-given-the-activations bound: {l1['ratios']}"
+
+
+def test_zero_rows_and_zero_dout_rows():
+    mlp = make_net([7, 256, 1], 2)
+    w = gc.weights_of(mlp)
+    b = gc.backward64(w, np.zeros((0, 7), F32), np.zeros((1, 0, 256), F32), np.zeros((0, 1), F32))
+    assert all((t == 0).all() for t in b["dW"] + b["db"] + b["bound_dW"] + b["bound_db"])
+    assert gc.worst_ratio(np.zeros((256, 7)), b["dW"][0], b["bound_dW"][0]) == 0.0
+    assert gc.worst_ratio(np.full((256, 7), 1e-30), b["dW"][0], b["bound_dW"][0]) == float("inf")
+    rng = np.random.default_rng(1)
+    x = rng.standard_normal((5, 7)).astype(F32)
+    _, acts = forward_twin(mlp, x)
+    dout = rng.standard_normal((5, 1)).astype(F32)
+    dout[2] = 0
+    b = gc.backward64(w, x, acts, dout)
+    assert (b["g"][0][2] == 0).all() and (b["bound_g"][0][2] == 0).all()
+
+
+def test_grad_entry_points_are_declared_and_bound():
+    header = open(os.path.join(ROOT, "include", "sigmaenv.h")).read()
+    for name in ("mlp32_forward_save", "mlp32_backward_workspace", "mlp32_backward"):
+        assert "sigmaenv_" + name in capi.exported_symbols() and name in capi._PRODUCT_ONLY
+        assert f"int sigmaenv_{name}(" in header
+    mk = open(os.path.join(CSRC, "Makefile")).read()
+    assert "sigmaenv_grad.inc" in [ln for ln in mk.splitlines() if ln.startswith("SRC = ")][0].split()  # sigmaenv_build_id() covers the kernels
+    assert '#include "sigmaenv_grad.inc"' in open(os.path.join(CSRC, "sigmaenv.hip")).read()
+
+
+MAIN = r"""
+static long bad = 0;
+static void same(const char* what, int F, int K, const std::vector<float>& a, const std::vector<float>& b) {
+  if (a.size() != b.size()) { printf("SIZE %s F=%d K=%d: %zu against %zu\n", what, F, K, a.size(), b.size()); ++bad; return; }
+  for (size_t i = 0; i < a.size(); ++i)
+    if (std::memcmp(&a[i], &b[i], 4) != 0 && ++bad <= 20) printf("MISMATCH %s F=%d K=%d slot %zu\n", what, F, K, i);
+}
+int main() {
+  const int Fs[] = {256, 32, 9, 8, 7, 4, 2, 1}, Ks[] = {256, 35, 32, 7};
+  long slots = 0;
+  uint32_t x = 12345u;
+  for (int F : Fs)
+    for (int K : Ks) {
+      std::vector<float> w((size_t)F * K), wT((size_t)F * K);
+      for (auto& v : w) { x = x * 1664525u + 1013904223u; v = (float)(x >> 8) / 8388608.0f - 1.0f; }
+      w[0] = -0.0f; w[w.size() - 1] = 1e-40f; w[w.size() / 2] = NAN;
+      for (int f = 0; f < F; ++f) for (int k = 0; k < K; ++k) wT[(size_t)k * F + f] = w[(size_t)f * K + k];
+      /* 1: the host packer of sigmaenv_mlp32_create (its text, from sigmaenv_grad.inc) */
+      const std::vector<float> a = mlp32_pack_transposed(w.data(), F, K);
+      /* 2: the loop of the device pack kernel, one destination slot at a time */
+      std::vector<float> b((size_t)load_exact_t_slots(F, K), 7.0f);
+      std::vector<int> seen((size_t)F * K, 0);
+      for (int d = 0; d < (int)b.size(); ++d) { const int s = load_exact_t_src(F, K, d); if (s >= (int)seen.size()) { ++bad; continue; } b[d] = s >= 0 ? w[s] : 0.0f; if (s >= 0) ++seen[s]; }
+      for (int c : seen) if (c != 1) { if (++bad <= 20) printf("COVER F=%d K=%d: a weight packed %d times\n", F, K, c); }
+      /* 3: the forward's exact form (load_exact_src, held to sigmaenv_mlp32_create's loop by tests/test_weight_load_host.py) of the transposed matrix [K][F] */
+      std::vector<float> c((size_t)load_exact_slots(K, F));
+      for (int d = 0; d < (int)c.size(); ++d) { const int s = load_exact_src(K, F, d); c[d] = s >= 0 ? wT[s] : 0.0f; }
+      same("create-vs-kernel", F, K, a, b);
+      same("transposed-vs-exact-of-transpose", F, K, a, c);
+      slots += (long)a.size();
+    }
+  printf("%ld slots compared: %ld mismatches\n", slots, bad);
+  return bad ? 1 : 0;
+}
+"""
+
+
+@pytest.mark.skipif(shutil.which("g++") is None and shutil.which("c++") is None, reason="no host C++ compiler")
+def test_transposed_form_packers_agree_word_for_word(tmp_path):
+    """F in {256, 32, 9, 8, 7, 4, 2, 1} x K in {256, 35, 32, 7}: the host packer of sigmaenv_mlp32_create (text taken from sigmaenv_grad.inc), the loop of the device
+    pack kernel over load_exact_t_src, and the forward's exact form of the transposed matrix give the same words in every slot, padding (zeros) included; every
+    weight lands in exactly one slot.  -0, a subnormal and a NaN are planted (words are compared)."""
+    grad = open(os.path.join(CSRC, "sigmaenv_grad.inc")).read()
+    a = grad.index("static std::vector<float> mlp32_pack_transposed(")
+    packer = grad[a:grad.index("\n}\n", a) + 3]
+    assert "load_exact_t_src" in packer and "hip" not in packer
+    kernel = grad[grad.index("sigmaenv_load_mlp32_t_kernel("):]
+    assert "const int s = load_exact_t_src(F, K, i);" in kernel and "tw[i] = s >= 0 ? w[s] : 0.0f;" in kernel  # (the loop restated in MAIN)
+    src = tmp_path / "t_check.cpp"
+    src.write_text("#include <cmath>\n#include <cstdint>\n#include <cstdio>\n#include <cstring>\n#include <vector>\n#define MLP32S_SW 256.0f\n"
+                   "#define SIGMA_HD static inline\n#define SIGMAENV_LOAD_MAPS_ONLY\n#include \"sigmaenv_load.inc\"\n" + packer + MAIN)
+    cxx = shutil.which("g++") or shutil.which("c++")
+    exe = tmp_path / "t_check"
+    base = [cxx, "-std=c++17", "-O1", "-I", CSRC, str(src), "-o", str(exe)]
+    san = subprocess.run(base + ["-fsanitize=address,undefined", "-fno-sanitize-recover=all"], capture_output=True, text=True)
+    if san.returncode != 0:
+        subprocess.check_call(base)
+    run = subprocess.run([str(exe)], capture_output=True, text=True)
+    print(run.stdout[-3000:], run.stderr[-3000:])
+    assert run.returncode == 0, run.stdout[-2000:] + run.stderr[-2000:]
+    assert ": 0 mismatches" in run.stdout
