@@ -458,6 +458,21 @@ int sigmaenv_mlp32_forward_save(sigmaenv_t* h, sigmaenv_mlp32_t* m, const float*
 int sigmaenv_mlp32_backward_workspace(const sigmaenv_mlp32_t* m, int64_t rows, uint64_t* n_floats);
 int sigmaenv_mlp32_backward(sigmaenv_t* h, sigmaenv_mlp32_t* m, const float* in, int32_t rows_per_block, int64_t row_stride, int32_t n_blocks, int64_t block_stride,
                             const float* acts, const float* dout, float* workspace, float* const* grad_w, float* const* grad_b);
+/* The same two on a MINIBATCH OF BLOCKS picked by index (a minibatch of frames, sigmarl/mappo_cavs.py:321-340: SamplerWithoutReplacement, or the prioritized buffer,
+ * which samples with replacement): index is a device i32 [n_index]; block t of the network's rows is block index[t] of the record, i.e. row r = t * rows_per_block + b
+ * lies at in + index[t] * block_stride + b * row_stride.  n_blocks is the record's block count, the bound on the entries; rows = rows_per_block * n_index.  out, acts,
+ * dout and the workspace stay dense, in minibatch order; sigmaenv_mlp32_backward_workspace(rows) sizes the workspace.  For the actor a frame is a block of N rows
+ * of width D (block_stride = N D), for the critic one row of width N D.  Duplicates in index are legal.  An entry outside [0, n_blocks) is never used as an address:
+ * its rows are staged as zeros, exactly like rows beyond the last one (a caller that wants an error checks the range itself, as the Python layer does).
+ * Same arithmetic, same summation order and partition as above -- functions of rows and the layer shapes alone, no atomics --, so the results are bit for bit those
+ * of the non-indexed call on the same rows gathered dense, and with index = 0, 1, .. those of the non-indexed call on the record.  block_stride >= 0 is required;
+ * n_index = 0 is the rows = 0 case.  The index entry is loaded once per row, not per element (forward: by the first 64 lanes of the tile into LDS; dW_0: one load
+ * per lane and row). */
+int sigmaenv_mlp32_forward_save_indexed(sigmaenv_t* h, sigmaenv_mlp32_t* m, const float* in, int32_t rows_per_block, int64_t row_stride, int32_t n_blocks,
+                                        int64_t block_stride, const int32_t* index, int32_t n_index, float* out, float* acts);
+int sigmaenv_mlp32_backward_indexed(sigmaenv_t* h, sigmaenv_mlp32_t* m, const float* in, int32_t rows_per_block, int64_t row_stride, int32_t n_blocks,
+                                    int64_t block_stride, const int32_t* index, int32_t n_index, const float* acts, const float* dout, float* workspace,
+                                    float* const* grad_w, float* const* grad_b);
 
 /* n_steps x (sigmaenv_actor_forward; sigmaenv_step_autoreset) enqueued back to back (SyncDataCollectorCustom.rollout,
  * sigmarl/helper_training.py:687-788, without its per-step Python): actions_buf device f32 [B,N,2] scratch; optional records:
@@ -555,6 +570,60 @@ typedef struct sigmaenv_gae_args {
   int32_t reserved[5];             /* zero */
 } sigmaenv_gae_args_t;
 int sigmaenv_gae(sigmaenv_t* h, const sigmaenv_gae_args_t* a);
+
+/* ---- the clip-PPO loss head of a minibatch update (sigmaenv_ppo.inc) ---------------------------------------------------------------------
+ * sigmaenv_ppo_head: torchrl's ClipPPOLoss as sigmarl/modules/optimization_module.py:44-66 configures it (clip_epsilon, entropy_coeff = entropy_eps,
+ * normalize_advantage = False, the default smooth-L1 critic loss, samples_mc_entropy = 1) for one minibatch of frames (sigmarl/mappo_cavs.py:389-407, _train_epoch /
+ * _train_on_batch): from the networks' outputs of the minibatch and the learner's records, read through index, to the three loss terms and the gradients of their
+ * sum with respect to those outputs -- the dout of sigmaenv_mlp32_backward_indexed.  torchrl is third-party and absent: the formulas below are the specification
+ * (restated from its published behaviour, as actor_distribution is).  N = the handle's agents, M = n_index, F = n_frames; slot m, frame f = index[m], agent n,
+ * action dimension d in {0, 1}, o = out[m, n, 0:4]:
+ *   parameters     loc_d = o[d];  sigma_d = max(softplus(o[2 + d] + ln(e^0.99 - 1)) + 0.01, 1e-4);  h_d = (high_d - low_d) / 2      (actor_distribution's)
+ *   log-probability of the recorded action a = action[f, n]   (the replay buffer has dropped the distribution's cache: the inverse transform)
+ *                  y_d = clamp((a_d - low_d) / h_d - 1, +-(1 - 1e-6));   x_d = atanh(y_d) = 0.5 (log1p(y_d) - log1p(-y_d));
+ *                  logp = sum_d [ -(x_d - loc_d)^2 / (2 sigma_d^2) - log sigma_d - log sqrt(2 pi) - 2 (log 2 - x_d - softplus(-2 x_d)) - log h_d ]
+ *   objective      lw = logp - sample_log_prob[f, n];  A = advantage[f, n];  g1 = exp(lw) A;  g2 = exp(clamp(lw, log1p(-eps), log1p(eps))) A;
+ *                  loss_objective = -mean_{m, n} min(g1, g2);  on a tie the unclamped branch carries the gradient
+ *   entropy bonus  TanhNormal has no closed-form entropy: one reparameterised sample.  (z_0, z_1) by Box-Muller (z_0 the cosine branch) from the generator keyed
+ *                  (seed, counter, env = f, agent = n), draws 7300 and 7301 (beside 7000 / 7001, 7100 / 7101, 7200);  x'_d = loc_d + sigma_d z_d;
+ *                  logp' = sum_d [ -z_d^2 / 2 - log sigma_d - log sqrt(2 pi) - 2 (log 2 - x'_d - softplus(-2 x'_d)) - log h_d ]   (never clamped);
+ *                  entropy = -mean logp';  loss_entropy = -entropy_coeff entropy;  the gradient flows through x' into loc and sigma
+ *   critic         v = value[m] (the centralised critic's one value per frame is every agent's);  e = v - value_target[f, n];
+ *                  smooth-L1, beta = 1: 0.5 e^2 if |e| < 1 else |e| - 0.5;  loss_critic = critic_coeff mean_{m, n}
+ *   outputs        dout_actor[m, n, 0:4] = d(loss_objective + loss_entropy) / d o, with d sigma / d raw = sigmoid(raw + ln(e^0.99 - 1)), 0 where the 1e-4 floor acts;
+ *                  dout_critic[m] = sum_n d loss_critic / d v;
+ *                  result[0 .. 5] = loss_objective, loss_entropy, loss_critic, entropy, clip_fraction = mean[clamp(lw) != lw], kl_approx = mean(-lw); [6], [7] = 0
+ * Tensors (device f32 unless said): index i32 [M]; out [M, N, 4] and dout_actor [M, N, 4], 16-byte aligned; value, dout_critic [M]; action [F, N, 2], 8-byte
+ * aligned; sample_log_prob, advantage, value_target [F, N]; result [8]; workspace [SIGMAENV_PPO_SUMS * ceil(M N / 256)].  The records are read in place; duplicates
+ * in index are legal; an entry outside [0, F) is never used as an address (its rows give zero gradients and add zeros to the sums -- the means still divide by M N).
+ * Arithmetic: fp32, one IEEE operation per operator, no contraction, denormals kept; log1p(+-eps), 1 / (M N), entropy_coeff / (M N) and critic_coeff / (M N) are
+ * rounded once, on the host.  Summation order: one lane per (m, n) row r = m N + n, workgroups of 256 rows.  dout_critic[m]: the chain over n = 0, 1, .. from 0.
+ * Each mean: per wavefront of 64 consecutive rows the butterfly v += v[lane ^ s], s = 32, 16, .., 1; per workgroup ((w0 + w1) + w2) + w3 over its wavefronts;
+ * then one wavefront: lane k the chain over the workgroups k, k + 64, .. from 0, and the same butterfly.  A function of (M, N) alone, no atomics: the same inputs
+ * give the same bits on every run.  Two launches on the handle's stream; nothing waits.
+ * M < 1, F < 1, a null or misaligned tensor, clip_epsilon outside (0, 1), high <= low: SIGMAENV_EINVAL with sigmaenv_last_error set, before any launch. */
+#define SIGMAENV_PPO_SUMS 5
+typedef struct sigmaenv_ppo_head_args {
+  int32_t n_index;                 /* M */
+  int32_t n_frames;                /* F */
+  const int32_t* index;
+  const float* out;
+  const float* value;
+  const float* action;
+  const float* sample_log_prob;
+  const float* advantage;
+  const float* value_target;
+  float* dout_actor;
+  float* dout_critic;
+  float* result;
+  float* workspace;
+  float low[2], high[2];
+  float clip_epsilon, entropy_coeff, critic_coeff;
+  int32_t reserved0;               /* zero */
+  uint64_t seed, counter;
+  int32_t reserved[4];             /* zero */
+} sigmaenv_ppo_head_args_t;
+int sigmaenv_ppo_head(sigmaenv_t* h, const sigmaenv_ppo_head_args_t* a);
 
 /* The priority module (sigmarl/modules/priority_module.py).  sigmaenv_priority_forward: priority_net (MultiAgentMLP depth 2: obs_dim -> 256 -> 256 -> 2, Tanh,
  * :34-51) on `obs` (device f32 [B * N, obs_dim], or NULL for SIGMAENV_BUF_OBS), NormalParamExtractor ("biased_softplus_1.0", as the actor's) and a 1-D

@@ -15,6 +15,8 @@ rollout's records where they lie (``sigmaenv_mlp32_forward_rows``); ``sigmarl_am
 Weights come from any ``torch.nn.Sequential`` of four ``Linear`` layers (the parameter layout torchrl's shared-parameter MLP has).
 ``Mlp32.load`` / ``Actor.load`` put a learner's updated CUDA parameters into the existing device networks (``sigmaenv_mlp32_load_device`` /
 ``sigmaenv_actor_load_device``: packed by a kernel, no weight visits the host), so that collect -> torch update -> load -> collect stays on the device.
+``Mlp32.apply`` / ``Actor.apply`` / ``Critic.apply`` differentiate the fp32 networks on the device (``sigmaenv_mlp32_forward_save`` / ``sigmaenv_mlp32_backward``); with
+``index=`` on a minibatch of frames picked out of the records (``*_indexed``), which ``sigmarl_amd.learn`` (``ppo_head``, ``update``) trains from.
 
 The distribution heads (actor, priority actor) and ``random_ranks``: the draw of every row -- the counter-based generator keyed by (seed, the low 32 bits of
 counter, env_index_base + env, agent), Box-Muller with z0 the cosine and z1 the sine branch -- the action and the log-probability are pinned against fp64 on every
@@ -308,7 +310,21 @@ class Mlp32:
 
 
     # ---- the network differentiated (sigmaenv_mlp32_forward_save / sigmaenv_mlp32_backward) ----
-    def _rows_spec(self, x, rows):
+    def _index(self, env, index, n_blocks, check_index):
+        """The minibatch's block indices, checked before any launch: a contiguous int32 CUDA tensor ``[M]`` on the env's device (``TypeError``) whose entries --
+        unless ``check_index`` is false -- lie in ``[0, n_blocks)`` (``ValueError``; ``min`` / ``max`` on the device, one host wait)."""
+        if not (isinstance(index, torch.Tensor) and index.is_cuda and index.dtype == torch.int32 and index.dim() == 1 and index.is_contiguous()
+                and index.device == env.device):
+            raise TypeError(f"apply: index must be a contiguous int32 CUDA tensor [M] on {env.device}")
+        if check_index and index.numel():
+            lo, hi = (int(v) for v in torch.stack((index.min(), index.max())).tolist())
+            if lo < 0 or hi >= n_blocks:
+                raise ValueError(f"apply: index entries in [{lo}, {hi}] are not all inside the record's {n_blocks} blocks")
+        return index
+
+    def _rows_spec(self, x, rows, env=None, index=None, check_index=True):
+        if index is not None and rows is None:
+            raise TypeError("apply: index picks blocks of rows = (base, offset, rows_per_block, row_stride, n_blocks, block_stride)")
         if (x is None) == (rows is None):
             raise TypeError("apply: either x [rows, in_dim] or rows = (base, offset, rows_per_block, row_stride, n_blocks, block_stride)")
         if x is not None:
@@ -316,7 +332,7 @@ class Mlp32:
                 raise TypeError(f"input must be a contiguous float32 CUDA tensor [..., {self.in_dim}]")
             if x.requires_grad:
                 raise NotImplementedError("apply: the gradient with respect to the input is not built (x.requires_grad)")
-            return (x, 0, x.numel() // self.in_dim, self.in_dim, 1, 0), (*x.shape[:-1], self.out_dim)
+            return (x, 0, x.numel() // self.in_dim, self.in_dim, 1, 0, None), (*x.shape[:-1], self.out_dim)
         base, offset, rpb, rs, nb, bs = rows
         if not (isinstance(base, torch.Tensor) and base.is_cuda and base.dtype == torch.float32 and base.is_contiguous()):
             raise TypeError("the rows must lie in a contiguous float32 CUDA tensor")
@@ -327,7 +343,10 @@ class Mlp32:
             raise ValueError(f"apply: counts and offsets must be >= 0 and row_stride >= the input width {self.in_dim}")
         if rpb and nb and offset + (nb - 1) * bs + (rpb - 1) * rs + self.in_dim > base.numel():
             raise ValueError("apply: the last row ends beyond the tensor")
-        return (base, offset, rpb, rs, nb, bs), (nb, rpb, self.out_dim)
+        if index is not None:
+            index = self._index(env, index, nb, check_index)
+            return (base, offset, rpb, rs, nb, bs, index), (index.numel(), rpb, self.out_dim)
+        return (base, offset, rpb, rs, nb, bs, None), (nb, rpb, self.out_dim)
 
     def _chk_grad(self, env, rc, what):
         if rc != 0:
@@ -335,25 +354,29 @@ class Mlp32:
 
     def _forward_save(self, env, spec):
         """(y [rows, out_dim], acts [n_layers - 1, rows, 256]) on the env's stream, ordered after and before torch's current stream."""
-        base, offset, rpb, rs, nb, bs = spec
-        n, dev = rpb * nb, env.device
+        base, offset, rpb, rs, nb, bs, index = spec
+        n, dev = rpb * (nb if index is None else index.numel()), env.device
         cur = torch.cuda.current_stream(dev)
         y = torch.empty((n, self.out_dim), dtype=torch.float32, device=dev)
         acts = torch.empty((len(self._keep[1]) - 1, n, 256), dtype=torch.float32, device=dev)
         with torch.cuda.device(dev):
             h = self.handle(env.lib, env)
             env.stream.wait_stream(cur)
-            self._chk_grad(env, env.lib.mlp32_forward_save(env.h, h, C.c_void_p(base.data_ptr() + 4 * offset), rpb, rs, nb, bs, C.c_void_p(y.data_ptr()),
-                                                          C.c_void_p(acts.data_ptr())), "mlp32_forward_save")
+            src = C.c_void_p(base.data_ptr() + 4 * offset)
+            if index is None:
+                self._chk_grad(env, env.lib.mlp32_forward_save(env.h, h, src, rpb, rs, nb, bs, C.c_void_p(y.data_ptr()), C.c_void_p(acts.data_ptr())), "mlp32_forward_save")
+            else:
+                self._chk_grad(env, env.lib.mlp32_forward_save_indexed(env.h, h, src, rpb, rs, nb, bs, C.c_void_p(index.data_ptr()), index.numel(), C.c_void_p(y.data_ptr()),
+                                                                      C.c_void_p(acts.data_ptr())), "mlp32_forward_save_indexed")
             cur.wait_stream(env.stream)
-        for t in (base, y, acts):
+        for t in (base, y, acts) + (() if index is None else (index,)):
             t.record_stream(env.stream)
         return y, acts
 
     def _backward(self, env, spec, acts, dout):
         """(grad_w, grad_b) lists in ``torch.nn.Linear`` layout: ``sigmaenv_mlp32_backward`` on the env's stream, ordered as ``_forward_save``."""
-        base, offset, rpb, rs, nb, bs = spec
-        n, dev = rpb * nb, env.device
+        base, offset, rpb, rs, nb, bs, index = spec
+        n, dev = rpb * (nb if index is None else index.numel()), env.device
         dims = [int(d) for d in self._keep[0]]
         cur = torch.cuda.current_stream(dev)
         dout = dout.reshape(n, self.out_dim).to(torch.float32).contiguous()
@@ -368,18 +391,25 @@ class Mlp32:
         PA = C.c_void_p * len(gw)
         with torch.cuda.device(dev):
             env.stream.wait_stream(cur)
-            self._chk_grad(env, env.lib.mlp32_backward(env.h, h, C.c_void_p(base.data_ptr() + 4 * offset), rpb, rs, nb, bs, C.c_void_p(acts.data_ptr()),
-                                                      C.c_void_p(dout.data_ptr()), C.c_void_p(ws.data_ptr()), PA(*[t.data_ptr() for t in gw]),
-                                                      PA(*[t.data_ptr() for t in gb])), "mlp32_backward")
+            src, tail = C.c_void_p(base.data_ptr() + 4 * offset), (C.c_void_p(acts.data_ptr()), C.c_void_p(dout.data_ptr()), C.c_void_p(ws.data_ptr()),
+                                                                   PA(*[t.data_ptr() for t in gw]), PA(*[t.data_ptr() for t in gb]))
+            if index is None:
+                self._chk_grad(env, env.lib.mlp32_backward(env.h, h, src, rpb, rs, nb, bs, *tail), "mlp32_backward")
+            else:
+                self._chk_grad(env, env.lib.mlp32_backward_indexed(env.h, h, src, rpb, rs, nb, bs, C.c_void_p(index.data_ptr()), index.numel(), *tail), "mlp32_backward_indexed")
             cur.wait_stream(env.stream)
-        for t in [base, acts, dout, ws] + gw + gb:
+        for t in [base, acts, dout, ws] + gw + gb + ([] if index is None else [index]):
             t.record_stream(env.stream)
         return gw, gb
 
-    def apply(self, env: SigmaEnv, x: torch.Tensor | None = None, *, rows=None) -> torch.Tensor:
+    def apply(self, env: SigmaEnv, x: torch.Tensor | None = None, *, rows=None, index: torch.Tensor | None = None, check_index: bool = True) -> torch.Tensor:
         """The network with a ``grad_fn``: ``y = apply(env, x)`` for dense ``x [..., in_dim]`` (``y [..., out_dim]``) or ``apply(env, rows=(base, offset,
         rows_per_block, row_stride, n_blocks, block_stride))`` for rows read where they lie, as ``forward_rows`` addresses them (``y [n_blocks, rows_per_block,
-        out_dim]``) -- a minibatch of whole time slices of a rollout record.  A ``torch.autograd.Function`` whose inputs are the parameters of the module the
+        out_dim]``) -- a minibatch of whole time slices of a rollout record.  With ``index`` (a contiguous int32 CUDA tensor ``[M]``, with ``rows``): a minibatch of
+        BLOCKS, block ``m`` of the result being block ``index[m]`` of the record (``y [M, rows_per_block, out_dim]``; ``sigmaenv_mlp32_forward_save_indexed`` /
+        ``sigmaenv_mlp32_backward_indexed``) -- shuffled frames, duplicates allowed --, bit for bit what the same rows gathered dense give.  An entry outside
+        ``[0, n_blocks)`` raises ``ValueError`` before any launch (``index.min()`` / ``max()``: one host wait; ``check_index=False`` skips it, and the kernels then
+        read such a block as zeros).  A ``torch.autograd.Function`` whose inputs are the parameters of the module the
         network was built or last ``load``ed from (float32 CUDA tensors on the env's device): ``loss.backward()`` fills their ``.grad``, so ``clip_grad_norm_`` and
         ``torch.optim.Adam`` work unchanged.  The forward is the EXACT fp32 chain whatever mode the network runs in (``sigmaenv_mlp32_forward_save``); the gradient
         with respect to the input is not built (``x.requires_grad``: ``NotImplementedError``).
@@ -389,7 +419,7 @@ class Mlp32:
 
         Streams: the kernels run on the env's stream after everything torch's current stream holds, and torch's current stream then waits for them -- forwards
         and backwards alike (``load``'s discipline)."""
-        spec, shape = self._rows_spec(x, rows)
+        spec, shape = self._rows_spec(x, rows, env, index, check_index)
         for t in self._params:
             if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.device == env.device):
                 raise TypeError(f"apply: the network's parameters must be float32 CUDA tensors on {env.device}: load(env, module) with the module on the device first")
@@ -440,10 +470,13 @@ class Critic(Mlp32):
         return sv.view(T, B), nv.view(T, B)
 
 
-    def apply(self, env: SigmaEnv, record: torch.Tensor, T: int | None = None, env_first: int = 0, t_first: int = 0) -> torch.Tensor:  # noqa: D102
+    def apply(self, env: SigmaEnv, record: torch.Tensor, T: int | None = None, env_first: int = 0, t_first: int = 0, index: torch.Tensor | None = None,  # noqa: D102
+              check_index: bool = True) -> torch.Tensor:
         """``[T, B]`` state values with a ``grad_fn`` (``Mlp32.apply``) of the time slices ``[t_first, t_first + T)`` of a rollout record, read where they lie as
         ``rollout_values`` reads them: ``record`` is the root-observation record ``obs_rec [>= t_first + T, Bt, N, D]`` or the record rows ``slab [.., Bt, W]``
-        (their observation part: the next observations); ``env`` owns the envs ``[env_first, env_first + env.B)`` of the buffer."""
+        (their observation part: the next observations); ``env`` owns the envs ``[env_first, env_first + env.B)`` of the buffer.  With ``index`` (int32 CUDA ``[M]``,
+        ``Mlp32.apply``): the ``T * B`` frames ``f = t * B + b`` of those slices are blocks of one row each and the result is ``[M]``, the values of the frames
+        ``index[m]`` (the record must be the env's own: ``Bt == env.B``)."""
         B, N, D = env.B, env.N, env.D
         if self.in_dim != N * D or self.out_dim != 1:
             raise ValueError(f"the critic maps n_agents * obs_dim = {N * D} inputs to 1 value, not {self.in_dim} to {self.out_dim}")
@@ -455,6 +488,10 @@ class Critic(Mlp32):
         T, e0, t0 = int(record.shape[0] - t_first if T is None else T), int(env_first), int(t_first)
         if T < 0 or t0 < 0 or t0 + T > record.shape[0] or not 0 <= e0 <= Bt - B:
             raise ValueError(f"time slices [{t0}, {t0 + T}) / envs [{e0}, {e0 + B}) are not inside the record {list(record.shape)}")
+        if index is not None:
+            if Bt != B:
+                raise ValueError(f"apply: frames are indexed in the env's own record (Bt == B = {B}), not in a buffer of {Bt} envs")
+            return super().apply(env, rows=(record, t0 * Bt * width, 1, width, T * B, width), index=index, check_index=check_index).view(-1)
         return super().apply(env, rows=(record, (t0 * Bt + e0) * width, B, width, T, Bt * width)).view(T, B)
 
 
@@ -570,10 +607,10 @@ class Actor:
                 self._pack_bf16(group)
         return mode
 
-    def apply(self, env: SigmaEnv, x: torch.Tensor | None = None, *, rows=None) -> torch.Tensor:
-        """The fp32 network's four outputs per row with a ``grad_fn`` (``Mlp32.apply``: same arguments, stale-weight guard and stream order).  The distribution head
-        -- log-probability of the recorded action, ratio, clip, entropy -- stays in torch on top of it."""
-        return self._mlp32.apply(env, x, rows=rows)
+    def apply(self, env: SigmaEnv, x: torch.Tensor | None = None, *, rows=None, index: torch.Tensor | None = None, check_index: bool = True) -> torch.Tensor:
+        """The fp32 network's four outputs per row with a ``grad_fn`` (``Mlp32.apply``: same arguments, stale-weight guard and stream order; ``index``: a minibatch
+        of frames, blocks of ``N`` rows).  The loss head on top of it -- log-probability of the recorded action, ratio, clip, entropy -- is ``learn.ppo_head``."""
+        return self._mlp32.apply(env, x, rows=rows, index=index, check_index=check_index)
 
     def close(self):
         for lib, h in getattr(self, "_bf16", {}).values():

@@ -104,6 +104,22 @@ class GaeArgs(C.Structure):
     ]
 
 
+class PpoHeadArgs(C.Structure):
+    """``sigmaenv_ppo_head_args_t`` (sigmaenv_ppo_head): a minibatch's network outputs, the learner's records, the ``dout`` tensors and the loss terms."""
+
+    _fields_ = [
+        ("n_index", C.c_int32), ("n_frames", C.c_int32), ("index", C.c_void_p), ("out", C.c_void_p), ("value", C.c_void_p), ("action", C.c_void_p),
+        ("sample_log_prob", C.c_void_p), ("advantage", C.c_void_p), ("value_target", C.c_void_p), ("dout_actor", C.c_void_p), ("dout_critic", C.c_void_p),
+        ("result", C.c_void_p), ("workspace", C.c_void_p), ("low", C.c_float * 2), ("high", C.c_float * 2),
+        ("clip_epsilon", C.c_float), ("entropy_coeff", C.c_float), ("critic_coeff", C.c_float), ("reserved0", C.c_int32),
+        ("seed", C.c_uint64), ("counter", C.c_uint64), ("reserved", C.c_int32 * 4),
+    ]
+
+
+PPO_SUMS = 5  # SIGMAENV_PPO_SUMS: partial sums per workgroup of 256 rows in sigmaenv_ppo_head's workspace
+PPO_RESULT = ("loss_objective", "loss_entropy", "loss_critic", "entropy", "clip_fraction", "kl_approx")  # result[0 .. 5]
+
+
 class LaunchShape(C.Structure):
     """``sigmaenv_launch_shape_t`` (sigmaenv_launch_shape): the tilings the handle launches and the step kernel's instantiation."""
 
@@ -222,6 +238,10 @@ _PRODUCT_ONLY = {
     "mlp32_forward_save": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p]),
     "mlp32_backward_workspace": (C.c_int, [C.c_void_p, C.c_int64, C.POINTER(C.c_uint64)]),
     "mlp32_backward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mlp32_forward_save_indexed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
+    "mlp32_backward_indexed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                         C.c_void_p, C.c_void_p]),
+    "ppo_head": (C.c_int, [C.c_void_p, C.POINTER(PpoHeadArgs)]),
     "actor_forward_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64,
                                     C.c_int32]),
     "rollout_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64,

@@ -21,6 +21,8 @@
 //  * The partition of the rows (grad::range_len): a function of `rows` alone -- at most 64 ranges, each a multiple of 64 rows and at least 256 --, never of the
 //    device.  Every (range, block) writes its partial sums to the workspace; the sum kernel adds a slot's partials in range order.  No atomics: same bits every run.
 //  * rows = 0: only the sum kernel runs (zero partials to add: zeros).
+//  * sigmaenv_mlp32_forward_save_indexed / sigmaenv_mlp32_backward_indexed: the same kernels on a minibatch of the record's BLOCKS picked by a device index (frames of a
+//    shuffled minibatch); only the two places that read input rows differ, each by an instantiation of its own (INDEXED).  Everything above holds unchanged.
 
 namespace grad {
 
@@ -124,8 +126,11 @@ struct DwLayer {
   long long len;   // rows per range
 };
 
-template <bool INPUT>
-__global__ void __launch_bounds__(256) sigmaenv_mlp32_dw_kernel(DwLayer p, Mlp32Rows rw) {
+// INDEXED (INPUT only; sigmaenv_mlp32_backward_indexed): a third instantiation whose input rows are blocks picked by `ix` (Mlp32Index, sigmaenv_mlp32.inc).  A lane loads
+// the index entry of each of its rows once (the 32 lanes of a half-wavefront read the same word) and both of its columns from that row; a row whose entry is outside the
+// record contributes zeros to dW_0, as a row past the range does.  g, the partition and the order of the chains are those of the other two.
+template <bool INPUT, bool INDEXED = false>
+__global__ void __launch_bounds__(256) sigmaenv_mlp32_dw_kernel(DwLayer p, Mlp32Rows rw, Mlp32Index ix) {
   sigma_poison_lds();
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, m = lane & 31, h = lane >> 5;
   const int nkb = (p.K + GRAD_BLK - 1) / GRAD_BLK;
@@ -151,12 +156,17 @@ __global__ void __launch_bounds__(256) sigmaenv_mlp32_dw_kernel(DwLayer p, Mlp32
       const bool ok = row < r_end;
       const float* gp = p.g + (size_t)row * p.gs + f0 + m;
       const float* ap;
-      if constexpr (INPUT) ap = mlp32_row_ptr<true>(p.a, ok ? (int)row : 0, 0, rw) + k0 + m;
+      bool a_ok = ok;
+      if constexpr (INDEXED) {
+        const long long off = ok ? mlp32_indexed_row_offset((int)row, rw, ix) : -1ll;
+        a_ok = off >= 0;
+        ap = p.a + (a_ok ? off : 0ll) + k0 + m;
+      } else if constexpr (INPUT) ap = mlp32_row_ptr<true>(p.a, ok ? (int)row : 0, 0, rw) + k0 + m;
       else ap = p.a + (size_t)row * MLP32_H + k0 + m;
       gv[0][u] = ok && lf0 ? gp[0] : 0.0f;
       gv[1][u] = ok && lf1 ? gp[32] : 0.0f;
-      av[0][u] = ok && lk0 ? ap[0] : 0.0f;
-      av[1][u] = ok && lk1 ? ap[32] : 0.0f;
+      av[0][u] = a_ok && lk0 ? ap[0] : 0.0f;
+      av[1][u] = a_ok && lk1 ? ap[32] : 0.0f;
     }
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
@@ -264,26 +274,51 @@ static int mlp32_grad_rows(sigmaenv_t* h, const sigmaenv_mlp32* m, const char* w
   return SIGMAENV_OK;
 }
 
-extern "C" int sigmaenv_mlp32_forward_save(sigmaenv_t* h, sigmaenv_mlp32* m, const float* in, int32_t rows_per_block, int64_t row_stride, int32_t n_blocks, int64_t block_stride,
-                                           float* out, float* acts) {
+// the indexed entry points' own arguments: the minibatch takes the place of the record's blocks in the row count; *ix is what the kernels get
+static int mlp32_grad_index(sigmaenv_t* h, const char* what, int32_t n_blocks, int64_t block_stride, const int32_t* index, int32_t n_index, Mlp32Index* ix) {
+  if (n_blocks < 0 || n_index < 0 || block_stride < 0) { h->err = std::string(what) + ": negative n_blocks, index length or block_stride"; return SIGMAENV_EINVAL; }
+  if (n_index > 0 && (!index || ((uintptr_t)index & 3))) { h->err = std::string(what) + ": a null index or one that is not 4-byte aligned"; return SIGMAENV_EINVAL; }
+  ix->index = index;
+  ix->n_blocks = n_blocks;
+  return SIGMAENV_OK;
+}
+
+// index == nullptr: the rows' blocks are the record's blocks 0 .. n_blocks - 1 (sigmaenv_mlp32_forward_save); else the n_index blocks index[.] of its n_blocks
+static int mlp32_forward_save_impl(sigmaenv_t* h, sigmaenv_mlp32* m, const char* what, const float* in, int32_t rows_per_block, int64_t row_stride, int32_t n_blocks,
+                                   int64_t block_stride, const int32_t* index, int32_t n_index, float* out, float* acts) {
   if (!h) return SIGMAENV_EINVAL;
-  if (!m) { h->err = "mlp32_forward_save: null network handle"; return SIGMAENV_EINVAL; }
+  if (!m) { h->err = std::string(what) + ": null network handle"; return SIGMAENV_EINVAL; }
   Mlp32Rows rw{};
+  Mlp32Index ix{};
   int64_t rows = 0;
-  if (const int rc = mlp32_grad_rows(h, m, "mlp32_forward_save", in, rows_per_block, row_stride, n_blocks, block_stride, &rw, &rows)) return rc;
+  if (index || n_index)
+    if (const int rc = mlp32_grad_index(h, what, n_blocks, block_stride, index, n_index, &ix)) return rc;
+  if (const int rc = mlp32_grad_rows(h, m, what, in, rows_per_block, row_stride, ix.index ? n_index : n_blocks, block_stride, &rw, &rows)) return rc;
   if (rows == 0) return SIGMAENV_OK;
-  if (!out || !acts || ((uintptr_t)out & 3) || ((uintptr_t)acts & 15)) { h->err = "mlp32_forward_save: null out / acts, or acts not 16-byte aligned"; return SIGMAENV_EINVAL; }
+  if (!out || !acts || ((uintptr_t)out & 3) || ((uintptr_t)acts & 15)) { h->err = std::string(what) + ": null out / acts, or acts not 16-byte aligned"; return SIGMAENV_EINVAL; }
   HIPCHK(h, hipSetDevice(h->device));
-  const void* kfn = reinterpret_cast<const void*>(sigmaenv_mlp32_kernel<true, true>);
+  const void* kfn = ix.index ? reinterpret_cast<const void*>(sigmaenv_mlp32_kernel<true, true, true>) : reinterpret_cast<const void*>(sigmaenv_mlp32_kernel<true, true>);
   HIPCHK(h, hipFuncSetAttribute(kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)m->smem));
   const dim3 grid((unsigned)((rows + MLP32_ROWS - 1) / MLP32_ROWS));
 #ifdef SIGMAENV_PROFILE
-  hipLaunchKernelGGL((sigmaenv_mlp32_kernel<true, true>), grid, dim3(256), m->smem, h->stream, m->w, in, (int)rows, m->in_dim, out, rw, acts, (unsigned long long*)nullptr, 0);
+  if (ix.index) hipLaunchKernelGGL((sigmaenv_mlp32_kernel<true, true, true>), grid, dim3(256), m->smem, h->stream, m->w, in, (int)rows, m->in_dim, out, rw, acts, ix, (unsigned long long*)nullptr, 0);
+  else hipLaunchKernelGGL((sigmaenv_mlp32_kernel<true, true>), grid, dim3(256), m->smem, h->stream, m->w, in, (int)rows, m->in_dim, out, rw, acts, ix, (unsigned long long*)nullptr, 0);
 #else
-  hipLaunchKernelGGL((sigmaenv_mlp32_kernel<true, true>), grid, dim3(256), m->smem, h->stream, m->w, in, (int)rows, m->in_dim, out, rw, acts);
+  if (ix.index) hipLaunchKernelGGL((sigmaenv_mlp32_kernel<true, true, true>), grid, dim3(256), m->smem, h->stream, m->w, in, (int)rows, m->in_dim, out, rw, acts, ix);
+  else hipLaunchKernelGGL((sigmaenv_mlp32_kernel<true, true>), grid, dim3(256), m->smem, h->stream, m->w, in, (int)rows, m->in_dim, out, rw, acts, ix);
 #endif
   HIPCHK(h, hipGetLastError());
   return SIGMAENV_OK;
+}
+
+extern "C" int sigmaenv_mlp32_forward_save(sigmaenv_t* h, sigmaenv_mlp32* m, const float* in, int32_t rows_per_block, int64_t row_stride, int32_t n_blocks, int64_t block_stride,
+                                           float* out, float* acts) {
+  return mlp32_forward_save_impl(h, m, "mlp32_forward_save", in, rows_per_block, row_stride, n_blocks, block_stride, nullptr, 0, out, acts);
+}
+extern "C" int sigmaenv_mlp32_forward_save_indexed(sigmaenv_t* h, sigmaenv_mlp32* m, const float* in, int32_t rows_per_block, int64_t row_stride, int32_t n_blocks,
+                                                   int64_t block_stride, const int32_t* index, int32_t n_index, float* out, float* acts) {
+  if (h && !index && n_index == 0) return SIGMAENV_OK;  // (an empty minibatch: no row)
+  return mlp32_forward_save_impl(h, m, "mlp32_forward_save_indexed", in, rows_per_block, row_stride, n_blocks, block_stride, index, n_index, out, acts);
 }
 
 extern "C" int sigmaenv_mlp32_backward_workspace(const sigmaenv_mlp32* m, int64_t rows, uint64_t* n_floats) {
@@ -292,22 +327,27 @@ extern "C" int sigmaenv_mlp32_backward_workspace(const sigmaenv_mlp32* m, int64_
   return SIGMAENV_OK;
 }
 
-extern "C" int sigmaenv_mlp32_backward(sigmaenv_t* h, sigmaenv_mlp32* m, const float* in, int32_t rows_per_block, int64_t row_stride, int32_t n_blocks, int64_t block_stride,
-                                       const float* acts, const float* dout, float* workspace, float* const* grad_w, float* const* grad_b) {
+static int mlp32_backward_impl(sigmaenv_t* h, sigmaenv_mlp32* m, const char* what_c, const float* in, int32_t rows_per_block, int64_t row_stride, int32_t n_blocks,
+                               int64_t block_stride, const int32_t* index, int32_t n_index, const float* acts, const float* dout, float* workspace, float* const* grad_w,
+                               float* const* grad_b) {
   if (!h) return SIGMAENV_EINVAL;
-  if (!m) { h->err = "mlp32_backward: null network handle"; return SIGMAENV_EINVAL; }
+  const std::string what(what_c);
+  if (!m) { h->err = what + ": null network handle"; return SIGMAENV_EINVAL; }
   const int n = m->w.n_layers;
-  if (!grad_w || !grad_b) { h->err = "mlp32_backward: null gradient pointer array"; return SIGMAENV_EINVAL; }
+  if (!grad_w || !grad_b) { h->err = what + ": null gradient pointer array"; return SIGMAENV_EINVAL; }
   for (int l = 0; l < n; ++l)
     if (!grad_w[l] || !grad_b[l] || ((uintptr_t)grad_w[l] & 3) || ((uintptr_t)grad_b[l] & 3)) {
-      h->err = "mlp32_backward: layer " + std::to_string(l) + ": a null gradient tensor or one that is not 4-byte aligned";
+      h->err = what + ": layer " + std::to_string(l) + ": a null gradient tensor or one that is not 4-byte aligned";
       return SIGMAENV_EINVAL;
     }
   Mlp32Rows rw{};
+  Mlp32Index ix{};
   int64_t rows = 0;
-  if (const int rc = mlp32_grad_rows(h, m, "mlp32_backward", in, rows_per_block, row_stride, n_blocks, block_stride, &rw, &rows)) return rc;
+  if (index || n_index)
+    if (const int rc = mlp32_grad_index(h, what_c, n_blocks, block_stride, index, n_index, &ix)) return rc;
+  if (const int rc = mlp32_grad_rows(h, m, what_c, in, rows_per_block, row_stride, ix.index ? n_index : n_blocks, block_stride, &rw, &rows)) return rc;
   if (rows > 0 && (!acts || !dout || !workspace || ((uintptr_t)acts & 15) || ((uintptr_t)dout & 3) || ((uintptr_t)workspace & 15))) {
-    h->err = "mlp32_backward: null acts / dout / workspace, or acts / workspace not 16-byte aligned";
+    h->err = what + ": null acts / dout / workspace, or acts / workspace not 16-byte aligned";
     return SIGMAENV_EINVAL;
   }
   HIPCHK(h, hipSetDevice(h->device));
@@ -332,12 +372,25 @@ extern "C" int sigmaenv_mlp32_backward(sigmaenv_t* h, sigmaenv_mlp32* m, const f
       p.a = l == 0 ? in : acts + (size_t)(l - 1) * (size_t)R * MLP32_H;
       p.pw = pw; p.pb = pb; p.F = F; p.K = K; p.R = R; p.len = grad::range_len(rows);
       const dim3 grid((unsigned)(((F + GRAD_BLK - 1) / GRAD_BLK) * ((K + GRAD_BLK - 1) / GRAD_BLK)), (unsigned)ranges);
-      if (l == 0) hipLaunchKernelGGL(grad::sigmaenv_mlp32_dw_kernel<true>, grid, dim3(256), 0, h->stream, p, rw);
-      else hipLaunchKernelGGL(grad::sigmaenv_mlp32_dw_kernel<false>, grid, dim3(256), 0, h->stream, p, Mlp32Rows{});
+      if (l == 0 && ix.index) hipLaunchKernelGGL((grad::sigmaenv_mlp32_dw_kernel<true, true>), grid, dim3(256), 0, h->stream, p, rw, ix);
+      else if (l == 0) hipLaunchKernelGGL(grad::sigmaenv_mlp32_dw_kernel<true>, grid, dim3(256), 0, h->stream, p, rw, Mlp32Index{});
+      else hipLaunchKernelGGL(grad::sigmaenv_mlp32_dw_kernel<false>, grid, dim3(256), 0, h->stream, p, Mlp32Rows{}, Mlp32Index{});
       HIPCHK(h, hipGetLastError());
     }
     hipLaunchKernelGGL(grad::sigmaenv_mlp32_dw_sum_kernel, dim3((unsigned)((F * K + F + 255) / 256)), dim3(256), 0, h->stream, pw, pb, ranges, F * K, F, grad_w[l], grad_b[l]);
     HIPCHK(h, hipGetLastError());
   }
   return SIGMAENV_OK;
+}
+
+extern "C" int sigmaenv_mlp32_backward(sigmaenv_t* h, sigmaenv_mlp32* m, const float* in, int32_t rows_per_block, int64_t row_stride, int32_t n_blocks, int64_t block_stride,
+                                       const float* acts, const float* dout, float* workspace, float* const* grad_w, float* const* grad_b) {
+  return mlp32_backward_impl(h, m, "mlp32_backward", in, rows_per_block, row_stride, n_blocks, block_stride, nullptr, 0, acts, dout, workspace, grad_w, grad_b);
+}
+extern "C" int sigmaenv_mlp32_backward_indexed(sigmaenv_t* h, sigmaenv_mlp32* m, const float* in, int32_t rows_per_block, int64_t row_stride, int32_t n_blocks,
+                                               int64_t block_stride, const int32_t* index, int32_t n_index, const float* acts, const float* dout, float* workspace,
+                                               float* const* grad_w, float* const* grad_b) {
+  // (an empty minibatch is the rows = 0 case of sigmaenv_mlp32_backward: the gradients are written as zeros)
+  if (!index && n_index == 0) return mlp32_backward_impl(h, m, "mlp32_backward_indexed", in, rows_per_block, row_stride, 0, block_stride, nullptr, 0, acts, dout, workspace, grad_w, grad_b);
+  return mlp32_backward_impl(h, m, "mlp32_backward_indexed", in, rows_per_block, row_stride, n_blocks, block_stride, index, n_index, acts, dout, workspace, grad_w, grad_b);
 }

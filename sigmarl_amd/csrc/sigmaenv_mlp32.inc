@@ -56,6 +56,18 @@ __device__ __forceinline__ const float* mlp32_row_ptr(const float* __restrict__ 
     return in + (size_t)row * in_dim;
   }
 }
+// Indexed blocks (sigmaenv_mlp32_forward_save_indexed / sigmaenv_mlp32_backward_indexed): block t of the rows is block index[t] of the record, i.e. row r = t * rpb + b
+// lies at in + index[t] * block_stride + b * row_stride.  An entry outside [0, n_blocks) is never used as an address: the row is staged as zeros, as a row beyond R is.
+struct Mlp32Index {
+  const int32_t* index;  // device i32 [rows / rpb]
+  int n_blocks;          // the record's block count: the bound on the entries
+};
+// the float offset of row `row` (< the row count) from `in`, or -1 for an entry outside the record.  ONE load of the entry per row: the callers keep the offset
+__device__ __forceinline__ long long mlp32_indexed_row_offset(int row, const Mlp32Rows& rw, const Mlp32Index& ix) {
+  const int t = row / rw.rpb, b = row - t * rw.rpb;
+  const int f = ix.index[t];
+  return (unsigned)f < (unsigned)ix.n_blocks ? (long long)f * rw.block_stride + (long long)b * rw.row_stride : -1ll;
+}
 // Four (eight) floats at a 4-byte-aligned address p from 16-byte-ALIGNED loads: the granule that holds p[0] and the following one (two), each only when it holds
 // one of the wanted floats -- so no load touches a granule without a valid float, and an aligned granule never crosses a page --, the wanted floats selected by
 // s = the offset of p in its granule.  A row's lanes read consecutive granules: the requests coalesce as those of the aligned path do (3 loads per 8 floats, not 2).
@@ -139,9 +151,12 @@ __device__ __forceinline__ void mlp32_tile_k256(const float4* __restrict__ wa, c
 // 128 bytes of scratch per lane -- tools/kernel_resources.sh)
 // SAVE (sigmaenv_mlp32_forward_save, sigmaenv_grad.inc): a third instantiation that also writes every hidden layer's post-tanh tile -- the registers the LDS store
 // below takes -- to acts [n_layers - 1][R][256]; the other two never read `acts` and compile to what they were (profiles/learn_kernel_resources.txt).
-template <bool ROWS, bool SAVE = false>
+// INDEXED (sigmaenv_mlp32_forward_save_indexed): a fourth instantiation, <true, true, true>, whose rows are blocks picked by `ix` (Mlp32Index).  The 64 row offsets of the
+// tile are formed once, by the first 64 lanes, into the LDS words the output layer's partial sums use much later; stage() reads them from there.  The other three never
+// read `ix` and keep their figures (profiles/ppo_kernel_resources.txt).
+template <bool ROWS, bool SAVE = false, bool INDEXED = false>
 __global__ void __launch_bounds__(256, 2) sigmaenv_mlp32_kernel(Mlp32Weights mw, const float* __restrict__ in, int R, int in_dim, float* __restrict__ out, Mlp32Rows rw,
-                                                                float* __restrict__ acts MLP32_TS_ARG) {
+                                                                float* __restrict__ acts, Mlp32Index ix MLP32_TS_ARG) {
   sigma_poison_lds();
   MLP32_TS(0);
 #ifdef SIGMAENV_PROFILE
@@ -176,6 +191,11 @@ __global__ void __launch_bounds__(256, 2) sigmaenv_mlp32_kernel(Mlp32Weights mw,
     const int k1 = KQ0 > 1 ? 1 : 0;
     l0w[0] = wa0[0]; l0w[1] = wa0[(size_t)KQ0 * 64]; l0w[2] = wa0[(size_t)k1 * 64]; l0w[3] = wa0[(size_t)(KQ0 + k1) * 64];
   }
+  const long long* row_off = reinterpret_cast<const long long*>(part);  // INDEXED: [64] float offsets of the tile's rows, -1: a row to stage as zeros
+  if constexpr (INDEXED) {
+    if (tid < MLP32_ROWS) reinterpret_cast<long long*>(part)[tid] = row0 + tid < R ? mlp32_indexed_row_offset(row0 + tid, rw, ix) : -1ll;
+    __syncthreads();
+  }
   // input tile, columns [c0, c0 + cw) of layer 0 (cw a multiple of 8, at most MLP32_KC; columns >= in_dim are zeros) at LDS columns [0, cw)
   auto stage = [&](const int c0, const int cw) {
     if ((in_dim & 3) == 0) {  // four columns per lane and load (rows are 16-byte aligned: include/sigmaenv.h)
@@ -184,7 +204,10 @@ __global__ void __launch_bounds__(256, 2) sigmaenv_mlp32_kernel(Mlp32Weights mw,
         const int n = e / Q, kl = (e - n * Q) << 2, k = c0 + kl;
         const int row = row0 + n;
         float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (row < R && k < in_dim) {
+        if constexpr (INDEXED) {
+          const long long off = row_off[n];
+          if (off >= 0 && k < in_dim) v = rw.aligned ? reinterpret_cast<const float4*>(in + off + k)[0] : mlp32_ld4_realign(in + off + k);
+        } else if (row < R && k < in_dim) {
           if constexpr (ROWS) {
             const float* src = mlp32_row_ptr<true>(in, row, in_dim, rw) + k;
             v = rw.aligned ? reinterpret_cast<const float4*>(src)[0] : mlp32_ld4_realign(src);
@@ -201,7 +224,12 @@ __global__ void __launch_bounds__(256, 2) sigmaenv_mlp32_kernel(Mlp32Weights mw,
       for (int e = tid; e < cw * MLP32_ROWS; e += blockDim.x) {            // (coalesced along k within a row)
         const int n = e / cw, kl = e - n * cw, k = c0 + kl;
         const int row = row0 + n;
-        x[mlp32_act_idx(kl, n)] = (row < R && k < in_dim) ? mlp32_row_ptr<ROWS>(in, row, in_dim, rw)[k] : 0.0f;
+        if constexpr (INDEXED) {
+          const long long off = row_off[n];
+          x[mlp32_act_idx(kl, n)] = (off >= 0 && k < in_dim) ? in[off + k] : 0.0f;
+        } else {
+          x[mlp32_act_idx(kl, n)] = (row < R && k < in_dim) ? mlp32_row_ptr<ROWS>(in, row, in_dim, rw)[k] : 0.0f;
+        }
       }
     }
   };
@@ -565,11 +593,11 @@ static int mlp32_forward_impl(sigmaenv_t* h, sigmaenv_mlp32* m, const float* in,
     HIPCHK(h, hipFuncSetAttribute(kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem_l));
   }
   const int stagger_l = getenv("SIGMAENV_MLP32_STAGGER") ? atoi(getenv("SIGMAENV_MLP32_STAGGER")) : 0;
-  if (rw) hipLaunchKernelGGL(sigmaenv_mlp32_kernel<true>, dim3((rows + MLP32_ROWS - 1) / MLP32_ROWS), dim3(256), smem_l, h->stream, m->w, in, (int)rows, m->in_dim, out, *rw, (float*)nullptr, m->ts, stagger_l);
-  else hipLaunchKernelGGL(sigmaenv_mlp32_kernel<false>, dim3((rows + MLP32_ROWS - 1) / MLP32_ROWS), dim3(256), smem_l, h->stream, m->w, in, (int)rows, m->in_dim, out, Mlp32Rows{}, (float*)nullptr, m->ts, stagger_l);
+  if (rw) hipLaunchKernelGGL(sigmaenv_mlp32_kernel<true>, dim3((rows + MLP32_ROWS - 1) / MLP32_ROWS), dim3(256), smem_l, h->stream, m->w, in, (int)rows, m->in_dim, out, *rw, (float*)nullptr, Mlp32Index{}, m->ts, stagger_l);
+  else hipLaunchKernelGGL(sigmaenv_mlp32_kernel<false>, dim3((rows + MLP32_ROWS - 1) / MLP32_ROWS), dim3(256), smem_l, h->stream, m->w, in, (int)rows, m->in_dim, out, Mlp32Rows{}, (float*)nullptr, Mlp32Index{}, m->ts, stagger_l);
 #else
-  if (rw) hipLaunchKernelGGL(sigmaenv_mlp32_kernel<true>, dim3((rows + MLP32_ROWS - 1) / MLP32_ROWS), dim3(256), m->smem, h->stream, m->w, in, (int)rows, m->in_dim, out, *rw, (float*)nullptr);
-  else hipLaunchKernelGGL(sigmaenv_mlp32_kernel<false>, dim3((rows + MLP32_ROWS - 1) / MLP32_ROWS), dim3(256), m->smem, h->stream, m->w, in, (int)rows, m->in_dim, out, Mlp32Rows{}, (float*)nullptr);
+  if (rw) hipLaunchKernelGGL(sigmaenv_mlp32_kernel<true>, dim3((rows + MLP32_ROWS - 1) / MLP32_ROWS), dim3(256), m->smem, h->stream, m->w, in, (int)rows, m->in_dim, out, *rw, (float*)nullptr, Mlp32Index{});
+  else hipLaunchKernelGGL(sigmaenv_mlp32_kernel<false>, dim3((rows + MLP32_ROWS - 1) / MLP32_ROWS), dim3(256), m->smem, h->stream, m->w, in, (int)rows, m->in_dim, out, Mlp32Rows{}, (float*)nullptr, Mlp32Index{});
 #endif
   HIPCHK(h, hipGetLastError());
   timer_end(h, SIGMAENV_KERNEL_MLP32, slot);

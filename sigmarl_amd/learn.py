@@ -7,8 +7,14 @@ average_gae=False)``, ``sigmarl/modules/optimization_module.py:62-67``) and, wit
   ``Critic.rollout_values``        the critic on both sides of every step, read from the records where they lie (``sigmaenv_mlp32_forward_rows``)
   ``gae``                          ``sigmaenv_gae``: advantage, value target and TD-error priorities from the record's rewards / done flags and those values
   ``collect``                      the three in a row; returns the batch under the keys of the reference's tensordict
-This is the collector side of the boundary: no loss, no optimiser, no replay buffer.  torchrl is absent here: GAE's semantics are restated from its published
-behaviour (the arithmetic contract is in ``include/sigmaenv.h``).
+and the learner's side, ``_train_epoch`` / ``_train_on_batch`` (``sigmarl/mappo_cavs.py:389-426``) on minibatches of frames (``:321-340``):
+  ``minibatches``                  one epoch's shuffled frame indices, cut into minibatches (``SamplerWithoutReplacement``)
+  ``Actor.apply`` / ``Critic.apply(index=)``   the networks on the frames of a minibatch, read from the records where they lie, with a ``grad_fn``
+  ``ppo_head``                     ``sigmaenv_ppo_head``: torchrl's ``ClipPPOLoss`` as ``sigmarl/modules/optimization_module.py:44-66`` configures it, one fused launch
+                                   from the networks' outputs and the records to the loss terms and both ``dout`` tensors
+  ``update``                       the epochs x minibatches loop: apply -> head -> backward -> ``clip_grad_norm_`` -> ``optim.step()`` -> ``load``
+Gradient clipping, Adam and the prioritized buffer's priorities stay in torch.  torchrl is absent here: GAE's and the loss's semantics are restated from its published
+behaviour (the arithmetic contracts are in ``include/sigmaenv.h``).
 """
 from __future__ import annotations
 
@@ -96,3 +102,125 @@ def collect(env, actor, critic, T: int, params=None, gamma: float | None = None,
     if td is not None:
         out["td_error"] = td
     return out
+
+
+# ---- the learner's side: minibatches of frames, the clip-PPO head, the update loop --------------------------------------------------------
+class _PpoHeadFunction(torch.autograd.Function):
+    """``ppo_head``: ``sigmaenv_ppo_head`` forwards; backwards the stored ``dout`` tensors times the incoming gradient of the loss."""
+
+    @staticmethod
+    def forward(ctx, env, args, keep, out, value):
+        dev = env.device
+        M, N = out.shape[0], out.shape[1]
+        kw = dict(dtype=torch.float32, device=dev)
+        dout_a, dout_c, result = torch.empty((M, N, 4), **kw), torch.empty((M,), **kw), torch.empty((8,), **kw)
+        ws = torch.empty((capi.PPO_SUMS * ((M * N + 255) // 256),), **kw)
+        out, value = out.detach(), value.detach()
+        args.out, args.value = out.data_ptr(), value.data_ptr()
+        args.dout_actor, args.dout_critic, args.result, args.workspace = dout_a.data_ptr(), dout_c.data_ptr(), result.data_ptr(), ws.data_ptr()
+        cur = torch.cuda.current_stream(dev)
+        with torch.cuda.device(dev):  # on the env's stream after what torch's current stream holds, which then waits for it (Mlp32.apply's discipline)
+            env.stream.wait_stream(cur)
+            rc = env.lib.ppo_head(env.h, C.byref(args))
+            if rc != 0:
+                raise RuntimeError(f"sigmaenv_ppo_head failed with code {rc}: {env.lib.last_error(env.h).decode()}")
+            cur.wait_stream(env.stream)
+        for t in (out, value, dout_a, dout_c, result, ws, *keep):
+            t.record_stream(env.stream)
+        ctx.save_for_backward(dout_a, dout_c)
+        ctx.mark_non_differentiable(result)
+        return (result[0] + result[1]) + result[2], result
+
+    @staticmethod
+    def backward(ctx, g, _):
+        dout_a, dout_c = ctx.saved_tensors
+        return None, None, None, dout_a * g, dout_c * g
+
+
+def ppo_head(env, out: torch.Tensor, value: torch.Tensor, batch: dict, index: torch.Tensor, *, low, high, clip_epsilon: float, entropy_coeff: float,
+             critic_coeff: float = 1.0, seed: int, counter: int):
+    """The clip-PPO loss of one minibatch of frames (``sigmaenv_ppo_head``; every formula: ``include/sigmaenv.h``): ``out [M, N, 4]`` = ``Actor.apply(index=)``,
+    ``value [M]`` = ``Critic.apply(index=)``, ``batch`` what ``collect`` returned -- ``action``, ``sample_log_prob``, ``advantage`` and ``value_target`` are read in
+    place at the frames ``index [M]`` (int32 CUDA; frame ``f = t * B + b``) --, ``low`` / ``high`` the actor's action bounds, ``(seed, counter)`` the key of the
+    entropy sample's draws (a new ``counter`` per minibatch).  Returns ``(loss, info)``: ``loss = loss_objective + loss_entropy + loss_critic`` with a ``grad_fn``
+    over ``out`` and ``value`` (a ``torch.autograd.Function``: the head writes both ``dout`` tensors in its forward launch, ``backward`` scales them), ``info`` the
+    detached ``loss_objective``, ``loss_entropy``, ``loss_critic``, ``entropy``, ``clip_fraction``, ``kl_approx``.  Enqueued on the env's stream, nothing waits."""
+    N = env.N
+    for t, what in ((out, "out"), (value, "value")):
+        if not isinstance(t, torch.Tensor) or not (t.is_cuda and t.dtype == torch.float32 and t.device == env.device):
+            raise TypeError(f"ppo_head: {what} must be a float32 CUDA tensor on {env.device}")
+    if not (isinstance(index, torch.Tensor) and index.is_cuda and index.dtype == torch.int32 and index.dim() == 1 and index.is_contiguous() and index.device == env.device):
+        raise TypeError(f"ppo_head: index must be a contiguous int32 CUDA tensor [M] on {env.device}")
+    M = index.numel()
+    if M < 1 or out.numel() != M * N * 4 or value.numel() != M:
+        raise ValueError(f"ppo_head: out {list(out.shape)} / value {list(value.shape)} are not [M, {N}, 4] / [M] of the {M} indexed frames (M >= 1)")
+    act = batch["action"]
+    if not isinstance(act, torch.Tensor) or act.dim() != 4:
+        raise TypeError("ppo_head: batch['action'] must be [T, B, N, 2]")
+    T, B = act.shape[0], act.shape[1]
+    recs = (check_record(act, (T, B, N, 2), "action"), check_record(batch["sample_log_prob"], (T, B, N), "sample_log_prob"),
+            check_record(batch["advantage"], (T, B, N), "advantage"), check_record(batch["value_target"], (T, B, N), "value_target"))
+    if not 0.0 < float(clip_epsilon) < 1.0:
+        raise ValueError(f"clip_epsilon = {clip_epsilon} is not in (0, 1)")
+    a = capi.PpoHeadArgs()
+    a.n_index, a.n_frames, a.index = M, T * B, index.data_ptr()
+    a.action, a.sample_log_prob, a.advantage, a.value_target = (t.data_ptr() for t in recs)
+    a.low[0], a.low[1], a.high[0], a.high[1] = float(low[0]), float(low[1]), float(high[0]), float(high[1])
+    a.clip_epsilon, a.entropy_coeff, a.critic_coeff = float(clip_epsilon), float(entropy_coeff), float(critic_coeff)
+    a.seed, a.counter = int(seed) & 0xFFFFFFFFFFFFFFFF, int(counter) & 0xFFFFFFFFFFFFFFFF
+    loss, result = _PpoHeadFunction.apply(env, a, (index, *recs), out.reshape(M, N, 4).contiguous(), value.reshape(M).contiguous())
+    return loss, {k: result[i] for i, k in enumerate(capi.PPO_RESULT)}
+
+
+def minibatches(n_frames: int, minibatch_size: int, generator: torch.Generator | None = None, device="cuda") -> list:
+    """One epoch's minibatches of frames: ``torch.randperm(n_frames)`` on the device (``generator``: a CUDA generator, for a reproducible order) as int32, cut into
+    chunks of ``minibatch_size``; the last, shorter chunk is kept (``SamplerWithoutReplacement``'s default, ``drop_last=False``)."""
+    n, mb = int(n_frames), int(minibatch_size)
+    if n < 1 or mb < 1:
+        raise ValueError("minibatches: n_frames and minibatch_size must be >= 1")
+    dev = generator.device if generator is not None else device
+    return list(torch.randperm(n, device=dev, generator=generator).to(torch.int32).split(mb))
+
+
+def update(env, actor, critic, actor_module, critic_module, optim, batch: dict, params=None, *, num_epochs: int | None = None, minibatch_size: int | None = None,
+           clip_epsilon: float | None = None, entropy_coeff: float | None = None, max_grad_norm: float | None = None, critic_coeff: float = 1.0, seed: int = 0,
+           counter0: int = 0, generator: torch.Generator | None = None) -> list:
+    """``_train_epoch`` / ``_train_on_batch`` (``sigmarl/mappo_cavs.py:389-426``) on the batch ``collect`` returned: ``num_epochs x (frames // minibatch_size)``
+    steps of ``Actor.apply`` / ``Critic.apply(index=)`` -> ``ppo_head`` -> ``loss.backward()`` -> ``clip_grad_norm_`` over both modules' parameters ->
+    ``optim.step()`` -> ``optim.zero_grad()`` -> ``actor.load`` / ``critic.load``; every epoch draws a new ``minibatches`` permutation and uses its full chunks.
+    ``actor_module`` / ``critic_module`` are the torch modules the device networks were built or last loaded from (on the device), ``optim`` the optimiser over
+    their parameters.  ``num_epochs``, ``minibatch_size``, ``clip_epsilon``, ``entropy_coeff`` (``entropy_eps``) and ``max_grad_norm`` come from ``params`` (a
+    ``Parameters``; default: the env's) unless given.  Step ``k`` keys its entropy draws with ``(seed, counter0 + k)``.  Returns the ``info`` of every step."""
+    p = params if params is not None else getattr(env, "parameters", None)
+
+    def pick(v, name, attr=None):
+        if v is not None:
+            return v
+        if p is None:
+            raise ValueError(f"update(): {name}, or a Parameters to take it from")
+        return getattr(p, attr or name)
+
+    num_epochs, mb = int(pick(num_epochs, "num_epochs")), int(pick(minibatch_size, "minibatch_size"))
+    clip_epsilon, entropy_coeff = float(pick(clip_epsilon, "clip_epsilon")), float(pick(entropy_coeff, "entropy_coeff", "entropy_eps"))
+    max_grad_norm = float(pick(max_grad_norm, "max_grad_norm"))
+    obs = batch["observation"]
+    T, B, N, D = obs.shape
+    frames = T * B
+    low, high = actor._keep[-2], actor._keep[-1]
+    pars = list(actor_module.parameters()) + list(critic_module.parameters())
+    infos, k = [], 0
+    for _ in range(num_epochs):
+        for index in minibatches(frames, mb, generator, env.device)[: frames // mb]:
+            out = actor.apply(env, rows=(obs, 0, N, D, frames, N * D), index=index, check_index=False)  # (a permutation's entries are in range)
+            value = critic.apply(env, obs, index=index, check_index=False)
+            loss, info = ppo_head(env, out, value, batch, index, low=low, high=high, clip_epsilon=clip_epsilon, entropy_coeff=entropy_coeff, critic_coeff=critic_coeff,
+                                  seed=seed, counter=counter0 + k)
+            loss.backward()
+            torch.nn.utils.clip_grad_norm_(pars, max_grad_norm)
+            optim.step()
+            optim.zero_grad()
+            actor.load(env, actor_module)
+            critic.load(env, critic_module)
+            infos.append(info)
+            k += 1
+    return infos
