@@ -1199,7 +1199,8 @@ struct ResetPrefetch {
 template <bool WAVE = false, bool VARIANTS = true>
 __device__ __forceinline__ void auto_reset_tile(const sigmaenv_config_t& c, const DevMap& m, const DevBufs& g, const Smem& s, const Tile& t,
                                        const unsigned long long* s_mask, const int* s_full, uint64_t seed, uint64_t counter, int path_first,
-                                       int path_count, int obs_mode, const ResetPrefetch& pre, int g_cap = 64, int* lds_tim = nullptr, const CfgDerived* dvp = nullptr);
+                                       int path_count, int obs_mode, const ResetPrefetch& pre, int g_cap = 64, int* lds_tim = nullptr, const CfgDerived* dvp = nullptr,
+                                       bool fin = true);
 #define MAX_G 64
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -1258,7 +1259,7 @@ __global__ void sigmaenv_reset_scatter_kernel(DevBufs g, int N, int n, const int
 template <bool WAVE = false, bool VARIANTS = true>
 __device__ inline void reset_finish_body(const sigmaenv_config_t& c, const DevBufs& g, const Smem& s, const Tile& t,
                                          const unsigned long long* agent_mask, const int* full, int with_obs, int g_cap = 64, int* lds_tim = nullptr,
-                                         const CfgDerived* dvp = nullptr);
+                                         const CfgDerived* dvp = nullptr, bool fin = true);
 __device__ inline void reset_derive_body(const sigmaenv_config_t& c, const DevMap& m, const DevBufs& g, const Smem& s, const Tile& t,
                                          const unsigned long long* agent_mask, const int* full, int with_obs) {
   const int N = t.N;
@@ -1332,12 +1333,31 @@ __device__ inline void reset_derive_body(const sigmaenv_config_t& c, const DevMa
 // tail of every touched env: mutual distances, collisions cleared, prev_pos := pos, timer (road_traffic.py:902-923); with_obs:
 // also a fresh observation of the whole tile (2: every input of it is already in LDS).  Expects the derived state of the marked
 // agents in LDS and HBM.
+// fin = false (the step kernel's step loop, a step that is not the launch's last one; needs lds_tim): the next step of the launch recomputes the mutual distances, the
+// collision matrix and the observation from LDS and the last step writes them, with prev_pos, action, col_flags, the step count and done, to HBM -- what is left here
+// is what no step writes back: the step count and the episode counter in LDS (the latter also in HBM) and the cleared request words.  No random draw moves: the
+// sensor noise of the next observation is keyed on the LDS timer row, which is kept.
 template <bool WAVE, bool VARIANTS>
 __device__ inline void reset_finish_body(const sigmaenv_config_t& c, const DevBufs& g, const Smem& s, const Tile& t,
-                                         const unsigned long long* agent_mask, const int* full, int with_obs, int g_cap, int* lds_tim, const CfgDerived* dvp) {
+                                         const unsigned long long* agent_mask, const int* full, int with_obs, int g_cap, int* lds_tim, const CfgDerived* dvp,
+                                         bool fin) {
   const int N = t.N;
   const int tid = Grp<WAVE>::tid();
 #define TS2(k) PROF_TS2(g, tid, k)
+  if (!fin && lds_tim) {  // (without the step loop's LDS timer rows a reset is always complete)
+    for (int e = tid; e < t.nenv; e += Grp<WAVE>::size()) {
+      if (agent_mask[e] == 0ull) continue;
+      const int b = t.env0 + e;
+      if (full[e]) {
+        const int episodes = lds_tim[e * 4 + 3] + 1;  // (== SIGMAENV_BUF_TIMER's word: the first step of the launch read it, only the resets change it)
+        lds_tim[e * 4] = 0; lds_tim[e * 4 + 3] = episodes;
+        g.timer[b * 4 + 3] = episodes;
+      }
+      g.reset_mask[b] = 0ull;
+      g.reset_full[b] = 0;
+    }
+    return;
+  }
   const float diag = dvp ? dvp->diag : sqrtf(c.world_x_dim * c.world_x_dim + c.world_y_dim * c.world_y_dim);
   for (int p = tid; p < t.slots * N; p += Grp<WAVE>::size()) {
     int si = fdiv(p, g.mN), j = p - si * N;
@@ -1512,49 +1532,54 @@ __global__ void __launch_bounds__(256) sigmaenv_start_table_kernel(sigmaenv_conf
 // place agent slot `sl` on centre-line point `pt` of path `path` with speed `speed`: state and every derived tensor of the agent
 // come from the start table (LDS and HBM), as reset + reset_init_distances_and_short_term_ref_path leave them
 // (world_state_rt_sim.py:189-213, world_state_rt.py:422-529)
+// fin = false (a step of the in-kernel step loop that is not the launch's last one): only what the next step reads from LDS and the path row, which no
+// step writes back, are stored -- the last step of the launch writes every other HBM tensor of the agent, and phases S and C of the next step rewrite the
+// distances to the reference path and the boundaries (dref, dleft, dright, dbound) in LDS before anything reads them.
 __device__ __forceinline__ void place_from_start_table(const DevMap& m, const DevBufs& g, const Smem& s, const Tile& t, int sl, int path, int pt,
-                                                       float speed, int path_first, bool full_env, int scenario_id = 0) {
+                                                       float speed, int path_first, bool full_env, int scenario_id = 0, bool fin = true) {
   const float4* row4 = reinterpret_cast<const float4*>(m.start_table + ((size_t)path * m.P + pt) * START_ROW);
   float r[START_ROW];
 #pragma unroll
   for (int k = 0; k < START_ROW / 4; ++k) { float4 q = row4[k]; r[4 * k] = q.x; r[4 * k + 1] = q.y; r[4 * k + 2] = q.z; r[4 * k + 3] = q.w; }
   const size_t gi = t.a0 + sl;
   const float st[8] = {r[START_X], r[START_X + 1], r[START_X + 2], speed, 0.0f, speed * r[START_COSV], speed * r[START_COSV + 1], 0.0f};
-  float4* gs = reinterpret_cast<float4*>(g.state + gi * 8);
-  gs[0] = make_float4(st[0], st[1], st[2], st[3]);
-  gs[1] = make_float4(st[4], st[5], st[6], st[7]);
+  if (fin) {
+    float4* gs = reinterpret_cast<float4*>(g.state + gi * 8);
+    gs[0] = make_float4(st[0], st[1], st[2], st[3]);
+    gs[1] = make_float4(st[4], st[5], st[6], st[7]);
+  }
 #pragma unroll
   for (int k = 0; k < 8; ++k) s.st[sl * 8 + k] = st[k];
-  float2* gv = reinterpret_cast<float2*>(g.vertices + gi * 10);
 #pragma unroll
   for (int k = 0; k < 5; ++k) {
     s.vnew[sl * 10 + 2 * k] = r[START_VERT + 2 * k]; s.vnew[sl * 10 + 2 * k + 1] = r[START_VERT + 2 * k + 1];
-    gv[k] = make_float2(r[START_VERT + 2 * k], r[START_VERT + 2 * k + 1]);
+    if (fin) reinterpret_cast<float2*>(g.vertices + gi * 10)[k] = make_float2(r[START_VERT + 2 * k], r[START_VERT + 2 * k + 1]);
   }
   s.cs[sl * 2] = r[START_CS]; s.cs[sl * 2 + 1] = r[START_CS + 1];
   // what the next bicycle step of this launch starts from (phase A): steering 0 -> tan 0, sideslip 0, and cos / sin(yaw + 0): the start table's cos / sin of
   // the yaw (same function, same argument; `+ 0.0f` turns the sine of a yaw of -0.0 into the +0.0 that sin(-0.0 + 0.0) is)
   s.carry[sl * 3] = 0.0f; s.carry[sl * 3 + 1] = r[START_CS]; s.carry[sl * 3 + 2] = r[START_CS + 1] + 0.0f;
-  s.dref[sl] = r[START_DREF];
-  g.dist_ref[gi] = r[START_DREF];
+  if (fin) {
+    s.dref[sl] = r[START_DREF];
+    g.dist_ref[gi] = r[START_DREF];
 #pragma unroll
-  for (int q = 0; q < 5; ++q) {
-    s.dleft[sl * 5 + q] = r[START_DLEFT + q]; s.dright[sl * 5 + q] = r[START_DRIGHT + q];
-    g.dist_left[gi * 5 + q] = r[START_DLEFT + q]; g.dist_right[gi * 5 + q] = r[START_DRIGHT + q];
+    for (int q = 0; q < 5; ++q) {
+      s.dleft[sl * 5 + q] = r[START_DLEFT + q]; s.dright[sl * 5 + q] = r[START_DRIGHT + q];
+      g.dist_left[gi * 5 + q] = r[START_DLEFT + q]; g.dist_right[gi * 5 + q] = r[START_DRIGHT + q];
+    }
+    s.dbound[sl] = r[START_DBOUND];
+    g.dist_bound[gi] = r[START_DBOUND];
   }
-  s.dbound[sl] = r[START_DBOUND];
-  g.dist_bound[gi] = r[START_DBOUND];
-  float2* gso = reinterpret_cast<float2*>(g.short_term + gi * NS * 2);
 #pragma unroll
   for (int k = 0; k < NS; ++k) {
     s.shrt[sl * NS * 2 + 2 * k] = r[START_SHORT + 2 * k]; s.shrt[sl * NS * 2 + 2 * k + 1] = r[START_SHORT + 2 * k + 1];
-    gso[k] = make_float2(r[START_SHORT + 2 * k], r[START_SHORT + 2 * k + 1]);
+    if (fin) reinterpret_cast<float2*>(g.short_term + gi * NS * 2)[k] = make_float2(r[START_SHORT + 2 * k], r[START_SHORT + 2 * k + 1]);
   }
 #pragma unroll
-  for (int k = 0; k < 3; ++k) { const int cpk = __float_as_int(r[START_CP + k]); s.cp[sl * 3 + k] = cpk; g.closest[gi * 3 + k] = cpk; }
+  for (int k = 0; k < 3; ++k) { const int cpk = __float_as_int(r[START_CP + k]); s.cp[sl * 3 + k] = cpk; if (fin) g.closest[gi * 3 + k] = cpk; }
   s.path[sl] = path;
   s.fresh[sl] = 1;
-  if (g.fresh) g.fresh[gi] = 1;
+  if (fin && g.fresh) g.fresh[gi] = 1;
   g.path[gi * 4 + 0] = path;
   if (full_env) g.path[gi * 4 + 1] = scenario_id;  // (kept by a per-agent reset; 0 unless cpm_mixed)
   g.path[gi * 4 + 2] = path - path_first;
@@ -1570,7 +1595,8 @@ __device__ __forceinline__ void place_from_start_table(const DevMap& m, const De
 template <bool WAVE, bool VARIANTS>
 __device__ __forceinline__ void auto_reset_tile(const sigmaenv_config_t& c, const DevMap& m, const DevBufs& g, const Smem& s, const Tile& t,
                                        const unsigned long long* s_mask, const int* s_full, uint64_t seed, uint64_t counter, int path_first,
-                                       int path_count, int obs_mode, const ResetPrefetch& pre, int g_cap, int* lds_tim, const CfgDerived* dvp) {
+                                       int path_count, int obs_mode, const ResetPrefetch& pre, int g_cap, int* lds_tim, const CfgDerived* dvp, bool fin_arg) {
+  const bool fin = fin_arg || !lds_tim;  // (the reduced form exists only inside the step loop, which hands in its LDS timer rows: without them a reset is always complete)
   const int N = t.N;
   const int tid = Grp<WAVE>::tid(), lane = tid & 63, wave = tid >> 6, n_waves = Grp<WAVE>::size() >> 6;
   const bool mixed = path_count < 0;  // SIGMAENV_SCENARIO_LISTS: every env draws from the path list of ITS sub-scenario
@@ -1611,7 +1637,7 @@ __device__ __forceinline__ void auto_reset_tile(const sigmaenv_config_t& c, cons
         const int wl = f2 ? (__ffsll((long long)f2) - 1) : (AUTO_RESET_MAX_TRIES - 1);
         if (lane == wl) {
           float u = (float)(rng_u32(seed, counter, (uint32_t)(c.env_index_base + b), (uint32_t)i, 3000u) >> 8) * (1.0f / 16777216.0f);
-          place_from_start_table(m, g, s, t, sl, p2, q2, u * c.max_speed, rd.path_first, false);
+          place_from_start_table(m, g, s, t, sl, p2, q2, u * c.max_speed, rd.path_first, false, 0, fin);
         }
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
@@ -1666,13 +1692,13 @@ __device__ __forceinline__ void auto_reset_tile(const sigmaenv_config_t& c, cons
     if (lane < N) {  // finalise the accepted starts, one lane per agent (world_state_rt_sim.py:189-213)
       const int i = lane, sl = e * N + i;
       float u = (float)(rng_u32(seed, counter, (uint32_t)(c.env_index_base + b), (uint32_t)i, 1000u) >> 8) * (1.0f / 16777216.0f);
-      place_from_start_table(m, g, s, t, sl, my_path, my_pt, u * c.max_speed, rd.path_first, true, sid);
+      place_from_start_table(m, g, s, t, sl, my_path, my_pt, u * c.max_speed, rd.path_first, true, sid, fin);
     }
   }
   __threadfence_block();
   Grp<WAVE>::sync();
   TS2(2);
-  reset_finish_body<WAVE, VARIANTS>(c, g, s, t, s_mask, s_full, obs_mode, g_cap, lds_tim, dvp);
+  reset_finish_body<WAVE, VARIANTS>(c, g, s, t, s_mask, s_full, obs_mode, g_cap, lds_tim, dvp, fin);
 #undef TS2
 }
 

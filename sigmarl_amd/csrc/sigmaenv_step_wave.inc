@@ -1170,7 +1170,10 @@ __global__ void __launch_bounds__(256, STEP_WAVE_MIN_WAVES) sigmaenv_step_wave_k
     if (lane == 0) *s_any = any_w ? 1 : 0;
     wave_sync();
     if (any_w) {
-      auto_reset_tile<true, VAR>(c, m, g, s, t, s_mask, s_full, seed, counter, path_first, path_count, 2, pre, G, s_tim, &dv);  // (a restarted env counts its steps from 0: reset_finish_body)
+      // (a restarted env counts its steps from 0: reset_finish_body).  Before the last step of the launch a reset leaves in HBM only what no step writes back -- path rows,
+      // the episode counter, the request words -- and in LDS what the next step reads: the last step's phases write the rest of the tile (sigmaenv.hip: fin)
+      // (`last` is a run-time, wavefront-uniform switch: two compiled copies of the reset path measured the same and cost 4 KB of code per instantiation)
+      auto_reset_tile<true, VAR>(c, m, g, s, t, s_mask, s_full, seed, counter, path_first, path_count, 2, pre, G, s_tim, &dv, last);
     }
   }
   }
