@@ -18,7 +18,7 @@
 //    MFMA, one ds_read_b128 per lane from LDS), the activations the B operand (32 k x 16 rows) and live in REGISTERS for the whole
 //    network: the accumulator of a layer (feature = 16 ft + 4 (lane >> 4) + reg, row = lane & 15) is, after tanh and conversion to
 //    bf16, directly the B fragment of the next layer when that layer's weight matrix has its K axis permuted accordingly -- k slot
-//    (kb, g, j) <-> input feature 16 (2 kb + (j >> 2)) + 4 g + (j & 3) -- which the host does once (pack_layer).  No transpose, no
+//    (kb, g, j) <-> input feature 16 (2 kb + (j >> 2)) + 4 g + (j & 3) -- which the packing does once (sigmaenv_pack.h).  No transpose, no
 //    LDS round trip between layers.
 //  * One workgroup of 8 wavefronts per CU, every wavefront owns 2 row tiles (32 rows): each weight fragment read from LDS feeds two
 //    MFMAs.  LDS holds one big layer at a time (W2 or W3: 128 KB bf16 of the 160 KB) plus the small first / last layer.
@@ -26,7 +26,7 @@
 typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
 typedef float f32x4_t __attribute__((ext_vector_type(4)));
 
-#define ACT_H 256            /* hidden width */
+#include "sigmaenv_pack.h"  // ACT_H (the hidden width) and the packed bf16 form of the weights
 #ifndef ACT_RT
 #define ACT_RT 2             /* MFMA row tiles (16 rows) per wavefront */
 #endif
@@ -34,7 +34,7 @@ typedef float f32x4_t __attribute__((ext_vector_type(4)));
 #define ACT_WAVES (16 / ACT_RT)
 
 struct ActorWeights {
-  // packed bf16 weights: layer l as [K/32][4][F][8] (see pack_layer), biases fp32
+  // packed bf16 weights: layer l as [K/32][4][F][8] (the bf16 form of sigmaenv_pack.h), biases fp32
   const __bf16 *w1, *w2, *w3, *w4;
   const float *b1, *b2, *b3, *b4;
   int D;            // observation width (multiple of 8, <= 32)
@@ -210,28 +210,14 @@ struct sigmaenv_actor {
   int D = 0;
 };
 
-static uint16_t f32_to_bf16_rne(float f) {
-  uint32_t u;
-  std::memcpy(&u, &f, 4);
-  if ((u & 0x7F800000u) == 0x7F800000u && (u & 0x007FFFFFu)) return (uint16_t)((u >> 16) | 0x40);  // NaN
-  u += 0x7FFFu + ((u >> 16) & 1u);
-  return (uint16_t)(u >> 16);
-}
-
-// torch.nn.Linear weight [F, K] (row-major) -> [K/32][4][Fp][8] bf16 with the k-slot order of the MFMA chaining; `chained`: the
-// input is the previous layer's accumulator layout (k slot (kb, g, j) <-> feature 16 (2 kb + (j >> 2)) + 4 g + (j & 3)), else natural
-// (k slot (kb, g, j) <-> feature 32 kb + 8 g + j).  Fp = F padded to a multiple of 16, K padded to a multiple of 32 with zeros.
-static std::vector<uint16_t> pack_layer(const float* w, int F, int K, bool chained) {
-  const int Fp = (F + 15) / 16 * 16, KB = (K + 31) / 32;
-  std::vector<uint16_t> out((size_t)KB * 4 * Fp * 8, 0);
-  for (int kb = 0; kb < KB; ++kb)
-    for (int g = 0; g < 4; ++g)
-      for (int f = 0; f < F; ++f)
-        for (int j = 0; j < 8; ++j) {
-          const int k = chained ? 16 * (2 * kb + (j >> 2)) + 4 * g + (j & 3) : 32 * kb + 8 * g + j;
-          if (k < K) out[(((size_t)kb * 4 + g) * Fp + f) * 8 + j] = f32_to_bf16_rne(w[(size_t)f * K + k]);
-        }
-  return out;
+// one packed buffer of a network handle on the device (sigmaenv_actor_create, sigmaenv_mlp32_create): allocated, recorded in the handle's allocs, filled from host memory
+static int pack_upload(std::vector<void*>& allocs, const void* src, size_t bytes, const void** dst) {
+  void* p = nullptr;
+  if (hipMalloc(&p, bytes) != hipSuccess) return SIGMAENV_ENOMEM;
+  allocs.push_back(p);
+  if (hipMemcpy(p, src, bytes, hipMemcpyHostToDevice) != hipSuccess) return SIGMAENV_EHIP;
+  *dst = p;
+  return SIGMAENV_OK;
 }
 
 extern "C" void sigmaenv_actor_destroy(sigmaenv_actor* a) {
@@ -246,23 +232,20 @@ extern "C" int sigmaenv_actor_create(int32_t obs_dim, const float* w1, const flo
   if (!out || !w1 || !b1 || !w2 || !b2 || !w3 || !b3 || !w4 || !b4 || !low || !high || obs_dim < 8 || obs_dim > 32 || (obs_dim % 8)) return SIGMAENV_EINVAL;
   auto* a = new sigmaenv_actor();
   a->D = obs_dim;
-  auto up = [&](const void* src, size_t bytes, const void** dst) -> bool {
-    void* p = nullptr;
-    if (hipMalloc(&p, bytes) != hipSuccess) return false;
-    a->allocs.push_back(p);
-    if (hipMemcpy(p, src, bytes, hipMemcpyHostToDevice) != hipSuccess) return false;
-    *dst = p;
-    return true;
-  };
-  const std::vector<uint16_t> p1 = pack_layer(w1, ACT_H, obs_dim, false), p2 = pack_layer(w2, ACT_H, ACT_H, true), p3 = pack_layer(w3, ACT_H, ACT_H, true),
-                              p4 = pack_layer(w4, 4, ACT_H, true);
-  std::vector<float> b4p(16, 0.0f);
-  for (int i = 0; i < 4; ++i) b4p[i] = b4[i];
-  bool ok = up(p1.data(), p1.size() * 2, (const void**)&a->w.w1) && up(p2.data(), p2.size() * 2, (const void**)&a->w.w2) &&
-            up(p3.data(), p3.size() * 2, (const void**)&a->w.w3) && up(p4.data(), p4.size() * 2, (const void**)&a->w.w4) &&
-            up(b1, ACT_H * 4, (const void**)&a->w.b1) && up(b2, ACT_H * 4, (const void**)&a->w.b2) && up(b3, ACT_H * 4, (const void**)&a->w.b3) &&
-            up(b4p.data(), 64, (const void**)&a->w.b4);
-  if (!ok) { sigmaenv_actor_destroy(a); return SIGMAENV_ENOMEM; }
+  // the per-slot function of sigmaenv_pack.h over every lane index of every layer, on the host (sigmaenv_actor_load_device: the same function on the device)
+  const float *ws[4] = {w1, w2, w3, w4}, *bs[4] = {b1, b2, b3, b4};
+  const __bf16** pw[4] = {&a->w.w1, &a->w.w2, &a->w.w3, &a->w.w4};
+  const float** pb[4] = {&a->w.b1, &a->w.b2, &a->w.b3, &a->w.b4};
+  for (int l = 0; l < 4; ++l) {
+    ActorLayer y = pack_actor_layer(obs_dim, l);
+    std::vector<uint16_t> sw(y.n_slots);
+    std::vector<float> sb(y.nb);
+    y.w = ws[l]; y.b = bs[l]; y.pw = sw.data(); y.pb = sb.data();
+    for (int i = 0; i < y.n_slots + y.nb; ++i) pack_actor_slot(y, i);
+    int rc = pack_upload(a->allocs, sw.data(), sw.size() * 2, (const void**)pw[l]);
+    if (!rc) rc = pack_upload(a->allocs, sb.data(), sb.size() * 4, (const void**)pb[l]);
+    if (rc) { sigmaenv_actor_destroy(a); return rc; }
+  }
   a->w.D = obs_dim;
   for (int i = 0; i < 2; ++i) { a->w.low[i] = low[i]; a->w.high[i] = high[i]; }
   const int smem = 16 * 1024 + 128 * 1024;

@@ -10,7 +10,7 @@
 //
 // Mapping.
 //  * delta: one workgroup walks a 64-row tile BACKWARDS through all layers in LDS, as the forward walks it forwards: g_l lies in the forward's activation layout
-//    (mlp32_act_idx, 64 KB), the weights come from the handle's TRANSPOSED exact form (load_exact_t_src: the forward's fragment layout of W^T, so that g W
+//    (mlp32_act_idx, 64 KB), the weights come from the handle's TRANSPOSED exact form (sigmaenv_pack.h: the forward's fragment layout of W^T, so that g W
 //    contracts over the features with one 16-byte load per lane and k block), each wavefront owns two 32-wide tiles of the 256 outputs x both row tiles.  The chain
 //    of an element runs over the features f = 0, 1, .. in order.  Epilogue: times fma(-a, a, 1) -- ONE rounding of 1 - a^2, so the factor keeps its relative
 //    precision where |a| -> 1 -- one more for the product; rows past R are zeros.
@@ -210,13 +210,10 @@ __global__ void __launch_bounds__(256) sigmaenv_mlp32_dw_sum_kernel(const float*
   if (bias) gb[i - nw] = s; else gw[i] = s;
 }
 
-// the transposed exact form of one layer, every slot (padding: zeros) from the map of sigmaenv_load.inc
+// the transposed exact form of one layer, every slot (padding: zeros): the per-slot function of sigmaenv_pack.h, which sigmaenv_mlp32_create runs on the host
 __global__ void __launch_bounds__(256) sigmaenv_load_mlp32_t_kernel(const float* __restrict__ w, float* __restrict__ tw, int F, int K, int n) {
   sigma_poison_lds();
-  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
-    const int s = load_exact_t_src(F, K, i);
-    tw[i] = s >= 0 ? w[s] : 0.0f;
-  }
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) pack_mlp32_t_slot(w, tw, F, K, i);
 }
 
 static inline size_t partial_floats(const sigmaenv_mlp32* m) {  // one range's partials of the largest layer, weights then biases
@@ -226,28 +223,6 @@ static inline size_t partial_floats(const sigmaenv_mlp32* m) {  // one range's p
 }
 
 }  // namespace grad
-
-// the host packer of sigmaenv_mlp32_create: the same map, slot by slot (tests/test_gradient_check.py holds it, the kernel's loop and the exact form of W^T word for word)
-static std::vector<float> mlp32_pack_transposed(const float* w, int F, int K) {
-  std::vector<float> tw((size_t)load_exact_t_slots(F, K));
-  for (int d = 0; d < (int)tw.size(); ++d) {
-    const int s = load_exact_t_src(F, K, d);
-    tw[d] = s >= 0 ? w[s] : 0.0f;
-  }
-  return tw;
-}
-
-static int mlp32_grad_create(sigmaenv_mlp32* m, const float* const* weights) {
-  for (int l = 1; l < m->w.n_layers; ++l) {
-    const std::vector<float> tw = mlp32_pack_transposed(weights[l], m->dims[l + 1], m->dims[l]);
-    void* dw = nullptr;
-    if (hipMalloc(&dw, tw.size() * 4) != hipSuccess) return SIGMAENV_ENOMEM;
-    m->allocs.push_back(dw);
-    if (hipMemcpy(dw, tw.data(), tw.size() * 4, hipMemcpyHostToDevice) != hipSuccess) return SIGMAENV_EHIP;
-    m->wt[l] = (float*)dw;
-  }
-  return SIGMAENV_OK;
-}
 
 static int mlp32_grad_load(sigmaenv_t* h, sigmaenv_mlp32* m, const float* const* weights_dev) {
   for (int l = 1; l < m->w.n_layers; ++l) {

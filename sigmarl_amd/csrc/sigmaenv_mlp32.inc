@@ -26,7 +26,7 @@ typedef float f32x16_t __attribute__((ext_vector_type(16)));
 
 #define MLP32_ROWS 64
 #define MLP32_MAX_LAYERS 4
-#define MLP32_H 256
+#include "sigmaenv_pack.h"  // MLP32_H (the hidden width) and the packed forms of the weights
 #define MLP32_KC 256  // layer 0's input columns staged in LDS at a time (a wider input is multiplied chunk by chunk: the LDS per workgroup does not grow with it)
 
 struct Mlp32Weights {
@@ -413,8 +413,6 @@ struct sigmaenv_mlp32 {
   int ts_groups = 0;
 };
 
-static int mlp32_grad_create(sigmaenv_mlp32* m, const float* const* weights);  // sigmaenv_grad.inc: allocates and fills wt
-
 extern "C" void sigmaenv_mlp32_destroy(sigmaenv_mlp32* m) {
   if (!m) return;
   for (void* p : m->allocs) (void)hipFree(p);
@@ -434,62 +432,36 @@ extern "C" int sigmaenv_mlp32_create(int32_t n_layers, const int32_t* dims, cons
   for (int l = 0; l <= n_layers; ++l) m->dims[l] = dims[l];
   if (hipMalloc((void**)&m->range_word, 4) != hipSuccess) { sigmaenv_mlp32_destroy(m); return SIGMAENV_ENOMEM; }
   m->allocs.push_back(m->range_word);
-  for (int l = 0; l < n_layers; ++l) {
-    const int K = dims[l], F = dims[l + 1];
-    const int Kp = (K + 7) / 8 * 8, Fp = (F + 31) / 32 * 32, KQ = Kp / 8;
-    // packed [Fp / 32][KQ][2][32][4]: weight (feature 32 ft + mm, k = 8 kq + 2 u + hh) at ((((ft KQ + kq) 2 + hh) 32 + mm) 4 + u
-    std::vector<float> wt((size_t)Kp * Fp, 0.0f), bp(Fp, 0.0f);
-    for (int f = 0; f < F; ++f) {
-      bp[f] = biases[l][f];
-      const int ft = f >> 5, mm = f & 31;
-      for (int k = 0; k < K; ++k) {
-        const int kq = k >> 3, u = (k & 7) >> 1, hh = k & 1;
-        wt[((((size_t)ft * KQ + kq) * 2 + hh) * 32 + mm) * 4 + u] = weights[l][(size_t)f * K + k];
-      }
-    }
-    void *dw = nullptr, *db = nullptr;
-    if (hipMalloc(&dw, wt.size() * 4) != hipSuccess) { sigmaenv_mlp32_destroy(m); return SIGMAENV_ENOMEM; }
-    m->allocs.push_back(dw);
-    if (hipMalloc(&db, bp.size() * 4) != hipSuccess) { sigmaenv_mlp32_destroy(m); return SIGMAENV_ENOMEM; }
-    m->allocs.push_back(db);
-    if (hipMemcpy(dw, wt.data(), wt.size() * 4, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(db, bp.data(), bp.size() * 4, hipMemcpyHostToDevice) != hipSuccess) {
-      sigmaenv_mlp32_destroy(m);
-      return SIGMAENV_EHIP;
-    }
-    m->w.w[l] = (const float*)dw; m->w.b[l] = (const float*)db;
-    m->w.K[l] = Kp; m->w.F[l] = F; m->w.Fp[l] = Fp;
-  }
-  m->smem = ((size_t)MLP32_H * MLP32_ROWS + 2 * 32 * 32) * sizeof(float);  // 72 KB for every input width (layer 0's inputs are staged MLP32_KC columns at a time)
-  // the split form: (hi, lo) fp16 fragments of the weights times 2^8, biases times the accumulator scale of their layer
   m->ws.n_layers = n_layers;
-  for (int l = 0; l < n_layers && m->split_ok; ++l)
-    for (size_t i = 0, n = (size_t)dims[l] * dims[l + 1]; i < n; ++i)
-      if (!(std::fabs(weights[l][i]) < 255.0f)) { m->split_ok = false; break; }
-  // (the split buffers exist for a network outside the range as well -- never read while split_ok is false --: sigmaenv_mlp32_load_device may bring it into range)
-  for (int l = 0; l < n_layers; ++l) {
-    const int K = dims[l], F = dims[l + 1];
-    const bool last = l + 1 == n_layers;
-    const std::vector<uint16_t> pk = mlp32s_pack(weights[l], F, K, l > 0, last);
-    const int Fp = last ? 32 : MLP32_H;
-    std::vector<float> bp(Fp, 0.0f);
-    const float bscale = MLP32S_SW * (l == 0 ? MLP32S_SX0 : MLP32S_SX);
-    for (int f = 0; f < F; ++f) bp[f] = biases[l][f] * bscale;
-    void *dw = nullptr, *db = nullptr;
-    if (hipMalloc(&dw, pk.size() * 2) != hipSuccess) { sigmaenv_mlp32_destroy(m); return SIGMAENV_ENOMEM; }
-    m->allocs.push_back(dw);
-    if (hipMalloc(&db, bp.size() * 4) != hipSuccess) { sigmaenv_mlp32_destroy(m); return SIGMAENV_ENOMEM; }
-    m->allocs.push_back(db);
-    if (hipMemcpy(dw, pk.data(), pk.size() * 2, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(db, bp.data(), bp.size() * 4, hipMemcpyHostToDevice) != hipSuccess) {
-      sigmaenv_mlp32_destroy(m);
-      return SIGMAENV_EHIP;
-    }
-    m->ws.w[l] = (const f16x8_t*)dw; m->ws.b[l] = (const float*)db;
-    m->ws.KB[l] = (K + 15) / 16; m->ws.F[l] = F;
-  }
-  m->smem_s = (size_t)(m->ws.KB[0] > 16 ? m->ws.KB[0] : 16) * 256 * 16 + (2 * 16 * 64 + (MLP32_MAX_LAYERS - 1) * MLP32_H + 32) * sizeof(float);
+  m->smem = ((size_t)MLP32_H * MLP32_ROWS + 2 * 32 * 32) * sizeof(float);  // 72 KB for every input width (layer 0's inputs are staged MLP32_KC columns at a time)
+  // whether the split kernel's LDS takes the input width depends on dims[0] alone: known before the layers are packed
+  const int KB0 = load_split_kb(dims[0]);
+  m->smem_s = (size_t)(KB0 > 16 ? KB0 : 16) * 256 * 16 + (2 * 16 * 64 + (MLP32_MAX_LAYERS - 1) * MLP32_H + 32) * sizeof(float);
   m->split_fits = m->smem_s <= 160 * 1024;
-  if (!m->split_ok || !m->split_fits) { m->split_ok = false; m->mode = SIGMAENV_MLP32_EXACT; }
-  if (const int rc = mlp32_grad_create(m, weights)) { sigmaenv_mlp32_destroy(m); return rc; }
+  // Every form of every layer: the per-slot functions of sigmaenv_pack.h over every lane index, on the host (sigmaenv_mlp32_load_device: the same functions on the
+  // device).  The split form is (hi, lo) fp16 fragments of the weights times 2^8 and biases times the accumulator scale of their layer; its buffers exist for a
+  // network outside the range as well (never read while split_ok is false: sigmaenv_mlp32_load_device may bring it into range), and with their full size for a
+  // network that is exact-only by its width, which neither create nor load packs: they hold zeros, and are never read.
+  bool out_of_range = false;
+  for (int l = 0; l < n_layers; ++l) {
+    Mlp32Layer a = pack_mlp32_layer(dims, l, n_layers, m->split_fits);
+    std::vector<float> ew(a.n_exact), eb(a.fp_exact), sb(load_split_biases(a.output_layer != 0), 0.0f), tw(l > 0 ? load_exact_t_slots(a.F, a.K) : 0);
+    std::vector<uint16_t> sw((size_t)2 * load_split_pairs(a.F, a.K, a.output_layer != 0), 0);
+    a.w = weights[l]; a.b = biases[l];
+    a.ew = ew.data(); a.eb = eb.data(); a.sw = sw.data(); a.sb = sb.data();
+    for (int i = 0, n = pack_mlp32_lanes(a); i < n; ++i) out_of_range |= pack_mlp32_slot(a, i);
+    for (int i = 0; i < (int)tw.size(); ++i) pack_mlp32_t_slot(weights[l], tw.data(), a.F, a.K, i);  // the backward pass's form (sigmaenv_grad.inc): layers 1 .. n_layers - 1
+    int rc = pack_upload(m->allocs, ew.data(), ew.size() * 4, (const void**)&m->w.w[l]);
+    if (!rc) rc = pack_upload(m->allocs, eb.data(), eb.size() * 4, (const void**)&m->w.b[l]);
+    if (!rc) rc = pack_upload(m->allocs, sw.data(), sw.size() * 2, (const void**)&m->ws.w[l]);
+    if (!rc) rc = pack_upload(m->allocs, sb.data(), sb.size() * 4, (const void**)&m->ws.b[l]);
+    if (!rc && l > 0) rc = pack_upload(m->allocs, tw.data(), tw.size() * 4, (const void**)&m->wt[l]);
+    if (rc) { sigmaenv_mlp32_destroy(m); return rc; }
+    m->w.K[l] = load_exact_kp(a.K); m->w.F[l] = a.F; m->w.Fp[l] = a.fp_exact;
+    m->ws.KB[l] = load_split_kb(a.K); m->ws.F[l] = a.F;
+  }
+  m->split_ok = m->split_fits && !out_of_range;
+  if (!m->split_ok) m->mode = SIGMAENV_MLP32_EXACT;
   *out = m;
   return SIGMAENV_OK;
 }

@@ -16,14 +16,12 @@
 // Mapping: as the exact kernel -- one workgroup (4 wavefronts) owns 64 rows through all layers, wavefront w owns feature tiles 2 w, 2 w + 1 x both row tiles,
 // weights stream from L2 as A operands (pre-split, pre-permuted fragments: 2 x 1 KB contiguous per wavefront, tile and k block of 16), the activations live in
 // LDS as B-operand fragments [k block][hi | lo][k half][row][8 halves] = 64 KB per 64 rows and K = 256.  Per tile and k block: 2 global 16-byte loads + 4
-// ds_read_b128 feed 6 MFMAs (192 matrix cycles).  A hidden layer's outputs go back as whole 16-byte fragments: the k order of the next layer is PERMUTED on the host so that the
+// ds_read_b128 feed 6 MFMAs (192 matrix cycles).  A hidden layer's outputs go back as whole 16-byte fragments: the k order of the next layer is PERMUTED when its weights are packed (sigmaenv_pack.h) so that the
 // 8 accumulator registers (j = 8 hh .. 8 hh + 7) a lane holds for one row are one fragment -- k slot (kb, hh, j8) <-> feature 32 (kb >> 1) + (j & 3) + 8 (j >> 2)
 // + 4 (kb & 1), j = 8 hh + j8 (conflict-free ds_write_b128, no transpose).
 typedef _Float16 f16x8_t __attribute__((ext_vector_type(8)));
 
-#define MLP32S_SW 256.0f   /* weight scale */
-#define MLP32S_SX 256.0f   /* scale of the hidden activations */
-#define MLP32S_SX0 16.0f   /* scale of the input rows */
+#include "sigmaenv_pack.h"  // the scales MLP32S_SW / SX / SX0 and the packed form of the weights (host: sigmaenv_mlp32_create, device: sigmaenv_load.inc)
 
 struct Mlp32sWeights {
   const f16x8_t* w[MLP32_MAX_LAYERS];  // hidden layer: [F / 32 tiles][KB][hi | lo][64 lanes] fragments; output layer: [KB][hi | lo][64 lanes]
@@ -307,70 +305,4 @@ __global__ void __launch_bounds__(256, 2) sigmaenv_mlp32s_kernel(Mlp32sWeights m
 #endif
   }
 #undef MLP32S_SEL
-}
-
-// ---- host side: fp32 -> (hi, lo) fp16 fragments ----------------------------------------------------------------------------------------
-static uint16_t f32_to_f16_rne(float f) {
-  uint32_t u;
-  std::memcpy(&u, &f, 4);
-  const uint16_t sign = (uint16_t)((u >> 16) & 0x8000u);
-  u &= 0x7FFFFFFFu;
-  if (u >= 0x7F800000u) return (uint16_t)(sign | (u > 0x7F800000u ? 0x7E00u : 0x7C00u));
-  if (u >= 0x477FF000u) return (uint16_t)(sign | 0x7C00u);  // >= 65520 rounds to infinity
-  if (u < 0x38800000u) {                                     // below 2^-14: subnormal result, in units of 2^-24
-    if (u < 0x33000000u) return sign;                        // below 2^-25
-    const int e = (int)(u >> 23), shift = 126 - e;           // 14 .. 24
-    const uint32_t mant = (u & 0x7FFFFFu) | 0x800000u;
-    uint32_t r = mant >> shift;
-    const uint32_t rem = mant & ((1u << shift) - 1u), half = 1u << (shift - 1);
-    if (rem > half || (rem == half && (r & 1u))) ++r;
-    return (uint16_t)(sign | r);
-  }
-  const uint32_t r = u + 0xFFFu + ((u >> 13) & 1u);
-  return (uint16_t)(sign | ((r - 0x38000000u) >> 13));
-}
-static float f16_to_f32(uint16_t hv) {
-  const uint32_t sign = (uint32_t)(hv & 0x8000u) << 16, e = (hv >> 10) & 31u, mant = hv & 0x3FFu;
-  float out;
-  if (e == 0) {
-    out = std::ldexp((float)mant, -24);
-    uint32_t u;
-    std::memcpy(&u, &out, 4);
-    u |= sign;
-    std::memcpy(&out, &u, 4);
-    return out;
-  }
-  const uint32_t u = sign | (e == 31 ? 0x7F800000u | (mant << 13) : ((e + 112u) << 23) | (mant << 13));
-  std::memcpy(&out, &u, 4);
-  return out;
-}
-
-// input feature of k slot (kb, hh, j8) of a layer: natural order for the input layer, the accumulator order of the previous layer's tiles otherwise (a lane's
-// registers j = 8 hh .. 8 hh + 7 are one fragment of k block 2 t + h)
-static inline int mlp32s_feature_of_slot(bool chained, int kb, int hh, int j8) {
-  if (!chained) return 16 * kb + 8 * hh + j8;
-  const int j = 8 * hh + j8;
-  return 32 * (kb >> 1) + (j & 3) + 8 * (j >> 2) + 4 * (kb & 1);
-}
-
-// torch.nn.Linear weight [F, K] -> split fragments.  hidden: [F / 32][KB][hi | lo][64 lanes][8]; output layer (F <= 32): [KB][hi | lo][64 lanes][8]
-static std::vector<uint16_t> mlp32s_pack(const float* w, int F, int K, bool chained, bool output_layer) {
-  const int KB = (K + 15) / 16, Fp = output_layer ? 32 : (F + 63) / 64 * 64;
-  std::vector<uint16_t> out((size_t)Fp * KB * 16 * 2, 0);
-  for (int f = 0; f < F; ++f)
-    for (int kb = 0; kb < KB; ++kb)
-      for (int hh = 0; hh < 2; ++hh)
-        for (int j8 = 0; j8 < 8; ++j8) {
-          const int k = mlp32s_feature_of_slot(chained, kb, hh, j8);
-          if (k >= K) continue;
-          const float v = w[(size_t)f * K + k] * MLP32S_SW;
-          const uint16_t hi = f32_to_f16_rne(v), lo = f32_to_f16_rne(v - f16_to_f32(hi));
-          const int lane = hh * 32 + (f & 31);
-          size_t frag_hi;
-          if (output_layer) frag_hi = ((size_t)kb * 2) * 64 + lane;
-          else frag_hi = (((size_t)(f >> 5) * KB + kb) * 2) * 64 + lane;
-          out[frag_hi * 8 + j8] = hi;
-          out[(frag_hi + 64) * 8 + j8] = lo;
-        }
-  return out;
 }

@@ -1,16 +1,15 @@
 """The backward pass's yardstick (tests/gradient_check.py) on the host: a numpy float32 twin of sigmaenv_grad.inc -- the same formulas, the same tile- and
 range-ordered sums, every product rounded separately -- passes both layers of the criterion, the planted defects fail it; the row partition is what the header
-states; the transposed packed form of the weights (load_exact_t_src) is held word for word across its packers.  No GPU needed."""
+states; the transposed packed form of the weights (sigmaenv_pack.h) is held word for word to its reference.  No GPU needed."""
 import copy
 import os
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
 import gradient_check as gc
+import host_program
 from sigmarl_amd import capi
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -187,7 +186,16 @@ def test_grad_entry_points_are_declared_and_bound():
     assert '#include "sigmaenv_grad.inc"' in open(os.path.join(CSRC, "sigmaenv.hip")).read()
 
 
-MAIN = r"""
+PROGRAM = r"""
+#include <cmath>
+#include <cstdint>
+#include <cstdio>
+#include <cstring>
+#include <vector>
+#define SIGMA_HD static inline
+#include "sigmaenv_pack.h"
+#include "weight_pack_reference.h"
+
 static long bad = 0;
 static void same(const char* what, int F, int K, const std::vector<float>& a, const std::vector<float>& b) {
   if (a.size() != b.size()) { printf("SIZE %s F=%d K=%d: %zu against %zu\n", what, F, K, a.size(), b.size()); ++bad; return; }
@@ -204,18 +212,20 @@ int main() {
       for (auto& v : w) { x = x * 1664525u + 1013904223u; v = (float)(x >> 8) / 8388608.0f - 1.0f; }
       w[0] = -0.0f; w[w.size() - 1] = 1e-40f; w[w.size() / 2] = NAN;
       for (int f = 0; f < F; ++f) for (int k = 0; k < K; ++k) wT[(size_t)k * F + f] = w[(size_t)f * K + k];
-      /* 1: the host packer of sigmaenv_mlp32_create (its text, from sigmaenv_grad.inc) */
-      const std::vector<float> a = mlp32_pack_transposed(w.data(), F, K);
-      /* 2: the loop of the device pack kernel, one destination slot at a time */
+      /* 1: the reference scatter by (f, k), written from the layout */
+      const std::vector<float> a = ref::exact_t_pack_ref(w.data(), F, K);
+      /* 2: the product's per-slot function, as sigmaenv_mlp32_create and the device pack kernel call it, one destination slot at a time */
       std::vector<float> b((size_t)load_exact_t_slots(F, K), 7.0f);
+      for (int d = 0; d < (int)b.size(); ++d) pack_mlp32_t_slot(w.data(), b.data(), F, K, d);
+      /* every weight lands in exactly one slot */
       std::vector<int> seen((size_t)F * K, 0);
-      for (int d = 0; d < (int)b.size(); ++d) { const int s = load_exact_t_src(F, K, d); if (s >= (int)seen.size()) { ++bad; continue; } b[d] = s >= 0 ? w[s] : 0.0f; if (s >= 0) ++seen[s]; }
+      for (int d = 0; d < (int)b.size(); ++d) { const int s = load_exact_t_src(F, K, d); if (s >= (int)seen.size()) { ++bad; continue; } if (s >= 0) ++seen[s]; }
       for (int c : seen) if (c != 1) { if (++bad <= 20) printf("COVER F=%d K=%d: a weight packed %d times\n", F, K, c); }
-      /* 3: the forward's exact form (load_exact_src, held to sigmaenv_mlp32_create's loop by tests/test_weight_load_host.py) of the transposed matrix [K][F] */
+      /* 3: the forward's exact form (held to the reference by tests/test_weight_load_host.py) of the transposed matrix [K][F] */
       std::vector<float> c((size_t)load_exact_slots(K, F));
       for (int d = 0; d < (int)c.size(); ++d) { const int s = load_exact_src(K, F, d); c[d] = s >= 0 ? wT[s] : 0.0f; }
-      same("create-vs-kernel", F, K, a, b);
-      same("transposed-vs-exact-of-transpose", F, K, a, c);
+      same("reference-vs-product", F, K, a, b);
+      same("transposed-vs-exact-of-transpose", F, K, b, c);
       slots += (long)a.size();
     }
   printf("%ld slots compared: %ld mismatches\n", slots, bad);
@@ -224,27 +234,10 @@ int main() {
 """
 
 
-@pytest.mark.skipif(shutil.which("g++") is None and shutil.which("c++") is None, reason="no host C++ compiler")
+@pytest.mark.skipif(host_program.compiler() is None, reason="no host C++ compiler")
 def test_transposed_form_packers_agree_word_for_word(tmp_path):
-    """F in {256, 32, 9, 8, 7, 4, 2, 1} x K in {256, 35, 32, 7}: the host packer of sigmaenv_mlp32_create (text taken from sigmaenv_grad.inc), the loop of the device
-    pack kernel over load_exact_t_src, and the forward's exact form of the transposed matrix give the same words in every slot, padding (zeros) included; every
-    weight lands in exactly one slot.  -0, a subnormal and a NaN are planted (words are compared)."""
-    grad = open(os.path.join(CSRC, "sigmaenv_grad.inc")).read()
-    a = grad.index("static std::vector<float> mlp32_pack_transposed(")
-    packer = grad[a:grad.index("\n}\n", a) + 3]
-    assert "load_exact_t_src" in packer and "hip" not in packer
-    kernel = grad[grad.index("sigmaenv_load_mlp32_t_kernel("):]
-    assert "const int s = load_exact_t_src(F, K, i);" in kernel and "tw[i] = s >= 0 ? w[s] : 0.0f;" in kernel  # (the loop restated in MAIN)
-    src = tmp_path / "t_check.cpp"
-    src.write_text("#include <cmath>\n#include <cstdint>\n#include <cstdio>\n#include <cstring>\n#include <vector>\n#define MLP32S_SW 256.0f\n"
-                   "#define SIGMA_HD static inline\n#define SIGMAENV_LOAD_MAPS_ONLY\n#include \"sigmaenv_load.inc\"\n" + packer + MAIN)
-    cxx = shutil.which("g++") or shutil.which("c++")
-    exe = tmp_path / "t_check"
-    base = [cxx, "-std=c++17", "-O1", "-I", CSRC, str(src), "-o", str(exe)]
-    san = subprocess.run(base + ["-fsanitize=address,undefined", "-fno-sanitize-recover=all"], capture_output=True, text=True)
-    if san.returncode != 0:
-        subprocess.check_call(base)
-    run = subprocess.run([str(exe)], capture_output=True, text=True)
-    print(run.stdout[-3000:], run.stderr[-3000:])
-    assert run.returncode == 0, run.stdout[-2000:] + run.stderr[-2000:]
-    assert ": 0 mismatches" in run.stdout
+    """F in {256, 32, 9, 8, 7, 4, 2, 1} x K in {256, 35, 32, 7}: the per-slot function of sigmaenv_pack.h that sigmaenv_mlp32_create loops over on the host and the
+    device pack kernel on the device, the reference scatter by (f, k) of tests/weight_pack_reference.h, and the forward's exact form of the transposed matrix give the
+    same words in every slot, padding (zeros) included; every weight lands in exactly one slot.  -0, a subnormal and a NaN are planted (words are compared)."""
+    out = host_program.build_and_run(tmp_path, "t_check", PROGRAM)
+    assert ": 0 mismatches" in out

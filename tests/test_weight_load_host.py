@@ -1,15 +1,15 @@
 """Host parts of the on-device weight refresh (sigmaenv_mlp32_load_device / sigmaenv_actor_load_device, sigmarl_amd/csrc/sigmaenv_load.inc; Mlp32.load / Actor.load):
-the ABI, the refusals that happen before any device call, and the index maps + roundings of the pack kernels -- the `__host__ __device__` functions the kernels loop
-over -- against the host packers of sigmaenv_mlp32_create / sigmaenv_actor_create, word for word, in a stand-alone host program.  No GPU needed."""
+the ABI, the refusals that happen before any device call, and the packed forms of sigmarl_amd/csrc/sigmaenv_pack.h -- the per-slot functions, index maps and roundings
+that *_create loops over on the host and the pack kernels on the device -- against the frozen packers of tests/weight_pack_reference.h, word for word, in a
+stand-alone host program.  No GPU needed."""
 import os
 import re
-import shutil
-import subprocess
 import types
 
 import pytest
 import torch
 
+import host_program
 from sigmarl_amd import capi
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -24,7 +24,7 @@ def test_load_entry_points_are_declared_and_bound():
         assert f"int sigmaenv_{name}(sigmaenv_t* h, " in header
     mk = open(os.path.join(CSRC, "Makefile")).read()
     src = [ln for ln in mk.splitlines() if ln.startswith("SRC = ")][0].split()
-    assert "sigmaenv_load.inc" in src  # sigmaenv_build_id() covers the pack kernels
+    assert "sigmaenv_load.inc" in src and "sigmaenv_pack.h" in src  # sigmaenv_build_id() covers the pack kernels and the packed forms they write
     assert '#include "sigmaenv_load.inc"' in open(os.path.join(CSRC, "sigmaenv.hip")).read()
 
 
@@ -85,12 +85,16 @@ def test_load_refuses_bad_sources_before_any_device_call(which):
         load(wrong_dtype)
 
 
-def _between(text, start, end):
-    a = text.index(start)
-    return text[a:text.index(end, a)]
+PROGRAM = r"""
+#include <cmath>
+#include <cstdint>
+#include <cstdio>
+#include <cstring>
+#include <vector>
+#define SIGMA_HD static inline
+#include "sigmaenv_pack.h"
+#include "weight_pack_reference.h"
 
-
-MAIN = r"""
 static std::vector<float> special_values(bool huge) {
   std::vector<float> s = {0.0f, -0.0f,
     1e-7f, -3e-8f, 2.0e-9f, -2.0e-9f, 1e-10f,                       /* times 2^8: fp16 subnormals, and below the smallest one */
@@ -126,6 +130,60 @@ template <class T> static void compare(const char* form, int F, int K, int chain
     if (++bad <= 20) printf("MISMATCH %s F=%d K=%d chained=%d slot %zu: %x, the packer has %x\n", form, F, K, chained, i, a, b);
   }
 }
+static std::vector<float> in_range_weights(int F, int K, uint32_t seed) {  /* make_weights with every value outside the split range replaced */
+  std::vector<float> w = make_weights(F, K, false, seed);
+  for (auto& v : w) if (!(std::fabs(v) < 255.0f)) v = 0.5f;
+  return w;
+}
+static bool range_ref(const std::vector<float>& w) {  /* the predicate as sigmaenv_mlp32_create wrote it, OR-ed over a layer's weights */
+  bool out = false;
+  for (float v : w) if (!(std::fabs(v) < 255.0f)) out = true;
+  return out;
+}
+/* one layer (K -> F; chained: not the input layer) through the product's shape function and per-slot function, every lane index, against the reference packers;
+   returns the range flag OR-ed over the lanes */
+static bool mlp32_layer(int F, int K, int chained, bool output_layer, bool split_fits, const std::vector<float>& w, const std::vector<float>& b, long& slots) {
+  int32_t dims[4] = {1, 1, 1, 1};
+  dims[chained] = K; dims[chained + 1] = F;
+  Mlp32Layer a = pack_mlp32_layer(dims, chained, chained + (output_layer ? 1 : 2), split_fits);
+  if (a.F != F || a.K != K || a.chained != chained || (a.output_layer != 0) != output_layer) { printf("SHAPE F=%d K=%d chained=%d\n", F, K, chained); ++bad; }
+  const float* wp[1] = {w.data()};
+  const float* bp[1] = {b.data()};
+  std::vector<float> ref_w, ref_b, ref_sb((size_t)(output_layer ? 32 : 256), 0.0f);
+  ref::exact_pack_ref(wp, bp, 0, K, F, ref_w, ref_b);
+  const std::vector<uint16_t> ref_s = ref::mlp32s_pack(w.data(), F, K, chained != 0, output_layer);
+  for (int f = 0; f < F; ++f) ref_sb[f] = b[f] * (chained ? 65536.0f : 4096.0f);  /* 2^8 times the scale of the layer's inputs: 2^4 for the input rows, 2^8 behind a tanh */
+  std::vector<float> ew((size_t)a.n_exact, 7.0f), eb((size_t)a.fp_exact, 7.0f), sb(ref_sb.size(), 7.0f);
+  std::vector<uint16_t> sw(ref_s.size(), (uint16_t)0xDEAD);
+  a.w = w.data(); a.b = b.data(); a.ew = ew.data(); a.eb = eb.data(); a.sw = sw.data(); a.sb = sb.data();
+  if (split_fits && ((size_t)a.n_pairs * 2 != sw.size() || (size_t)a.fp_split != sb.size())) { printf("SIZE split F=%d K=%d: %d pairs, %d biases\n", F, K, a.n_pairs, a.fp_split); ++bad; return false; }
+  if (!split_fits && (a.n_pairs != 0 || a.fp_split != 0)) { printf("SIZE unsplit F=%d K=%d\n", F, K); ++bad; return false; }
+  bool flag = false;
+  for (int i = 0, n = pack_mlp32_lanes(a); i < n; ++i) flag |= pack_mlp32_slot(a, i);
+  compare("exact", F, K, chained, ew, ref_w);
+  compare("exact bias", F, K, chained, eb, ref_b);
+  if (split_fits) {
+    compare("split", F, K, chained, sw, ref_s);
+    compare("split bias", F, K, chained, sb, ref_sb);
+  } else {  /* a network that is exact-only by its width: its split form is not touched */
+    compare("unsplit", F, K, chained, sw, std::vector<uint16_t>(sw.size(), (uint16_t)0xDEAD));
+    compare("unsplit bias", F, K, chained, sb, std::vector<float>(sb.size(), 7.0f));
+  }
+  slots += (long)(ew.size() + eb.size() + sw.size() + sb.size());
+  return flag;
+}
+static void actor_layer(ActorLayer a, const std::vector<float>& w, const std::vector<float>& b, long& slots) {
+  const std::vector<uint16_t> ref = ref::pack_layer(w.data(), a.F, a.K, a.chained != 0);
+  std::vector<float> ref_b((size_t)a.nb, 0.0f);
+  for (int f = 0; f < a.F; ++f) ref_b[f] = b[f];
+  std::vector<uint16_t> pw((size_t)a.n_slots, (uint16_t)0xDEAD);
+  std::vector<float> pb((size_t)a.nb, 7.0f);
+  a.w = w.data(); a.b = b.data(); a.pw = pw.data(); a.pb = pb.data();
+  for (int i = 0; i < a.n_slots + a.nb; ++i) pack_actor_slot(a, i);
+  compare("bf16", a.F, a.K, a.chained, pw, ref);
+  compare("bf16 bias", a.F, a.K, a.chained, pb, ref_b);
+  slots += (long)(pw.size() + pb.size());
+}
 int main() {
   const int Ks[] = {1, 7, 32, 35, 256, 512, 595}, Fs[] = {256, 4, 2, 1};
   long slots = 0;
@@ -133,43 +191,38 @@ int main() {
   for (int K : Ks)
     for (int F : Fs) {
       const bool output_layer = F != 256;
-      { /* exact form: the loop of sigmaenv_mlp32_create */
-        const std::vector<float> w = make_weights(F, K, true, seed++), b = make_weights(F, 1, true, seed++);
-        const float* wp[1] = {w.data()};
-        const float* bp[1] = {b.data()};
-        std::vector<float> ref_w, ref_b;
-        exact_pack_ref(wp, bp, 0, K, F, ref_w, ref_b);
-        std::vector<float> got((size_t)load_exact_slots(F, K));
-        for (int d = 0; d < (int)got.size(); ++d) { const int s = load_exact_src(F, K, d); got[d] = s >= 0 ? w[s] : 0.0f; }
-        compare("exact", F, K, 0, got, ref_w);
-        slots += (long)got.size();
-      }
       for (int chained = 0; chained < 2; ++chained) {
-        { /* split form: mlp32s_pack */
-          const std::vector<float> w = make_weights(F, K, false, seed++);
-          const std::vector<uint16_t> ref = mlp32s_pack(w.data(), F, K, chained != 0, output_layer);
-          std::vector<uint16_t> got((size_t)load_split_pairs(F, K, output_layer) * 2, (uint16_t)0xDEAD);
-          for (int p = 0; p < load_split_pairs(F, K, output_layer); ++p) {
-            const int s = load_split_src(F, K, chained != 0, p), d = load_split_hi_slot(p);
-            uint16_t hi = 0, lo = 0;
-            if (s >= 0) load_split(w[s], hi, lo);
-            if (d < 0 || (size_t)d + 512 >= got.size()) { printf("RANGE split F=%d K=%d pair %d -> slot %d\n", F, K, p, d); ++bad; continue; }
-            got[d] = hi; got[d + 512] = lo;
+        { /* exact + split form and both bias vectors, with inf / NaN / 3e38 / 300 planted, then without; the range flag is the predicate OR-ed over the weights */
+          for (int huge = 1; huge >= 0; --huge) {
+            const std::vector<float> w = make_weights(F, K, huge != 0, seed++), b = make_weights(F, 1, true, seed++);
+            const bool flag = mlp32_layer(F, K, chained, output_layer, true, w, b, slots);
+            if (flag != range_ref(w) || (huge && w.size() >= 128 && !flag)) {  /* (a smaller matrix: the planted values overwrite one another) */ printf("RANGE F=%d K=%d chained=%d huge=%d: flag %d\n", F, K, chained, huge, (int)flag); ++bad; }
           }
-          compare("split", F, K, chained, got, ref);
-          slots += (long)got.size();
+          /* every weight inside the range: no flag; then a single NaN: flagged */
+          std::vector<float> w = in_range_weights(F, K, seed++);
+          const std::vector<float> b = make_weights(F, 1, false, seed++);
+          if (mlp32_layer(F, K, chained, output_layer, true, w, b, slots) || range_ref(w)) { printf("RANGE F=%d K=%d chained=%d: flagged inside the range\n", F, K, chained); ++bad; }
+          w[w.size() / 2] = NAN;
+          if (!mlp32_layer(F, K, chained, output_layer, true, w, b, slots) || !range_ref(w)) { printf("RANGE F=%d K=%d chained=%d: a single NaN is not flagged\n", F, K, chained); ++bad; }
+          if (K == 595) mlp32_layer(F, K, chained, output_layer, false, w, b, slots);
         }
-        { /* bf16 form: pack_layer */
-          const std::vector<float> w = make_weights(F, K, true, seed++);
-          const std::vector<uint16_t> ref = pack_layer(w.data(), F, K, chained != 0);
-          std::vector<uint16_t> got((size_t)load_bf16_slots(F, K));
-          for (int d = 0; d < (int)got.size(); ++d) { const int s = load_bf16_src(F, K, chained != 0, d); got[d] = s >= 0 ? load_bf16_rne(w[s]) : (uint16_t)0; }
-          compare("bf16", F, K, chained, got, ref);
-          slots += (long)got.size();
+        { /* bf16 form: pack_layer; biases padded to whole tiles of 16 */
+          ActorLayer a{};
+          a.F = F; a.K = K; a.chained = chained; a.n_slots = load_bf16_slots(F, K); a.nb = (F + 15) / 16 * 16;
+          actor_layer(a, make_weights(F, K, true, seed++), make_weights(F, 1, true, seed++), slots);
         }
       }
     }
-  /* the roundings alone on many bit patterns (every exponent, mantissa edges), and the range predicate as sigmaenv_mlp32_create writes it */
+  /* the actor's own four layers, shapes from the function sigmaenv_actor_create and sigmaenv_actor_load_device share */
+  for (int D = 8; D <= 32; D += 8)
+    for (int l = 0; l < 4; ++l) {
+      const ActorLayer a = pack_actor_layer(D, l);
+      if (a.K != (l == 0 ? D : 256) || a.F != (l == 3 ? 4 : 256) || a.nb != (l == 3 ? 16 : 256) || a.chained != (l > 0) || a.n_slots != load_bf16_slots(a.F, a.K)) {
+        printf("SHAPE actor D=%d layer %d\n", D, l); ++bad; continue;
+      }
+      actor_layer(a, make_weights(a.F, a.K, true, seed++), make_weights(a.F, 1, true, seed++), slots);
+    }
+  /* the roundings alone on many bit patterns (every exponent, mantissa edges), and the range predicate as sigmaenv_mlp32_create wrote it */
   long words = 0;
   for (uint32_t e = 0; e < 256; ++e)
     for (uint32_t sgn = 0; sgn < 2; ++sgn)
@@ -178,12 +231,12 @@ int main() {
         const uint32_t u = (sgn << 31) | (e << 23) | (mant & 0x7FFFFFu);
         float f; std::memcpy(&f, &u, 4);
         ++words;
-        if (load_f16_rne(f) != f32_to_f16_rne(f)) { if (++bad <= 20) printf("MISMATCH f16 of %08x: %x, the packer has %x\n", u, load_f16_rne(f), f32_to_f16_rne(f)); }
-        if (load_bf16_rne(f) != f32_to_bf16_rne(f)) { if (++bad <= 20) printf("MISMATCH bf16 of %08x\n", u); }
+        if (load_f16_rne(f) != ref::f32_to_f16_rne(f)) { if (++bad <= 20) printf("MISMATCH f16 of %08x: %x, the packer has %x\n", u, load_f16_rne(f), ref::f32_to_f16_rne(f)); }
+        if (load_bf16_rne(f) != ref::f32_to_bf16_rne(f)) { if (++bad <= 20) printf("MISMATCH bf16 of %08x\n", u); }
         if (load_out_of_range(f) != !(std::fabs(f) < 255.0f)) { if (++bad <= 20) printf("MISMATCH range of %08x\n", u); }
       }
   for (uint32_t hv = 0; hv < 65536; ++hv) {
-    const float a = load_f16_to_f32((uint16_t)hv), b = f16_to_f32((uint16_t)hv);
+    const float a = load_f16_to_f32((uint16_t)hv), b = ref::f16_to_f32((uint16_t)hv);
     if (std::memcmp(&a, &b, 4) != 0) { if (++bad <= 20) printf("MISMATCH f16 -> f32 of %04x\n", hv); }
   }
   printf("%ld slots, %ld bit patterns compared: %ld mismatches, %ld zeros of the other sign\n", slots, words, bad, zero_sign);
@@ -192,36 +245,31 @@ int main() {
 """
 
 
-@pytest.mark.skipif(shutil.which("g++") is None and shutil.which("c++") is None, reason="no host C++ compiler")
+@pytest.mark.skipif(host_program.compiler() is None, reason="no host C++ compiler")
 def test_index_maps_and_roundings_equal_the_host_packers(tmp_path):
     """Every destination slot of every form, K in {1, 7, 32, 35, 256, 512, 595} x F in {256, 4, 2, 1} (F < 256: the output layer's layout), chained and unchained:
-    the map + conversion functions of sigmaenv_load.inc give the words of the host packers -- whose own text (mlp32s_pack with its roundings, pack_layer, the loop
-    of sigmaenv_mlp32_create) is taken from the library's sources, so the program holds no GPU code.  Weights: the default initialisation range with +-0, values
-    whose 2^8-fold is an fp16 subnormal (or below), exact fp16 / bf16 ties, 254.999, fp32 subnormals and (exact, bf16) 3e38, 300, inf, NaN planted.  A zero of the
-    other sign is reported slot by slot and fails like any other difference: there is none.  Built with AddressSanitizer + UBSan where the compiler has them."""
-    mlp32 = open(os.path.join(CSRC, "sigmaenv_mlp32.inc")).read()
-    mlp32s = open(os.path.join(CSRC, "sigmaenv_mlp32s.inc")).read()
-    actor = open(os.path.join(CSRC, "sigmaenv_actor.inc")).read()
-    scales = "\n".join(re.findall(r"^#define MLP32S_S(?:W|X|X0) .*$", mlp32s, flags=re.M))
-    assert scales.count("#define") == 3
-    split_host = mlp32s[mlp32s.index("static uint16_t f32_to_f16_rne(float f) {"):]
-    assert "mlp32s_pack(" in split_host and "__global__" not in split_host
-    bf16_host = _between(actor, "static uint16_t f32_to_bf16_rne(float f) {", 'extern "C" void sigmaenv_actor_destroy')
-    assert "pack_layer(" in bf16_host
-    exact_loop = _between(mlp32, "    const int Kp = (K + 7) / 8 * 8, Fp = (F + 31) / 32 * 32, KQ = Kp / 8;", "    void *dw = nullptr, *db = nullptr;")
-    assert "wt[" in exact_loop and "hip" not in exact_loop
-    src = tmp_path / "maps_check.cpp"
-    src.write_text("#include <cmath>\n#include <cstdint>\n#include <cstdio>\n#include <cstring>\n#include <vector>\n" + scales + "\n" + split_host + "\n" + bf16_host
-                   + "\nstatic void exact_pack_ref(const float* const* weights, const float* const* biases, int l, int K, int F, std::vector<float>& wt_out, "
-                   "std::vector<float>& bp_out) {\n" + exact_loop + "    wt_out = wt; bp_out = bp;\n}\n"
-                   "#define SIGMA_HD static inline\n#define SIGMAENV_LOAD_MAPS_ONLY\n#include \"sigmaenv_load.inc\"\n" + MAIN)
-    cxx = shutil.which("g++") or shutil.which("c++")
-    exe = tmp_path / "maps_check"
-    base = [cxx, "-std=c++17", "-O1", "-ffp-contract=off", "-I", CSRC, str(src), "-o", str(exe)]
-    san = subprocess.run(base + ["-fsanitize=address,undefined", "-fno-sanitize-recover=all"], capture_output=True, text=True)
-    if san.returncode != 0:  # (a compiler without the sanitizer runtimes: the comparison itself does not need them)
-        subprocess.check_call(base)
-    run = subprocess.run([str(exe)], capture_output=True, text=True)
-    print(run.stdout[-4000:], run.stderr[-4000:])
-    assert run.returncode == 0, run.stdout[-2000:] + run.stderr[-2000:]
-    assert " 0 mismatches, 0 zeros of the other sign" in run.stdout
+    the program includes sigmaenv_pack.h alone of the library, builds each layer's descriptor with the shape functions *_create and *_load_device use, runs the
+    per-slot function they loop over across every lane index into buffers pre-filled with 0xDEAD / 7.0f, and compares exact weights, split words, bf16 words and all
+    three bias vectors (padding and the split form's bias scale included) with the frozen packers of tests/weight_pack_reference.h.  The range flag returned over a
+    layer is !(|w| < 255) OR-ed over its weights: with 3e38, 300, inf, NaN planted, without them, with every weight inside the range (no flag), and with a single NaN.
+    Weights: the default initialisation range with +-0, values whose 2^8-fold is an fp16 subnormal (or below), exact fp16 / bf16 ties, 254.999, fp32 subnormals.
+    Then 2 M bit patterns through each rounding and all 65536 fp16 patterns.  A zero of the other sign is reported slot by slot and fails like any other
+    difference: there is none.  Built with AddressSanitizer + UBSan where the compiler has them."""
+    out = host_program.build_and_run(tmp_path, "maps_check", PROGRAM)
+    assert " 0 mismatches, 0 zeros of the other sign" in out
+
+
+def test_each_layout_map_is_stated_in_the_pack_header_only():
+    """The destination-slot maps are defined AND used in sigmaenv_pack.h alone: every other source of the library reaches a packed form through the header's per-slot
+    functions, and the scatter packers the header replaced have not come back."""
+    for name in sorted(os.listdir(CSRC)):
+        if name == "sigmaenv_pack.h" or not name.endswith((".h", ".inc", ".hip")):
+            continue
+        text = open(os.path.join(CSRC, name)).read()
+        for word in ("load_exact_src", "load_split_src", "load_bf16_src", "load_exact_t_src",
+                     "f32_to_f16_rne", "f16_to_f32", "mlp32s_feature_of_slot", "mlp32s_pack", "f32_to_bf16_rne", "pack_layer", "mlp32_pack_transposed", "mlp32_grad_create"):
+            assert not re.search(r"\b" + word + r"\b", text), f"{name} names {word}"
+    pack = open(os.path.join(CSRC, "sigmaenv_pack.h")).read()
+    for word in ("load_exact_src", "load_split_src", "load_bf16_src", "load_exact_t_src"):
+        assert len(re.findall(r"SIGMA_HD int " + word + r"\(", pack)) == 1
+    assert "hip" not in pack.replace("sigmaenv.hip", "") and pack.count("#include") == 1  # plain C++: <stdint.h> and nothing of the library
