@@ -12,7 +12,7 @@ failing an fp32 forward in another summation order.  So a kernel passes when its
 shows that, and which defects the criterion catches).
 
 bf16 kernel (``emulated_bf16``): a restatement of what it computes -- bf16 inputs, weights and hidden activations, fp32 accumulation -- in numpy; the tests
-hold the kernel to it with their own tolerances (the matrix cores' summation order differs)."""
+hold the kernel to it with their own tolerances (the matrix cores' summation order differs); tests/bf16_actor_check.py holds it bit for bit where that order cannot matter."""
 from __future__ import annotations
 
 import atexit

@@ -155,8 +155,8 @@ REGIME_NEEDS = {1: dict(inside=16), 8: dict(tanh_is_one=16, shortcut_jacobian=16
 def test_actor_head_in_every_regime(envs, path, last):
     """257 x 16 rows.  Every row's action and log-probability against fp64; the regime the case is meant for holds at least 16 values; on the fp32 paths the scale
     against scale_of(raw) of the fp64 network within the network criterion's bound on raw (|d scale / d raw| <= 1) plus one float32 rounding.  The bf16 path's
-    scale is only held to >= 0.01 here (its raw output carries the bf16 network's error): the scale FORMULA is covered by the fp32 paths, which run the same
-    actor_distribution."""
+    scale is only held to >= 0.01 HERE (on these dense weights its raw output carries the bf16 network's error, which has no derived bound); it is held to
+    scale_of(raw) with a raw bound of 0 in tests/test_gpu_bf16_actor_exact.py, on a network and on rows where the bf16 kernel's raw output is exact."""
     base, seed, counter, bounds = PATH_CASES[path]
     env, mlp, x = envs(257, 16, base), ph.regime_net(last), ph.regime_input(257 * 16)
     actor = _actor(mlp, bounds, path)
