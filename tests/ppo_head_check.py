@@ -42,6 +42,9 @@ ENTROPY_DRAWS = (7300, 7301)
 BIAS, LOG_SQRT_2PI, LOG2 = phc.BIAS, phc.LOG_SQRT_2PI, phc.LOG2
 RESULT = ("loss_objective", "loss_entropy", "loss_critic", "entropy", "clip_fraction", "kl_approx")
 DEFECTS = ("ratio_clip", "tie_clamped_neg", "no_dsigma_draw", "entropy_no_sigma_grad", "smooth_l1_half", "critic_mean", "index_on_out")
+# faults of the final sum (``ordered_sum``): they show only past 64 (first_64: the workgroups from 64 on are never read) or 32 (stride_32: lane k also adds the
+# workgroups k + 32, k + 96, .., which belong to lane k + 32) workgroups, so they are planted at sizes of their own (tests/test_ppo_head_check.py)
+SUM_DEFECTS = ("first_64", "stride_32")
 
 
 def clip_bounds(eps):
@@ -58,9 +61,9 @@ def wave_sum(v):
     return v[..., 0]
 
 
-def ordered_sum(t):
+def ordered_sum(t, defect=None):
     """The device's sum of one value per row, in t's dtype: rows padded with zeros to workgroups of 256, per wavefront the butterfly, per workgroup
-    ((w0 + w1) + w2) + w3, then one wavefront -- lane k the chain over the workgroups k, k + 64, .. from 0 -- and the butterfly."""
+    ((w0 + w1) + w2) + w3, then one wavefront -- lane k the chain over the workgroups k, k + 64, .. from 0 -- and the butterfly.  ``defect``: one of SUM_DEFECTS."""
     t = np.asarray(t).reshape(-1)
     dt = t.dtype.type
     G = -(-t.size // 256)
@@ -73,7 +76,13 @@ def ordered_sum(t):
     q[:G] = g
     q = q.reshape(J, 64)
     v = np.zeros(64, t.dtype)
-    for j in range(J):
+    if defect == "stride_32":  # lane k: the workgroups k, k + 32, k + 64, ..
+        h = np.zeros(2 * J * 64 + 32, t.dtype)
+        h[:G] = g
+        for j in range(2 * J):
+            v = (v + h[32 * j:32 * j + 64]).astype(dt)
+        return dt(wave_sum(v))
+    for j in range(1 if defect == "first_64" else J):
         v = (v + q[j]).astype(dt)
     return dt(wave_sum(v))
 
@@ -179,7 +188,7 @@ def head(case, dtype=np.float64, defect=None):
         for n in range(N):
             s = (s + de[:, n]).astype(f)
         dout_c = cc_inv * s
-        S = {k: ordered_sum(t.astype(f)) for k, t in (("obj", np.minimum(g1, g2)), ("lps", lps), ("sl1", sl1), ("clip", clipped), ("kl", -lw))}
+        S = {k: ordered_sum(t.astype(f), defect if defect in SUM_DEFECTS else None) for k, t in (("obj", np.minimum(g1, g2)), ("lps", lps), ("sl1", sl1), ("clip", clipped), ("kl", -lw))}
     else:
         dout_c = cc_inv * de.sum(1)
         S = {k: float(t.sum()) for k, t in (("obj", np.minimum(g1, g2)), ("lps", lps), ("sl1", sl1), ("clip", clipped), ("kl", -lw))}
@@ -189,7 +198,7 @@ def head(case, dtype=np.float64, defect=None):
     result = dict(loss_objective=-(f(S["obj"]) * inv), loss_entropy=-(f(ce) * entropy), loss_critic=f(cc) * (f(S["sl1"]) * inv), entropy=entropy,
                   clip_fraction=f(S["clip"]) * inv, kl_approx=f(S["kl"]) * inv)
     r = dict(dout_actor=dout_a, dout_critic=dout_c, result=result, terms=dict(obj=np.minimum(g1, g2), lps=lps, sl1=sl1, lw=lw), lw=lw, g1=g1, g2=g2, A=A, e=e,
-             sigma=sig, y=y, dlw_on=on, lo=lo, hi=hi, rows=R, inv=float(inv), ce=float(ce), cc=float(cc))
+             sigma=sig, y=y, dlw_on=on, lo=lo, hi=hi, rows=R, inv=float(inv), ce=float(ce), cc=float(cc), clipped=int((cl != lw).sum()))
     if f != np.float64:
         return r
     # ---- the magnitudes (float64 reference only), in units of one float32 rounding
@@ -265,21 +274,50 @@ def calibration():
     return _CALIBRATION
 
 
+def constants_in_force(case, ref):
+    """the constants ``compare`` holds ``case`` to: the twin's over its rows, and the calibration case's for fewer than FULL_ROWS rows"""
+    c = constants(case, ref)
+    if ref["rows"] < FULL_ROWS:
+        c = {k: max(v, calibration()[k]) for k, v in c.items()}
+    return c
+
+
+def in_the_band(ref, c):
+    """[M, N] bool: the rows whose float64 lw lies within its own bound of a clip bound (module docstring, Branches)"""
+    tol = MARGIN * c["lw"] * U23 * ref["S_terms"]["lw"]
+    return (np.abs(ref["lw"] - float(ref["lo"])) <= tol) | (np.abs(ref["lw"] - float(ref["hi"])) <= tol)
+
+
+def clear_of_the_band(case, shift=0.05):
+    """``case`` with every row of the branch band moved out of it, away from zero, through its ``sample_log_prob`` (a frame picked twice has one record and the same
+    outputs in both slots: its slots move together).  Returns (case, reference, constants, the rows moved); the caller asserts that ``in_the_band`` is empty.  With no
+    row in the band a kernel that meets the criterion of ``lw`` clips exactly the rows the float64 reference clips."""
+    case = dict(case, sample_log_prob=np.array(case["sample_log_prob"], np.float32))
+    moved = 0
+    for _ in range(4):
+        ref = head(case)
+        c = constants_in_force(case, ref)
+        amb = in_the_band(ref, c)
+        if not amb.any():
+            break
+        for m, n in np.argwhere(amb):
+            case["sample_log_prob"][case["index"][m], n] -= np.float32(math.copysign(shift, ref["lw"][m, n]))
+        moved += int(amb.sum())
+    return case, ref, c, moved
+
+
 def compare(dout_actor, dout_critic, result, case, what=""):
     """The criterion of the module docstring: the device's (or a twin's) outputs against ``head(case, float64)``.  ``result``: the six scalars in RESULT order.
     Returns the figures; ``ok`` says whether everything passed."""
     ref = head(case)
-    c = constants(case, ref)
-    if ref["rows"] < FULL_ROWS:
-        c = {k: max(v, calibration()[k]) for k, v in c.items()}
+    c = constants_in_force(case, ref)
     M, N = ref["lw"].shape
     r = dict(what=what, rows=ref["rows"], c=c)
     da = np.asarray(dout_actor, np.float64).reshape(M, N, 4)
     ck = np.array([c["dloc"], c["dloc"], c["draw"], c["draw"]])
     main, alt = _ratio(da, ref["dout_actor"], ref["S_dout_actor"]) / ck, _ratio(da, ref["alt_dout_actor"], ref["S_alt_dout_actor"]) / ck
     # rows whose lw is within its own bound of a clip bound may take either side of the branch
-    tol = MARGIN * c["lw"] * U23 * ref["S_terms"]["lw"]
-    amb = (np.abs(ref["lw"] - float(ref["lo"])) <= tol) | (np.abs(ref["lw"] - float(ref["hi"])) <= tol)
+    amb = in_the_band(ref, c)
     use = np.where(amb[..., None], np.minimum(main, alt), main)
     r["ambiguous_rows"] = int(amb.sum())
     r["dloc"], r["draw"] = float(use[..., :2].max()), float(use[..., 2:].max())
@@ -375,6 +413,32 @@ def synthetic_case(M=512, N=3, F=700, seed=1, entropy_coeff=0.01, critic_coeff=1
     rec = records_for(out, value, index, F, N, seed + 1, low, high)
     return dict(out=out, value=value, index=index, low=np.asarray(low, np.float32), high=np.asarray(high, np.float32), clip_epsilon=clip_epsilon,
                 entropy_coeff=entropy_coeff, critic_coeff=critic_coeff, seed=1234567, counter=counter, **rec)
+
+
+# ---- past 64 workgroups: the second and third term of a lane's chain in the final sum ---------------------------------------------------------------
+BIG_N = 16
+BIG_M = {1024: (16384, 64, 1), 1025: (16400, 65, 2), 2049: (32784, 129, 3)}  # M -> (rows, workgroups, the longest chain of a lane: lane 0's)
+BIG_PATTERNS = ("duplicates", "permutation")
+_BIG = {}
+
+
+def big_case(M, pattern):
+    """The case of M frames x BIG_N agents over F = M + 3 frames, its index a sample with duplicates or a cut of a permutation, cleared of the branch band:
+    (case, float64 reference, constants, rows moved out of the band).  Made once per (M, pattern)."""
+    if (M, pattern) not in _BIG:
+        F = M + 3
+        g = np.random.default_rng(1000 * M + BIG_PATTERNS.index(pattern))
+        idx = (g.integers(0, F, M) if pattern == "duplicates" else g.permutation(F)[:M]).astype(np.int32)
+        if pattern == "duplicates":
+            idx[-1] = idx[0]
+        _BIG[(M, pattern)] = clear_of_the_band(synthetic_case(N=BIG_N, F=F, seed=40 + M, index=idx, floor_rows=2))
+    return _BIG[(M, pattern)]
+
+
+def exact_clip_fraction(ref):
+    """clip_fraction as the device forms it when it clips the rows of the float64 reference: the flags are 0 or 1, their sum is exact in any order, then one product
+    with the float32 1 / R"""
+    return np.float32(ref["clipped"]) * (np.float32(1.0) / np.float32(ref["rows"]))
 
 
 # ---- the same formulas in torch (autograd: the host cross-check of the analytical gradients, and the whole-chain reference of the GPU test) --------------

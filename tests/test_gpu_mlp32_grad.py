@@ -1,7 +1,10 @@
 """The fp32 network differentiated on the device (sigmaenv_mlp32_forward_save / sigmaenv_mlp32_backward, Mlp32.apply / Actor.apply / Critic.apply): every case is
 held to both layers of tests/gradient_check.py -- the backward given the device's own saved activations within a derived count of roundings, the saved activations
 and the gradients end to end against float64 autograd with the fp32 autograd's own error as the yardstick --, dense rows and the same rows inside a record give the
-same bits, as do two runs, a loaded and a fresh handle, and the C entry point and ``loss.backward()``."""
+same bits, as do two runs, a loaded and a fresh handle, and the C entry point and ``loss.backward()``.  At the four row counts where the dW kernel's row partition
+changes (THRESHOLDS: 16384 .. 20481 rows, what a minibatch of the workload has) the actor and the critic are held to both layers again, and -- the bound there being no
+more than a third of what one lost row moves -- exactly: one-row probes whose dW / db are a single product (gc.check_one_row), an output-layer db that is an exact
+sum.  Every backward of this module runs on a workspace of exactly the floats it asks for, followed by guard words (c_grad)."""
 import ctypes as C
 
 import numpy as np
@@ -94,12 +97,17 @@ def in_record(x):
     return rec.cuda(), (3, rpb, W, nb, bstride)
 
 
-def c_grad(env, net, base, spec, dout):
-    """The C entry points on rows ``spec`` of ``base``: (y, acts, grad_w, grad_b, g); every output buffer and the workspace start as NaN."""
+GUARD, GUARD_WORD = 4096, 0x5A5AA5A5  # the words after the workspace: written by no kernel
+
+
+def c_grad(env, net, base, spec, dout, index=None):
+    """The C entry points on rows ``spec`` of ``base`` (``index``: a CUDA int32 tensor of blocks of ``spec``'s record, the ``_indexed`` entry points): (y, acts,
+    grad_w, grad_b, g); every output buffer and the workspace start as NaN.  The workspace is exactly what sigmaenv_mlp32_backward_workspace asks for, followed by
+    GUARD words of a fixed pattern that must come back unchanged."""
     import torch
 
     offset, rpb, rs, nb, bs = spec
-    n, L, lib = rpb * nb, len(net._keep[1]), env.lib
+    n, L, lib = rpb * (nb if index is None else index.numel()), len(net._keep[1]), env.lib
     dims = [int(d) for d in net._keep[0]]
     nan = lambda *shape: torch.full(shape, float("nan"), dtype=torch.float32, device="cuda")  # noqa: E731
     y, acts = nan(n, net.out_dim), nan(L - 1, n, 256)
@@ -108,18 +116,26 @@ def c_grad(env, net, base, spec, dout):
     assert lib.mlp32_backward_workspace(h, n, C.byref(nf)) == 0
     length, nr = gc.partition(n)
     assert nf.value == (L - 1) * n * 256 + nr * (max(dims[l] * dims[l + 1] for l in range(L)) + 256)
-    ws = nan(max(int(nf.value), 1))
+    ws = nan(int(nf.value) + GUARD)
+    ws[int(nf.value):].view(torch.int32).fill_(GUARD_WORD)
     gw, gb = [nan(dims[l + 1], dims[l]) for l in range(L)], [nan(dims[l + 1]) for l in range(L)]
     d = torch.from_numpy(dout).cuda()
     torch.cuda.synchronize()
     p = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
     PA = C.c_void_p * L
     src = C.c_void_p(base.data_ptr() + 4 * offset)
-    rc = lib.mlp32_forward_save(env.h, h, src, rpb, rs, nb, bs, p(y), p(acts))
-    assert rc == 0, lib.last_error(env.h)
-    rc = lib.mlp32_backward(env.h, h, src, rpb, rs, nb, bs, p(acts), p(d), p(ws), PA(*[t.data_ptr() for t in gw]), PA(*[t.data_ptr() for t in gb]))
+    tail = (p(acts), p(d), p(ws), PA(*[t.data_ptr() for t in gw]), PA(*[t.data_ptr() for t in gb]))
+    if index is None:
+        rc = lib.mlp32_forward_save(env.h, h, src, rpb, rs, nb, bs, p(y), p(acts))
+        assert rc == 0, lib.last_error(env.h)
+        rc = lib.mlp32_backward(env.h, h, src, rpb, rs, nb, bs, *tail)
+    else:
+        rc = lib.mlp32_forward_save_indexed(env.h, h, src, rpb, rs, nb, bs, p(index), index.numel(), p(y), p(acts))
+        assert rc == 0, lib.last_error(env.h)
+        rc = lib.mlp32_backward_indexed(env.h, h, src, rpb, rs, nb, bs, p(index), index.numel(), *tail)
     assert rc == 0, lib.last_error(env.h)
     env.sync()
+    assert (ws[int(nf.value):].view(torch.int32) == GUARD_WORD).all(), "the backward wrote past the workspace it asks for"
     return y, acts, gw, gb, ws[: (L - 1) * n * 256].view(L - 1, n, 256)
 
 
@@ -193,6 +209,138 @@ def test_zero_dout_rows_are_as_if_absent(env):
         assert gc.worst_ratio(gw[l].cpu().numpy(), ref["dW"][l], full["bound_dW"][l]) <= 1.0
         assert gc.worst_ratio(gb[l].cpu().numpy(), ref["db"][l], full["bound_db"][l]) <= 1.0
     assert (g.cpu().numpy()[:, ~keep] == 0).all()
+
+
+# ---- past the partition's thresholds -------------------------------------------------------------------------------------------------
+THRESHOLDS = gc.THRESHOLDS  # the four row counts at which grad::range_len changes the shape of the dW / db sums
+BIG_NETS = [(ACTOR, "exact"), (CRITIC, "split")]  # (the critic's 512 inputs: four input blocks of 128 in dW_0)
+BIG_IDS = dict(ids=lambda v: v if isinstance(v, str) else "x".join(map(str, v)) if isinstance(v, list) else str(v))
+INDEXED = {16385: (5, 3277), 20481: (3, 6827)}    # rows = rows per block x index entries
+
+
+def test_the_threshold_row_counts_are_where_the_partition_changes():
+    for rows, (length, n, last) in THRESHOLDS.items():
+        assert gc.partition(rows) == (length, n) and rows - (n - 1) * length == last and 0 < last <= length
+    assert gc.partition(16384)[1] == gc.MAX_RANGES == gc.partition(20480)[1] and gc.partition(16384)[0] == gc.MIN_RANGE
+    assert all(rpb * m == rows and rows in THRESHOLDS for rows, (rpb, m) in INDEXED.items())
+
+
+def frames_record(frames, seed):
+    """A record of ``frames`` blocks of ``rpb`` rows (odd row stride, a gap between the blocks, the base at a storage offset of 3 floats, NaN around the rows) and
+    an index of ``m`` entries into it, not sorted and with duplicates: (record on the device, spec, index on the device, the indexed rows gathered dense [m rpb, K])"""
+    import torch
+
+    xf, m = frames
+    Fr, rpb, K = xf.shape
+    W = K + 3 if (K + 3) % 2 else K + 4
+    bstride = rpb * W + 5
+    rec = torch.full((3 + Fr * bstride + W,), float("nan"), dtype=torch.float32)
+    rec[3:3 + Fr * bstride].view(Fr, bstride)[:, : rpb * W].view(Fr, rpb, W)[:, :, :K] = torch.from_numpy(xf)
+    idx = np.random.default_rng(seed).integers(0, Fr, m).astype(np.int32)
+    idx[-1] = idx[0]
+    assert len(np.unique(idx)) < m and (np.diff(idx) < 0).any()
+    return rec.cuda(), (3, rpb, W, Fr, bstride), torch.from_numpy(idx).cuda(), np.ascontiguousarray(xf[idx].reshape(m * rpb, K))
+
+
+def indexed_case(rows, dims):
+    """the indexed form of ``rows``: a record of 1000 frames, the index over it"""
+    rpb, m = INDEXED[rows]
+    xf = ((np.random.default_rng(rows).random((1000, rpb, dims[0])) * 2 - 1) * 1.5).astype(np.float32)
+    return frames_record((xf, m), rows)
+
+
+@pytest.mark.parametrize("rows", list(THRESHOLDS))
+@pytest.mark.parametrize("dims,mode", BIG_NETS, **BIG_IDS)
+def test_gradients_hold_both_layers_past_the_partition_thresholds(env, dims, mode, rows):
+    """The rows inside a record (odd stride, blocks with gaps, NaN around them; outputs and workspace start as NaN, the workspace is guarded -- c_grad) against both
+    layers of the criterion with its own constants, and the same bits from the dense rows."""
+    import torch
+
+    mlp, net = network(dims, mode)
+    x, dout = inputs(rows, dims)
+    rec, spec = in_record(x)
+    y, acts, gw, gb, g = c_grad(env, net, rec, spec, dout)
+    assert not any(torch.isnan(t).any() for t in gw + gb + [y, acts, g])
+    other = c_grad(env, net, torch.from_numpy(x).cuda(), (0, rows, dims[0], 1, 0), dout)
+    assert same(y, other[0]) and same(acts, other[1]) and same(g, other[4]) and all(same(a, b) for a, b in zip(gw + gb, other[2] + other[3]))
+    cpu = lambda ts: [t.cpu().numpy() for t in ts]  # noqa: E731
+    what = f"{'x'.join(map(str, dims))} {mode} rows={rows}"
+    acts_h = acts.cpu().numpy()
+    r1 = gc.check_backward(gc.weights_of(mlp), x, acts_h, dout, cpu(gw), cpu(gb), g.cpu().numpy(), what=what)
+    gc.check_acts(acts_h, mlp, x, what=what)
+    r2 = gc.check_end_to_end([t for q in zip(cpu(gw), cpu(gb)) for t in q], mlp, x, dout, what=what)
+    print(what, "layer 1", {k: round(v, 4) for k, v in r1["ratios"].items()}, "end to end", {k: round(v, 4) for k, v in r2["ratios"].items()})
+
+
+@pytest.mark.parametrize("rows", list(INDEXED))
+@pytest.mark.parametrize("dims,mode", BIG_NETS, **BIG_IDS)
+def test_indexed_entry_points_equal_the_dense_gather_past_the_thresholds(env, dims, mode, rows):
+    import torch
+
+    mlp, net = network(dims, mode)
+    rec, spec, index, x = indexed_case(rows, dims)
+    dout = inputs(rows, dims)[1]
+    y, acts, gw, gb, g = c_grad(env, net, rec, spec, dout, index)
+    assert not any(torch.isnan(t).any() for t in gw + gb + [y, acts, g])
+    yd, actsd, gwd, gbd, gd = c_grad(env, net, torch.from_numpy(x).cuda(), (0, rows, dims[0], 1, 0), dout)
+    assert same(y, yd) and same(acts, actsd) and same(g, gd)
+    assert all(same(a, b) for a, b in zip(gw + gb, gwd + gbd))
+
+
+def hold_one_row_probes(env, net, dims, x, base, spec, index, what):
+    """Per probe row r: the backward of a dout that is zero but in row r (entries of magnitude about 1).  Every other row of the device's g_l is an exact zero, so
+    every dW / db chain is zeros plus one term and gc.check_one_row holds each layer with == to the one product of the device's own g_l[r] and a_l[r]."""
+    import torch
+
+    rows, L = len(x), len(dims) - 1
+    rng = np.random.default_rng(rows)
+    small = [0] * L
+    assert len(set(gc.probe_rows(rows))) == 8 and all(0 <= r < rows for r in gc.probe_rows(rows))
+    for r in gc.probe_rows(rows):
+        dout = np.zeros((rows, dims[-1]), np.float32)
+        dout[r] = rng.uniform(0.5, 1.5, dims[-1]) * rng.choice([-1.0, 1.0], dims[-1])
+        y, acts, gw, gb, g = c_grad(env, net, base, spec, dout, index)
+        inside = int(torch.count_nonzero(g[:, r]))  # (a NaN left in the workspace counts as non-zero)
+        assert 0 < inside == int(torch.count_nonzero(g)), f"{what} probe {r}: g is not zero outside the row"
+        g_rows = list(g[:, r].cpu().numpy()) + [dout[r]]
+        a_rows = [x[r]] + list(acts[:, r].cpu().numpy())
+        for l in range(L):
+            small[l] += gc.check_one_row(rows, g_rows[l], a_rows[l], gw[l].cpu().numpy(), gb[l].cpu().numpy(), what=f"{what} probe {r} layer {l}")
+    print(what, "probes", gc.probe_rows(rows), "products below 2^-120 held to the bound, per layer:", small)
+    assert small[L - 1] == 0
+
+
+@pytest.mark.parametrize("rows", list(THRESHOLDS))
+@pytest.mark.parametrize("dims,mode", BIG_NETS, **BIG_IDS)
+def test_one_row_of_dout_is_added_once_in_its_own_range(env, dims, mode, rows):
+    import torch
+
+    mlp, net = network(dims, mode)
+    x = inputs(rows, dims)[0]
+    hold_one_row_probes(env, net, dims, x, torch.from_numpy(x).cuda(), (0, rows, dims[0], 1, 0), None, f"{'x'.join(map(str, dims))} rows={rows}")
+
+
+@pytest.mark.parametrize("dims,mode", BIG_NETS, **BIG_IDS)
+def test_one_row_of_dout_is_added_once_through_the_index(env, dims, mode):
+    mlp, net = network(dims, mode)
+    rec, spec, index, x = indexed_case(16385, dims)
+    hold_one_row_probes(env, net, dims, x, rec, spec, index, f"{'x'.join(map(str, dims))} indexed rows=16385")
+
+
+@pytest.mark.parametrize("rows", list(THRESHOLDS))
+@pytest.mark.parametrize("dims,mode", BIG_NETS, **BIG_IDS)
+def test_db_of_the_output_layer_is_the_exact_sum_of_a_dyadic_dout(env, dims, mode, rows):
+    """dout = multiples of 2^-10 below 1 in magnitude, in every row: a column's sum of magnitudes stays below 2^14, so every partial sum in any order is a multiple
+    of 2^-10 below 2^14 -- 24 bits: exact.  db of the output layer (the sum of dout over the rows) therefore equals the float64 sum."""
+    import torch
+
+    mlp, net = network(dims, mode)
+    x = inputs(rows, dims)[0]
+    dout = (np.random.default_rng(rows).integers(-1023, 1024, (rows, dims[-1])) / 1024.0).astype(np.float32)
+    assert np.abs(dout.astype(np.float64)).sum(0).max() < 2.0 ** 14
+    y, acts, gw, gb, g = c_grad(env, net, torch.from_numpy(x).cuda(), (0, rows, dims[0], 1, 0), dout)
+    assert not any(torch.isnan(t).any() for t in gw + gb)
+    assert np.array_equal(gb[-1].cpu().numpy().astype(np.float64), dout.astype(np.float64).sum(0))
 
 
 @pytest.mark.parametrize("dims", [ACTOR, WIDE], ids=lambda v: "x".join(map(str, v)))

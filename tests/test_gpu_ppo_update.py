@@ -5,7 +5,8 @@ criterion against float64, the whole chain to float64 torch autograd with tests/
 
 Shapes: a record of F = 37 frames of N = 5 agents; the actor D -> 256^3 -> 4 with D in {32, 35} (16-byte and 4-byte rows), the critic N D -> 256^3 -> 1;
 M in {1, 13, 52} frames = 5 / 65 / 260 actor rows (inside a 64-row tile, one row past it, two dW ranges) and 1 / 13 / 52 critic rows, plus 70 critic rows with
-repetition (past a tile)."""
+repetition (past a tile).  The head alone also at M in {1024, 1025, 2049} frames of an env of 16 agents: 64 / 65 / 129 workgroups, where a lane of the final sum adds
+one, two, three workgroups (ppo_head_check.BIG_M)."""
 import copy
 import ctypes as C
 
@@ -142,7 +143,8 @@ def c_head(env, case):
     import torch
     from sigmarl_amd import capi
 
-    M = len(case["index"])
+    M, N = case["out"].shape[:2]
+    assert env.N == N
     dev = lambda a, dt=np.float32: torch.from_numpy(np.ascontiguousarray(a, dt)).cuda()  # noqa: E731
     nan = lambda *shape: torch.full(shape, float("nan"), dtype=torch.float32, device="cuda")  # noqa: E731
     t = dict(index=dev(case["index"], np.int32), out=dev(case["out"]), value=dev(case["value"]), action=dev(case["action"]), sample_log_prob=dev(case["sample_log_prob"]),
@@ -177,6 +179,39 @@ def test_head_holds_the_criterion_against_float64_and_repeats_its_bits(env, M):
     if M == 52:  # every branch is populated where it can be (260 rows)
         p = pc.populations(ref)
         assert all(p[k] > 0 for k in ("inside_pos", "inside_neg", "above_pos", "above_neg", "below_pos", "below_neg", "e_small", "e_large", "sigma_floor")), p
+
+
+@pytest.fixture(scope="module")
+def env16():
+    """16 agents (the head's rows per frame are the env's agents): 1024 frames are 64 workgroups of 256 rows"""
+    from sigmarl_amd.env import SigmaEnv
+    from sigmarl_amd.params import Parameters
+
+    e = SigmaEnv(Parameters(n_agents=pc.BIG_N, scenario_type="cpm_entire", is_use_mtv_distance=False, is_apply_mask=False, is_obs_noise=False, max_steps=6), n_envs=8,
+                 device="cuda:0")
+    e.reset_random(seed=3)
+    yield e
+    e.close()
+
+
+@pytest.mark.parametrize("M", list(pc.BIG_M))
+def test_head_past_64_workgroups_holds_the_criterion_and_counts_the_clipped_rows_exactly(env16, M):
+    """M x 16 rows in 64 / 65 / 129 workgroups: in sigmaenv_ppo_sum_kernel every lane adds one workgroup, lane 0 two, lane 0 three (a ragged last pass).  The
+    criterion against float64 as it stands, the same bits from a second launch, and clip_fraction bit for bit: the flags are 0 or 1, so their sum is exact in any
+    order, and no row of the case lies in the branch band (asserted; tests/test_ppo_head_check.py holds the twin to the same)."""
+    rows, groups, chain = pc.BIG_M[M]
+    assert M * pc.BIG_N == rows and -(-rows // 256) == groups and -(-groups // 64) == chain
+    for pattern in pc.BIG_PATTERNS:
+        case, ref, c, moved = pc.big_case(M, pattern)
+        assert not pc.in_the_band(ref, c).any() and pc.head(case, np.float32)["clipped"] == ref["clipped"]
+        da, dc, res = c_head(env16, case)
+        r, _ = pc.check(da, dc, res, case, what=f"head M={M} N={pc.BIG_N} {pattern}")
+        assert r["ambiguous_rows"] == 0 and res[6] == 0 and res[7] == 0
+        print(f"head M={M} {pattern}: clip_fraction {res[4]!r}, {ref['clipped']} of {rows} rows clipped in float64")
+        assert res[4].tobytes() == pc.exact_clip_fraction(ref).tobytes()
+        da2, dc2, res2 = c_head(env16, case)
+        assert np.array_equal(da.view(np.int32), da2.view(np.int32)) and np.array_equal(dc.view(np.int32), dc2.view(np.int32))
+        assert np.array_equal(res.view(np.int32), res2.view(np.int32))
 
 
 def test_head_entropy_draws_are_those_the_host_generator_predicts(env):

@@ -1,6 +1,7 @@
 """The backward pass's yardstick (tests/gradient_check.py) on the host: a numpy float32 twin of sigmaenv_grad.inc -- the same formulas, the same tile- and
-range-ordered sums, every product rounded separately -- passes both layers of the criterion, the planted defects fail it; the row partition is what the header
-states; the transposed packed form of the weights (sigmaenv_pack.h) is held word for word to its reference.  No GPU needed."""
+range-ordered sums, every product rounded separately -- passes both layers of the criterion, the planted defects fail it; at the four row counts where the partition
+changes a narrower twin passes both layers, the one-row probes and the exact dyadic sum, and two faults of the partition that no earlier size can show fail them;
+the row partition is what the header states; the transposed packed form of the weights (sigmaenv_pack.h) is held word for word to its reference.  No GPU needed."""
 import copy
 import os
 
@@ -50,9 +51,12 @@ def backward_twin(weights, x, acts, dout, defect=None):
     g[n - 1] = dout.astype(F32).reshape(rows, -1)
     for l in range(n - 1, 0, -1):
         Wl = weights[l].T if (defect == "untransposed" and weights[l].shape[0] == weights[l].shape[1]) else weights[l]
-        acc = np.zeros((rows, weights[l].shape[1]), F32)
+        live = np.flatnonzero((g[l] != 0).any(1))  # (a row whose g is zero throughout adds zeros to +0: its chains are not run)
+        part = np.zeros((live.size, weights[l].shape[1]), F32)
         for f in range(weights[l].shape[0]):
-            acc = acc + g[l][:, f:f + 1] * Wl[f:f + 1, :]
+            part = part + g[l][live, f:f + 1] * Wl[f:f + 1, :]
+        acc = np.zeros((rows, weights[l].shape[1]), F32)
+        acc[live] = part
         if defect == "pad_column" and l == n - 1:  # a padded feature column of the contraction (4 -> 8) carrying a value: one more, spurious, term
             rng = np.random.default_rng(5)
             acc = acc + (np.abs(g[l]).max(1, keepdims=True) * F32(2e-3)) * rng.standard_normal((1, acc.shape[1])).astype(F32) * np.abs(Wl).max()
@@ -61,33 +65,45 @@ def backward_twin(weights, x, acts, dout, defect=None):
         if defect == "drop_tile":
             g[l - 1][rows // 64 * 64:] = 0
     length, nr = gc.partition(rows)
+    if defect == "range_floor":  # the range length held at its floor under the cap of 64 ranges: the rows from 64 * 256 on are in no range
+        length, nr = gc.MIN_RANGE, min(gc.MAX_RANGES, -(-rows // gc.MIN_RANGE))
+    in_w = np.arange(nr * length) < rows  # the rows a range adds (its slots past the last row add +0: exact)
+    if defect == "r_end_short" and length > gc.MIN_RANGE:  # the end of every range one row short once the length is above the floor
+        in_w[np.minimum(np.arange(1, nr + 1) * length, rows) - 1] = False
+    in_b = in_w.copy()
+    if defect == "db_one_tile":
+        in_b[64:] = False
+
+    def ranged(t, on):  # [nr, length, width]: the rows by range, zeros where a range adds nothing
+        p = np.zeros((nr * length, t.shape[1]), F32)
+        n = min(rows, nr * length)
+        p[:n] = t[:n]
+        p[~on] = 0
+        return p.reshape(nr, length, t.shape[1])
+
     dW, db = [], []
     for l in range(n):
         gl = g[l].copy()
         if defect == "drop_tile":
             gl[rows // 64 * 64:] = 0
+        gb = gl.copy()  # (row63 is a fault of the dW chain alone)
         if defect == "row63":
             gl[100] = 0  # one row of the second tile is never added
-        pw, pb = [], []
-        for r in range(nr):
-            lo, hi = r * length, min(rows, (r + 1) * length)
-            acc = np.zeros((gl.shape[1], a[l].shape[1]), F32)
-            for row in range(lo, hi):
-                acc = acc + gl[row][:, None] * a[l][row][None, :]
-            pw.append(acc)
-            gb = g[l] if defect == "row63" else gl  # (row63 is a fault of the dW chain alone)
-            if defect == "db_one_tile":
-                hi = min(hi, lo + 64) if r == 0 else lo
-            even, odd = np.zeros(gl.shape[1], F32), np.zeros(gl.shape[1], F32)
-            for row in range(lo, hi):
-                if (row - lo) % 2 == 0:
-                    even = even + gb[row]
-                else:
-                    odd = odd + gb[row]
-            pb.append(even + odd)
+        gw_r, gb_r, a_r = ranged(gl, in_w), ranged(gb, in_b), ranged(a[l], in_w)
+        pw, even, odd = np.zeros((nr, gl.shape[1], a[l].shape[1]), F32), np.zeros((nr, gl.shape[1]), F32), np.zeros((nr, gl.shape[1]), F32)
+        on = np.flatnonzero((gw_r != 0).any((1, 2)) | (gb_r != 0).any((1, 2)))  # (a range whose g is zero throughout adds zeros to +0: its partial sums are +0)
+        gw_o, gb_o, a_o, pw_o, even_o, odd_o = gw_r[on], gb_r[on], a_r[on], pw[on], even[on], odd[on]
+        for i in range(length if on.size else 0):  # every range's chain over its rows in order, the ranges side by side
+            pw_o = pw_o + gw_o[:, i, :, None] * a_o[:, i, None, :]
+            if i % 2 == 0:
+                even_o = even_o + gb_o[:, i]
+            else:
+                odd_o = odd_o + gb_o[:, i]
+        pw[on], even[on], odd[on] = pw_o, even_o, odd_o
+        pw, pb = list(pw), list(even + odd)
         if defect == "missing_partial" and l == 1:
             del pw[2]
-        sw, sb = np.zeros_like(pw[0]) if not pw else pw[0], np.zeros(gl.shape[1], F32) if not pb else pb[0]
+        sw, sb = np.zeros((gl.shape[1], a[l].shape[1]), F32) if not pw else pw[0], np.zeros(gl.shape[1], F32) if not pb else pb[0]
         for t in pw[1:]:
             sw = sw + t
         for t in pb[1:]:
@@ -98,6 +114,8 @@ def backward_twin(weights, x, acts, dout, defect=None):
 
 
 DEFECTS = ["drop_tile", "row63", "no_dtanh", "untransposed", "db_one_tile", "pad_column", "missing_partial"]
+# faults of the row partition that need more than 64 * 256 rows to show: planted at the thresholds below, not at ROWS
+PARTITION_DEFECTS = ["range_floor", "r_end_short"]
 
 
 @pytest.fixture(scope="module")
@@ -158,6 +176,102 @@ def test_planted_defects_fail(case, defect):
     l1, l2 = both_layers(case, defect)
     print(defect, l1["ratios"], l2["ratios"])
     assert not l1["ok"], f"{defect} passes the backward-given-the-activations bound: {l1['ratios']}"
+
+
+# ---- the row counts at which the partition changes (tests/test_gpu_mlp32_grad.py runs the device there) ------------------------------------------------------
+THRESHOLDS = gc.THRESHOLDS
+NARROW = [35, 64, 64, 4]  # the twin's network at these sizes: 64 wide, not 256 -- the partition and every chain over the rows are functions of the row count alone
+# every row count the suite ran a backward on before (host and device): one range length, at most 4 ranges
+EARLIER_ROWS = (0, 1, 5, 13, 52, 63, 64, 65, 70, 130, 200, 260, 838)
+_big = {}
+
+
+def big(rows):
+    """(mlp, weights, x, acts, dout, refs) of the narrow network on ``rows`` rows, made once"""
+    if rows not in _big:
+        mlp = make_net(NARROW, 4)
+        rng = np.random.default_rng(rows)
+        x = ((rng.random((rows, NARROW[0])) * 2 - 1) * 1.5).astype(F32)
+        x[7] = 0.0
+        y, acts = forward_twin(mlp, x)
+        dout = (rng.standard_normal((rows, NARROW[-1])) / rows).astype(F32)
+        dout[11] = 0.0
+        _big[rows] = (mlp, gc.weights_of(mlp), x, acts, dout, gc.references(mlp, x, dout))
+    return _big[rows]
+
+
+def probe(rows, r, defect=None):
+    """The one-row probe of row ``r`` on the twin: the checks of tests/test_gpu_mlp32_grad.py's hold_one_row_probes; returns the small products per layer"""
+    mlp, weights, x, acts, _, _ = big(rows)
+    dout = np.zeros((rows, NARROW[-1]), F32)
+    rng = np.random.default_rng(r)
+    dout[r] = rng.uniform(0.5, 1.5, NARROW[-1]) * rng.choice([-1.0, 1.0], NARROW[-1])
+    dW, db, g = backward_twin(weights, x, acts, dout, defect)
+    assert all(np.count_nonzero(t) == np.count_nonzero(t[r]) > 0 for t in g)
+    g_rows, a_rows = [t[r] for t in g] + [dout[r]], [x[r]] + [t[r] for t in acts]
+    return [gc.check_one_row(rows, g_rows[l], a_rows[l], dW[l], db[l], what=f"twin rows={rows} probe {r} layer {l}") for l in range(len(weights))]
+
+
+def dyadic(rows, defect=None):
+    """(db of the output layer, the float64 sum of dout) for a dout of multiples of 2^-10 below 1 in magnitude: every partial sum in any order is exact"""
+    mlp, weights, x, acts, _, _ = big(rows)
+    dout = (np.random.default_rng(rows).integers(-1023, 1024, (rows, NARROW[-1])) / 1024.0).astype(F32)
+    assert np.abs(dout.astype(np.float64)).sum(0).max() < 2.0 ** 14
+    return backward_twin(weights, x, acts, dout, defect)[1][-1].astype(np.float64), dout.astype(np.float64).sum(0)
+
+
+def test_the_thresholds_are_where_the_partition_changes():
+    for rows, (length, n, last) in THRESHOLDS.items():
+        assert gc.partition(rows) == (length, n) and rows - (n - 1) * length == last
+        assert len(set(gc.probe_rows(rows))) == 8 and all(0 <= r < rows for r in gc.probe_rows(rows))
+    assert all(gc.partition(r) == (256, -(-r // 256)) and -(-r // 256) <= 4 for r in EARLIER_ROWS)
+
+
+@pytest.mark.parametrize("rows", list(THRESHOLDS))
+def test_the_float32_twin_passes_every_check_at_the_thresholds(rows):
+    mlp, weights, x, acts, dout, refs = big(rows)
+    gc.check_acts(acts, mlp, x, what=f"twin rows={rows}")
+    l1, l2 = both_layers(big(rows), None)
+    print(rows, l1["ratios"], l2["ratios"])
+    assert l1["ok"] and l2["ok"], (l1["ratios"], l2["ratios"])
+    small = np.sum([probe(rows, r) for r in gc.probe_rows(rows)], 0)
+    print(rows, "products below 2^-120 per layer:", list(small))
+    assert small[-1] == 0
+    got, want = dyadic(rows)
+    assert np.array_equal(got, want)
+
+
+def fails(f, *args):
+    try:
+        f(*args)
+    except AssertionError:
+        return True
+    return False
+
+
+def test_partition_defects_pass_the_earlier_sizes_and_fail_at_the_thresholds(case):
+    """range_floor is the gap the thresholds close: below 64 * 256 + 1 rows it IS the partition, so at every size the suite had it gives the sound twin's bits; one row
+    further it drops rows, which the last row's probe, the dyadic sum and (from 20480 rows) the bound see.  r_end_short needs a range above the floor length."""
+    mlp, weights, x, acts, dout, refs = case
+    assert ROWS == max(EARLIER_ROWS)
+    for defect in PARTITION_DEFECTS:
+        for a, b in zip(backward_twin(weights, x, acts, dout, defect), backward_twin(weights, x, acts, dout)):
+            assert all(np.array_equal(p, q) for p, q in zip(a, b))
+        assert all(m["ok"] for m in both_layers(case, defect))
+    caught = {}
+    for defect in PARTITION_DEFECTS:
+        for rows, (length, n, last) in THRESHOLDS.items():
+            l1 = both_layers(big(rows), defect)[0]
+            got, want = dyadic(rows, defect)
+            caught[defect, rows] = dict(bound=not l1["ok"], probes=[r for r in gc.probe_rows(rows) if fails(probe, rows, r, defect)], dyadic=not np.array_equal(got, want))
+            print(defect, rows, caught[defect, rows], {k: round(v, 3) for k, v in l1["ratios"].items() if k.startswith("d")})
+    nothing = dict(bound=False, probes=[], dyadic=False)
+    assert caught["range_floor", 16384] == nothing and caught["r_end_short", 16384] == nothing  # (64 ranges of the floor length: neither fault changes anything)
+    assert caught["range_floor", 16385]["probes"] == [16384] and caught["range_floor", 16385]["dyadic"]   # the one row past 64 * 256
+    assert caught["range_floor", 20480]["bound"] and caught["range_floor", 20481]["bound"] and caught["range_floor", 20481]["probes"] == [r for r in gc.probe_rows(20481) if r >= 16384]
+    for rows in (16385, 20480, 20481):
+        length, n = gc.partition(rows)
+        assert caught["r_end_short", rows]["probes"] == [r for r in gc.probe_rows(rows) if (r + 1) % length == 0 or r == rows - 1] and caught["r_end_short", rows]["dyadic"]
 
 
 def test_zero_rows_and_zero_dout_rows():
