@@ -2023,9 +2023,17 @@ extern "C" int sigmaenv_create(const sigmaenv_config_t* cfg, const sigmaenv_map_
   H2D(d_y, map->yaw, (size_t)np * S * 4);
   H2D(d_nc, map->n_center, (size_t)np * 4); H2D(d_nl, map->n_left, (size_t)np * 4); H2D(d_nr, map->n_right, (size_t)np * 4);
   H2D(d_loop, map->is_loop, (size_t)np);
-  // pruning table: bounding boxes of runs of SIGMAENV_CHUNK consecutive real segments (points 8c .. min(8c+8, n-1))
+  // pruning table: bounding boxes of runs of SIGMAENV_CHUNK consecutive real segments (chunk c: points 4c .. min(4c+4, n-1)).  The table's stride counts the
+  // padded polyline (mask_stage1 reads a neighbour row at an index clamped to P - 2 before it knows the point count); the candidate masks are 64-bit, and only
+  // chunks with real segments ever get a bit: a map is pruned iff its longest polyline has at most 64 such chunks, i.e. 257 points, whatever the padding adds
+  // (tests/test_gpu_scan_synthetic.py: 257 and 258 points).  Longer polylines fall back to the full scan.
   int nch = (P - 1 + SIGMAENV_CHUNK - 1) / SIGMAENV_CHUNK;
-  bool prune = nch <= 64;  // the candidate masks are 64-bit; longer polylines fall back to the full scan
+  int real_nch = 0;
+  for (int p = 0; p < np; ++p) {
+    const int longest = std::max(map->n_center[p], std::max(map->n_left[p], map->n_right[p]));
+    real_nch = std::max(real_nch, (longest - 1 + SIGMAENV_CHUNK - 1) / SIGMAENV_CHUNK);
+  }
+  bool prune = real_nch <= 64;
   if (const char* e = getenv("SIGMAENV_PRUNE")) prune = prune && atoi(e) != 0;
   float4 *d_box = nullptr, *d_gbox = nullptr;
   std::vector<float4> hb, hg;  // must outlive the asynchronous uploads below

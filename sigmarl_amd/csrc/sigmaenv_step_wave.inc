@@ -770,7 +770,7 @@ __global__ void __launch_bounds__(256, STEP_WAVE_MIN_WAVES) sigmaenv_step_wave_k
       const float* pv = s.vnew + sl * 10 + 2 * e4;
       const Edge ed = make_edge(pv[0], pv[1], pv[2], pv[3]);
       const unsigned poly_off = (unsigned)(side + 1) * (unsigned)m.poly_stride + (unsigned)s.path[sl] * (unsigned)(m.P * 2);
-      // a list that overflowed (more than NEAR_CAP close segments: not seen on the shipped maps) is replaced by every real segment of the boundary
+      // a list that overflowed (more than NEAR_CAP close segments: the `dense` map of tests/test_gpu_scan_synthetic.py, exactly 8, 9 and up to 20) is replaced by every real segment of the boundary
       const bool all = nn > NEAR_CAP;
       const int cnt = all ? (s.npts[sl * 3 + 1 + side] - 1) : nn;
       bool hit = false;

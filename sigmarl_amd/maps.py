@@ -55,6 +55,14 @@ class MapTable:
         self.n_yaw = np.ascontiguousarray(z["n_yaw"].astype(np.int32))
         self.n_left = np.ascontiguousarray(z["n_left"].astype(np.int32))
         self.n_right = np.ascontiguousarray(z["n_right"].astype(np.int32))
+        # A zero-length segment has no projection parameter: the reference divides 0 by 0 there and stops at its own NaN assertion
+        # (helper_scenario.py:862-881), so there is no behaviour to reproduce -- the table is refused.
+        for key, poly, cnt in (("center", self.center, self.n_center), ("left", self.left, self.n_left), ("right", self.right, self.n_right)):
+            for p in range(self.n_paths):
+                same = np.nonzero((np.diff(poly[p, : int(cnt[p])], axis=0) == 0).all(axis=1))[0]
+                if len(same):
+                    raise ValueError(f"map {scenario_type!r}: path {p}, polyline {key!r}: points {int(same[0])} and {int(same[0]) + 1} coincide; "
+                                     "consecutive duplicate points are not supported (remove one of them)")
         self.is_loop = np.ascontiguousarray(z["is_loop"].astype(np.uint8))
         self.lanelet_ids = z["lanelet_ids"].astype(np.int32)
         self.n_lanelet_ids = z["n_lanelet_ids"].astype(np.int32)
