@@ -56,7 +56,7 @@ __device__ __constant__ uint32_t W_REF_BITS[NS] = SIGMAENV_W_REF_BITS;
 #define CAND_LIST 16               /* candidate chunks listed per (agent, polyline); longer masks fall back to bit counting */
 #define ITEM_CAP(S) ((S) * 24 > 64 ? (S) * 24 : 64)  /* candidate chunks of a tile listed per round of the balanced scan; never below 64: ONE task can have up to 64 candidate
                                                         chunks (the masks are 64-bit) and must fit the list alone, else a round could list nothing and the scan would spin */
-#define NEAR_CAP 8                 /* boundary segments within the circumradius listed per (agent, side); more are tested in place */
+#define NEAR_CAP 8                 /* boundary segments within the circumradius listed per agent slot of a FULL tile, in ONE list per tile; a tile with more tests them in place */
 struct Smem {
   float *st, *vold, *vnew, *shrt, *dref, *dleft, *dright, *dbound, *dist, *obs, *thr, *cs, *rew;
   float* carry;  // [S][3] tan(steering), cos / sin(yaw + sideslip) of the slot's CURRENT state: what the next bicycle step of the same launch starts from (phase A)
@@ -71,7 +71,8 @@ struct Smem {
   unsigned long long* acc64;  // per task: (bits of the minimal centre-point distance) << 32 | its lowest segment index, [S * 3]
   uint32_t* acc32;            // per boundary task: bits of the four minimal SQUARED corner distances, [S * 2][4]
   int* nearn;                 // per boundary task: number of segments within the circumradius, [S * 2]
-  uint8_t* nearl;             // indices of the boundary segments within the circumradius, [S * 2][NEAR_CAP]
+  uint16_t* nearl;            // the tile's boundary segments within the circumradius, in any order: (boundary task << 8) | segment index, [S * NEAR_CAP]
+  int* nearc;                 // their number, ONE word per tile; outside this carve-up (the step kernel points it at the free word of its tile's reset area)
   uint8_t* fresh;             // [S] 1 = the agent was (re)placed and has not been stepped since (boundary points of the observation: another index shift,
                               // world_state_rt.py:531-576 vs :686-724); the tile's copy of DevBufs::fresh, kept across the steps of one launch
   unsigned long long* key64;  // [S] scratch of the observation's lanelet search (min over (squared distance bits << 32 | lanelet))
@@ -81,7 +82,7 @@ struct Smem {
   // step, and the next step's scan initialises its areas again.  2 KB per 16-agent tile: the difference between 16 and 20 resident tiles per CU, i.e. room for the
   // wider rows of the non-default observation switches without dropping below the 16 tiles per CU (one resident round at 4096 envs) the default row runs at.
   __host__ __device__ static __forceinline__ size_t scan_scratch_ints(int S) {
-    return (size_t)S * 3 * 2 + (size_t)S * 2 * 4 + (size_t)S * 2 + (size_t)(ITEM_CAP(S) + 1) / 2 + (size_t)(S * 2 * NEAR_CAP + 3) / 4;
+    return (size_t)S * 3 * 2 + (size_t)S * 2 * 4 + (size_t)S * 2 + (size_t)(ITEM_CAP(S) + 1) / 2 + (size_t)(S * NEAR_CAP + 1) / 2;
   }
   __host__ __device__ static __forceinline__ size_t stage_floats(int S, int D, bool lean) {
     const size_t o = ((size_t)S * D + 3) & ~(size_t)3, q = (scan_scratch_ints(S) + 3) & ~(size_t)3;
@@ -97,7 +98,8 @@ struct Smem {
       acc32 = reinterpret_cast<uint32_t*>(q); q += S * 2 * 4;
       nearn = q; q += S * 2;
       items = reinterpret_cast<uint16_t*>(q); q += (ITEM_CAP(S) + 1) / 2;
-      nearl = reinterpret_cast<uint8_t*>(q);  // (only meaningful in the LEAN layout)
+      nearl = reinterpret_cast<uint16_t*>(q);  // (only meaningful in the LEAN layout)
+      nearc = nullptr;
     }
     f += stage_floats(S, D, lean);
     st = f; f += S * 8;

@@ -11,8 +11,9 @@
 //                             two sine / cosine pairs run side by side in the lane pair (DPP quad swap), vertices, state write-out
 //   S   the pruned scan as a balanced work list: lane per (agent, polyline) for the candidate chunks, then lane per (task, chunk) item,
 //                             per-task results merged by LDS atomics (see scan_tile_balanced).  Segments within the circumradius are
-//                             listed in LDS for the edge tests.
-//   E   lane per (agent, side, rectangle edge): edge x listed-segment crossing tests (interX)
+//                             appended to ONE list per tile in LDS for the edge tests.
+//   E   lane per (listed segment, rectangle edge): the tile's list in passes of 64 tests, crossing tests (interX) ORed into the agent's flag;
+//                             a tile whose list overflowed: lane per (agent, side, edge) over every segment of the boundaries with a near one
 //   B1  lane per unordered agent pair: mutual distance, rectangle-rectangle tests of close pairs
 //   C   lane per agent      : reward, short-term path, done / counters by ballots
 //   D   lane per item       : observation rows (observe_tile<WAVE>)
@@ -207,6 +208,7 @@ struct ScanItemOut {
   float best;
   int bk;
   float bs0, bs1, bs2, bs3;
+  unsigned near_bits;  // bit u: segment u of the lane's run lies within the circumradius (boundaries only)
 };
 
 // one chunk of one task: its SIGMAENV_CHUNK segments against the centre point (and, for a boundary, the four corner query points).
@@ -272,17 +274,8 @@ __device__ __forceinline__ void scan_chunk(const DevMap& m, const Smem& s, int s
       if (k + 1 < npt && fmaf(-d_up, d, zc[u]) <= 0.0f) o.bk = k;
     }
   }
-  if (near_bits) {  // one list append per chunk; a list that overflows makes phase E test every segment of that boundary
-    const int bt = sl * 2 + (pl - 1);
-    int slot = atomicAdd(&s.nearn[bt], (int)__popc(near_bits));
-#pragma unroll
-    for (int u = 0; u < SEGS; ++u) {
-      if ((near_bits >> u) & 1u) {
-        if (slot < NEAR_CAP) s.nearl[bt * NEAR_CAP + slot] = (uint8_t)(ch * SIGMAENV_CHUNK + u0 + u);
-        ++slot;
-      }
-    }
-  }
+  o.near_bits = near_bits;  // (the caller appends them to the tile's list: scan_tile_balanced)
+  if (near_bits) atomicAdd(&s.nearn[sl * 2 + (pl - 1)], (int)__popc(near_bits));  // (no value returned: the count tells the overflow walk of phase E which boundaries have a near segment at all)
 }
 __device__ __forceinline__ void scan_merge(const Smem& s, int sl, int pl, const ScanItemOut& o) {
   if (o.bk != 0x7FFFFFFF) {
@@ -300,8 +293,25 @@ template <bool FASTDIV>
 __device__ __forceinline__ void scan_tile_balanced(const DevMap& m, const CfgDerived& dv, const DevBufs& g, const Smem& s, const Tile& t, int G, int lane) {
   // tasks are numbered pl * SG + sl with SG = the slots of a FULL tile (kernel-uniform: division by multiplication); slots beyond a ragged
   // last tile stay idle
-  const int N = t.N, slots = t.slots, SG = G * N, n_tasks = SG * 3, cap = ITEM_CAP(SG);
+  const int N = t.N, slots = t.slots, SG = G * N, n_tasks = SG * 3, cap = ITEM_CAP(SG), near_cap = SG * NEAR_CAP;
   const float near_thr = m.rect_radius + 1e-4f;
+  // The tile's list of near segments: the wavefront owns the tile, so the position of a lane's entries is the number listed so far (wavefront-uniform, in a register)
+  // plus a prefix sum over the lanes of the pass -- no LDS counter.  (One counter per tile bumped by an atomic add per chunk serialises: up to 64 lanes on ONE address,
+  // S2 +2,700 cycles per tile-step against the per-boundary counters it replaced, more than phase E gains; profiles/edge_list_phase_cycles.txt.)
+  int near_total = 0;
+  auto near_append = [&](unsigned nb, int code0) {  // all lanes; nb = 0: nothing to list
+    const int cnt = (int)__popc(nb);
+    const int incl = wave_inclusive_sum(cnt, lane);
+    int slot = near_total + incl - cnt;
+    near_total += __builtin_amdgcn_readlane(incl, 63);
+#pragma unroll
+    for (int u = 0; u < SIGMAENV_CHUNK; ++u) {
+      if ((nb >> u) & 1u) {
+        if (slot < near_cap) s.nearl[slot] = (uint16_t)(code0 + u);
+        ++slot;
+      }
+    }
+  };
   // ---- S1: candidate chunks per task
   for (int base = 0; base < n_tasks; base += 64) {
     // lane -> task: left boundaries, right boundaries, THEN the centre lines.  The work list is filled in lane order, so the centre-line items (one query point
@@ -407,7 +417,7 @@ __device__ __forceinline__ void scan_tile_balanced(const DevMap& m, const CfgDer
 #endif
       // ---- S2: one lane per listed (task, chunk); a last round that fills at most half / a quarter of the wavefront gives every item two /
       // four lanes (two segments / one segment each) instead of leaving the lanes idle
-      auto item_part = [&](int it, auto segs_tag, int u0) {
+      auto item_part = [&](int it, auto segs_tag, int u0, unsigned& nb, int& code0) {
         constexpr int SEGS = decltype(segs_tag)::value;
         const unsigned code = s.items[it];
         const int tpm2 = (int)(code >> 6), ch = (int)(code & 63u);
@@ -417,23 +427,34 @@ __device__ __forceinline__ void scan_tile_balanced(const DevMap& m, const CfgDer
         const unsigned poly_off = (unsigned)pl2 * (unsigned)m.poly_stride + (unsigned)s.path[sl2] * (unsigned)(m.P * 2);
         scan_chunk<FASTDIV, SEGS>(m, s, sl2, pl2, poly_off, s.npts[sl2 * 3 + pl2], ch, u0, first, near_thr, o);
         scan_merge(s, sl2, pl2, o);
+        nb = o.near_bits;
+        code0 = ((sl2 * 2 + (pl2 - 1)) << 8) | (ch * SIGMAENV_CHUNK + u0);  // (boundary task << 8) | first segment of the lane's run
       };
       int it0 = 0;
-      for (; it0 + 64 <= total; it0 += 64) item_part(it0 + lane, std::integral_constant<int, SIGMAENV_CHUNK>{}, 0);
-      const int rem = total - it0;
-      if (rem > 32) {
-        if (lane < rem) item_part(it0 + lane, std::integral_constant<int, SIGMAENV_CHUNK>{}, 0);
-      } else if (rem > 16) {
-        if ((lane >> 1) < rem) item_part(it0 + (lane >> 1), std::integral_constant<int, SIGMAENV_CHUNK / 2>{}, (lane & 1) * (SIGMAENV_CHUNK / 2));
-      } else if (rem > 0) {
-        if ((lane >> 2) < rem) item_part(it0 + (lane >> 2), std::integral_constant<int, SIGMAENV_CHUNK / 4>{}, (lane & 3) * (SIGMAENV_CHUNK / 4));
+      for (; it0 + 64 <= total; it0 += 64) {
+        unsigned nb = 0u;
+        int code0 = 0;
+        item_part(it0 + lane, std::integral_constant<int, SIGMAENV_CHUNK>{}, 0, nb, code0);
+        near_append(nb, code0);
       }
+      const int rem = total - it0;
+      unsigned nb = 0u;
+      int code0 = 0;
+      if (rem > 32) {
+        if (lane < rem) item_part(it0 + lane, std::integral_constant<int, SIGMAENV_CHUNK>{}, 0, nb, code0);
+      } else if (rem > 16) {
+        if ((lane >> 1) < rem) item_part(it0 + (lane >> 1), std::integral_constant<int, SIGMAENV_CHUNK / 2>{}, (lane & 1) * (SIGMAENV_CHUNK / 2), nb, code0);
+      } else if (rem > 0) {
+        if ((lane >> 2) < rem) item_part(it0 + (lane >> 2), std::integral_constant<int, SIGMAENV_CHUNK / 4>{}, (lane & 3) * (SIGMAENV_CHUNK / 4), nb, code0);
+      }
+      if (rem > 0) near_append(nb, code0);
       wave_sync();
     } while (__any(pending));
   }
 #ifdef SIGMAENV_PROFILE
   if (g.dbg_ts && lane == 0) g.dbg_ts[(size_t)t.env0 / (size_t)G * 16 + 11] = __builtin_readcyclecounter();  // end of S2 (all rounds)
 #endif
+  if (lane == 0) *s.nearc = near_total;  // for phase E
   // ---- S3: results per task
   const float wh = dv.wh;
   for (int tpm = lane; tpm < n_tasks; tpm += 64) {
@@ -627,6 +648,7 @@ __global__ void __launch_bounds__(256, STEP_WAVE_MIN_WAVES) sigmaenv_step_wave_k
   unsigned long long* s_mask = reinterpret_cast<unsigned long long*>(base + ((Smem::bytes(G * N, N, t.K, t.DL, true) + 15) & ~(size_t)15));
   int* s_full = reinterpret_cast<int*>(s_mask + G);
   int* s_any = s_full + G;
+  s.nearc = s_any + 1;  // (the word between the any-reset flag and the reset's env list, which starts at s_any + 2: free in every phase)
   int* s_tim = reinterpret_cast<int*>(base + ((Smem::bytes(G * N, N, t.K, t.DL, true) + 15) & ~(size_t)15) + 16 * (size_t)G + 16);  // [G][4]: timer rows between the steps of one launch
   // The first step of a launch reads the tile from HBM, the last one writes it back; in between the tile lives in LDS (it is all there after a
   // step: state, vertices, closest indices, short-term path, path row, timers) and only the record row of the step, and whatever a reset
@@ -711,6 +733,7 @@ __global__ void __launch_bounds__(256, STEP_WAVE_MIN_WAVES) sigmaenv_step_wave_k
       s.fresh[sl] = 0;  // stepped (phase R sets it again for the agents it re-places)
       s.thr[sl * 3] = pp.x; s.thr[sl * 3 + 1] = pp.y;
       s.thr[sl * 3 + 2] = __int_as_float(tm.x);
+      s.flags[sl * 4 + 0] = 0;  // boundary collision: phase E sets it from the lanes that find a crossing
       s.flags[sl * 4 + 1] = loop_flag;
       s.flags[sl * 4 + 2] = tm.y;  // counters: the first agent's lane of every env keeps them for the done() bookkeeping
       s.near[sl * (t.K > 0 ? t.K : 1)] = tm.z;  // (the nearest-neighbour list is only filled by the observation phase)
@@ -760,48 +783,57 @@ __global__ void __launch_bounds__(256, STEP_WAVE_MIN_WAVES) sigmaenv_step_wave_k
   {
   STEP_TABLES(m, g);
   (void)g;
-  if (m.nch > 0 && !SKIP(4)) {
-    for (int base = 0; base < t.slots * 2; base += 16) {
-      const int bt = base + (lane >> 2), e4 = lane & 3;
-      const bool act = bt < t.slots * 2;
-      const int btc = act ? bt : 0;
-      const int sl = btc >> 1, side = btc & 1;
-      const int nn = act ? s.nearn[btc] : 0;
-      const float* pv = s.vnew + sl * 10 + 2 * e4;
-      const Edge ed = make_edge(pv[0], pv[1], pv[2], pv[3]);
-      const unsigned poly_off = (unsigned)(side + 1) * (unsigned)m.poly_stride + (unsigned)s.path[sl] * (unsigned)(m.P * 2);
-      // a list that overflowed (more than NEAR_CAP close segments: the `dense` map of tests/test_gpu_scan_synthetic.py, exactly 8, 9 and up to 20) is replaced by every real segment of the boundary
-      const bool all = nn > NEAR_CAP;
-      const int cnt = all ? (s.npts[sl * 3 + 1 + side] - 1) : nn;
-      bool hit = false;
-      // the first four listed segments are requested together (one round trip instead of one per segment; lists are rarely longer)
-      constexpr int PRE = 4;
-      Seg4 pre[PRE];
-#pragma unroll
-      for (int j = 0; j < PRE; ++j) {
-        const unsigned k = (j < cnt) ? (all ? (unsigned)j : (unsigned)s.nearl[btc * NEAR_CAP + (j < NEAR_CAP ? j : 0)]) : 0u;
-        pre[j] = *reinterpret_cast<const Seg4*>(m.center + (poly_off + 2u * k));
-      }
-#pragma unroll
-      for (int j = 0; j < PRE; ++j) {
-        if (j < cnt) {
-          const Seg4 sg = pre[j];
+  if (m.nch > 0 && !SKIP(4) && !SKIP(2)) {  // (a skipped scan leaves no list)
+    const int total = __builtin_amdgcn_readfirstlane(*s.nearc), near_cap = G * N * NEAR_CAP;
+#ifdef SIGMAENV_PROFILE
+    if (g.dbg_ts && lane == 0) {  // list statistics of the tile, in the upper halves of the work-list words: entries, tile-steps whose list overflowed
+      g.dbg_ts[(size_t)tile_index * 16 + 8] += (unsigned long long)total << 32;
+      g.dbg_ts[(size_t)tile_index * 16 + 9] += (unsigned long long)(total > near_cap ? 1 : 0) << 32;
+    }
+#endif
+    if (total <= near_cap) {
+      // one lane per (listed segment, rectangle edge), one test per lane and pass.  The flag of an agent is the OR over its entries and edges, so neither the
+      // order of the list nor the pass an entry falls into enters the result.  Every lane requests a segment (the last pass's idle lanes the last test's: no
+      // divergence before the load); only the test is predicated.  (Two passes per round with both segments requested up front are slower -- longer code, the
+      // second request's address arithmetic paid by every round: profiles/edge_list_ab.txt.)
+      const int n_tests = total * 4, e4 = lane & 3;
+      for (int base = 0; base < n_tests; base += 64) {
+        const int w = base + lane;
+        const unsigned code = s.nearl[min(w, n_tests - 1) >> 2];
+        const int bt = (int)(code >> 8), sl = bt >> 1, side = bt & 1;
+        const unsigned poly_off = (unsigned)(side + 1) * (unsigned)m.poly_stride + (unsigned)s.path[sl] * (unsigned)(m.P * 2);
+        const Seg4 sg = *reinterpret_cast<const Seg4*>(m.center + (poly_off + 2u * (code & 255u)));
+        if (w < n_tests) {
+          const float* pv = s.vnew + sl * 10 + 2 * e4;
+          const Edge ed = make_edge(pv[0], pv[1], pv[2], pv[3]);
           const float lx = sg.bx - sg.ax, ly = sg.by - sg.ay;
           const float S2 = lx * sg.ay - ly * sg.ax;
-          hit |= edge_hits_segment(ed, sg.ax, sg.ay, sg.bx, sg.by, lx, ly, S2);
+          if (edge_hits_segment(ed, sg.ax, sg.ay, sg.bx, sg.by, lx, ly, S2)) s.flags[sl * 4 + 0] = 1;
         }
       }
-      for (int j = PRE; __any(j < cnt); ++j) {
-        if (j < cnt) {
-          const unsigned k = all ? (unsigned)j : (unsigned)s.nearl[btc * NEAR_CAP + j];
-          const Seg4 sg = *reinterpret_cast<const Seg4*>(m.center + (poly_off + 2u * k));
-          const float lx = sg.bx - sg.ax, ly = sg.by - sg.ay;
-          const float S2 = lx * sg.ay - ly * sg.ax;
-          hit |= edge_hits_segment(ed, sg.ax, sg.ay, sg.bx, sg.by, lx, ly, S2);
+    } else {
+      // the list overflowed (more than NEAR_CAP close segments per slot of the tile: the `dense` map of tests/synthetic_maps.py): lane per (agent, side, edge),
+      // every real segment of each boundary that counted a near one -- a superset of the listed ones, which cannot change the OR
+      for (int base = 0; base < t.slots * 2; base += 16) {
+        const int bt = base + (lane >> 2), e4 = lane & 3;
+        const bool act = bt < t.slots * 2;
+        const int btc = act ? bt : 0;
+        const int sl = btc >> 1, side = btc & 1;
+        const int cnt = (act && s.nearn[btc] > 0) ? (s.npts[sl * 3 + 1 + side] - 1) : 0;
+        const float* pv = s.vnew + sl * 10 + 2 * e4;
+        const Edge ed = make_edge(pv[0], pv[1], pv[2], pv[3]);
+        const unsigned poly_off = (unsigned)(side + 1) * (unsigned)m.poly_stride + (unsigned)s.path[sl] * (unsigned)(m.P * 2);
+        bool hit = false;
+        for (int j = 0; __any(j < cnt); ++j) {
+          if (j < cnt) {
+            const Seg4 sg = *reinterpret_cast<const Seg4*>(m.center + (poly_off + 2u * (unsigned)j));
+            const float lx = sg.bx - sg.ax, ly = sg.by - sg.ay;
+            const float S2 = lx * sg.ay - ly * sg.ax;
+            hit |= edge_hits_segment(ed, sg.ax, sg.ay, sg.bx, sg.by, lx, ly, S2);
+          }
         }
+        if (hit) s.flags[sl * 4 + 0] = 1;
       }
-      const unsigned long long hb = __ballot(hit);
-      if (act && (lane & 7) == 0) s.flags[sl * 4 + 0] = ((hb >> lane) & 0xFFull) ? 1 : 0;  // both sides x four edges of the agent
     }
   }
   }

@@ -17,15 +17,33 @@ env = SigmaEnv(Parameters(**dict(dict(n_agents=N, scenario_type=scen, is_use_mtv
 env.reset_random(seed=1)
 acts = torch.rand((B, N, 2), device="cuda") * torch.tensor([1.0, 0.5], device="cuda") - torch.tensor([0.0, 0.25], device="cuda")
 pf, pc = env.map.list_first[0], env.map.list_count[0]
-for t in range(20):
-    env.step_autoreset(acts, seed=1, counter=t, path_first=pf, path_count=pc)
-env.sync()
 f = env.lib.cdll.sigmaenv_debug_timestamps
 f.restype = C.c_int; f.argtypes = [C.c_void_p, C.c_void_p, C.c_int32]
-ts = np.zeros((B, 16), np.uint64)
-n = f(env.h, ts.ctypes.data_as(C.c_void_p), B)
+def stamp_rows():
+    env.sync()
+    rows = np.zeros((B, 16), np.uint64)
+    return rows[:f(env.h, rows.ctypes.data_as(C.c_void_p), B)]
+# T=1 (default): 20 launches of one step, the accumulated words read back after every launch (per tile-step figures); T=k: one launch of k steps after the same
+# 20 single ones -- the stamps are then those of its last step, the accumulated words those of all its steps
+T = int(os.environ.get("T", 1))
+edge_steps = []  # per launch: (list entries, overflowed tile-steps) of every tile
+prev = stamp_rows()[:, 8:10] >> np.uint64(32)
+for t in range(20):
+    env.step_autoreset(acts, seed=1, counter=t, path_first=pf, path_count=pc)
+    if T == 1:
+        cur = stamp_rows()[:, 8:10] >> np.uint64(32)
+        edge_steps.append((cur - prev).astype(np.int64))
+        prev = cur
+n_steps = 20
+if T > 1:
+    prev = stamp_rows()[:, 8:10] >> np.uint64(32)
+    env.step_autoreset_n(acts.unsqueeze(0).expand(T, B, N, 2).contiguous(), None, seed=1, counter0=20, path_first=pf, path_count=pc)
+    edge_steps.append(((stamp_rows()[:, 8:10] >> np.uint64(32)) - prev).astype(np.int64))
+    n_steps += T
+ts = stamp_rows()
+n = len(ts)
 sub = ts[:n, [1, 10, 11, 2]].astype(np.int64)  # scan: start, end of S1 (candidate masks), end of S2 (work-list rounds), end (S3)
-stats = ts[:n, 8:10].astype(np.int64)
+stats = (ts[:n, 8:10] & np.uint64(0xFFFFFFFF)).astype(np.int64)  # (the upper halves: phase E's list statistics, read above)
 lvl = ts[:n, 12:16].astype(np.int64)
 ts = ts[:n, :8].astype(np.int64)
 ts = ts[ts[:, 0] > 0]
@@ -37,7 +55,13 @@ for k, nm in enumerate(names):
 print("tile total mean", (ts[:, 7] - ts[:, 0]).mean())
 if stats[:, 1].sum():  # accumulated over the launches above
     per = stats[:, 0] / np.maximum(stats[:, 1], 1)
-    print("scan work list: items per tile-step mean %.1f p10 %.0f p50 %.0f p90 %.0f max %.0f; rounds per step %.2f" % (per.mean(), np.percentile(per, 10), np.percentile(per, 50), np.percentile(per, 90), per.max(), stats[:, 1].sum() / (20.0 * len(stats))))
+    print("scan work list: items per tile-step mean %.1f p10 %.0f p50 %.0f p90 %.0f max %.0f; rounds per step %.2f" % (per.mean(), np.percentile(per, 10), np.percentile(per, 50), np.percentile(per, 90), per.max(), stats[:, 1].sum() / (float(n_steps) * len(stats))))
+if edge_steps and sum(int(e[:, 0].sum()) for e in edge_steps):
+    ent = np.concatenate([e[:, 0] for e in edge_steps]) / float(T)  # T = 1: one value per tile-step; T > 1: per tile, the mean over the launch's steps
+    print("edge list (%s): entries per tile-step mean %.1f p50 %.0f p99 %.0f max %.0f; overflowed tile-steps %d of %d" % (
+        "per tile-step" if T == 1 else "per tile, mean of the %d-step launch" % T, ent.mean(), np.percentile(ent, 50), np.percentile(ent, 99), ent.max(),
+        sum(int(e[:, 1].sum()) for e in edge_steps), len(ent) * T))
+
 sub = sub[(sub[:, 0] > 0) & (sub[:, 1] > 0)]
 if len(sub):
     print("scan split: S1 candidate masks %.0f, S2 work-list rounds %.0f, S3 results %.0f" % ((sub[:, 1] - sub[:, 0]).mean(), (sub[:, 2] - sub[:, 1]).mean(), (sub[:, 3] - sub[:, 2]).mean()))
