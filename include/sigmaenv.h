@@ -625,6 +625,66 @@ typedef struct sigmaenv_ppo_head_args {
 } sigmaenv_ppo_head_args_t;
 int sigmaenv_ppo_head(sigmaenv_t* h, const sigmaenv_ppo_head_args_t* a);
 
+/* ---- the optimiser step of a minibatch update (sigmaenv_optim.inc; the arithmetic: sigmaenv_optim.h) ---------------------------------------
+ * sigmaenv_optim_step: the last three lines of _train_on_batch (sigmarl/mappo_cavs.py:421-426) -- torch.nn.utils.clip_grad_norm_(loss_module.parameters(),
+ * max_grad_norm) (norm_type = 2, error_if_nonfinite = False: ONE norm over actor and critic together), optim.step() of the torch.optim.Adam of
+ * sigmarl/modules/optimization_module.py:69 (weight_decay = 0, amsgrad = False, maximize = False) and, in place of optim.zero_grad() followed by a load, the repack
+ * of every given network's weight forms -- for 1 .. 4 networks (SIGMAENV_OPTIM_MAX_NETS) of together at most 32 tensors (SIGMAENV_OPTIM_MAX_TENSORS), three launches on
+ * h's stream; nothing waits.  Per network: the sigmaenv_mlp32 handle, optionally the sigmaenv_actor handle of the same network (its bf16 form is then rewritten too;
+ * the fp32 handle must then be obs_dim -> 256 -> 256 -> 256 -> 4 with the actor's obs_dim), and eight HOST arrays of DEVICE pointers, one entry per layer as
+ * sigmaenv_mlp32_load_device takes the weights: the parameters (weights / biases, torch.nn.Linear layout, contiguous), their gradients, exp_avg and exp_avg_sq, all
+ * of the parameters' shapes; 4-byte alignment suffices (no access is wider).  The tensors are taken in the order given: per network, per layer, weight then bias.
+ *   norm      every tensor is cut into chunks of 1024 consecutive elements (the last chunk of a tensor may be short), one workgroup of 256 lanes per chunk: lane t the
+ *             chain s = 0; s += g[i]^2 over the chunk's elements i = t, t + 256, ..; per wavefront of 64 consecutive lanes the butterfly v += v[lane ^ s], s = 32, 16,
+ *             .., 1; ((w0 + w1) + w2) + w3 over the four wavefronts -> workspace[c], c the chunk's number in that sequence.  The P partials are added the same way
+ *             once more: lane t the chain over c = t, t + 256, .., the butterfly, the four wavefronts.  total_norm = sqrt(sum);
+ *             clip_coef = min(1, max_grad_norm / (total_norm + 1e-6)).  A non-finite gradient: clip_coef is NaN and every parameter becomes NaN (torch's behaviour).
+ *   Adam      g' = g clip_coef;  m = m + (g' - m) fl(1 - beta1);  v = fl(beta2) v + (fl(1 - beta2) g') g';  p = p - step_size (m / (sqrt(v) / sqrt_bc2 + fl(eps)))
+ *             with step_size = fl(lr / (1 - beta1^t)) and sqrt_bc2 = fl(sqrt(1 - beta2^t)) formed in double on the host and rounded once; p, m, v are updated in
+ *             place, the gradients are read, never written.  fp32, one IEEE operation per operator, correctly rounded division and square root, no contraction.
+ *   result    device f32 [2] := total_norm, clip_coef.
+ *   repack    every form the handles hold -- exact fragments, their transposes, the split pairs, both bias vectors, the bf16 form -- by the per-slot functions
+ *             sigmaenv_mlp32_create / sigmaenv_actor_create / *_load_device run (sigmaenv_pack.h), read from the updated parameters themselves: the handles then hold
+ *             word for word what *_create makes from those numbers.  The split form's range predicate is reduced into each network's own device word.
+ * No atomics in any sum; the shape of every sum is a function of the tensors' element counts alone: the same inputs give the same bits on every run.
+ * workspace: device f32 [P] (sigmaenv_optim_workspace: *n_floats := P, the chunks of all tensors; it reads the handles' shapes only).
+ * The deferred mode.  The range word decides between SPLIT and EXACT for the next forward, and reading it is a host wait -- which sigmaenv_mlp32_load_device pays on
+ * every call.  The training loop never needs the answer: sigmaenv_mlp32_forward_save runs the EXACT chain whatever mode is in force.  So the step does not wait: it
+ * leaves every given sigmaenv_mlp32 with EXACT in force -- always correct, the exact form is valid for every weight --, sigmaenv_mlp32_get_mode reports EXACT, and
+ * sigmaenv_mlp32_set_mode(SPLIT) is refused but remembered, as it is for a handle outside the range.  sigmaenv_mlp32_resolve_mode(h, m) copies m's range word back on
+ * h's stream and waits for it -- the only host wait of the device route, needed once, before the next rollout (after the last minibatch of
+ * sigmarl/mappo_cavs.py:421-426's loop) -- and then sets the mode in force exactly as sigmaenv_mlp32_load_device would have: the mode last accepted or remembered by
+ * set_mode when the weights allow it, else EXACT.  On a handle that no step has touched it re-derives the mode from the weights the handle holds.
+ * More than 4 networks or 32 tensors, a null handle, pointer array or tensor, a tensor that is not 4-byte aligned, an actor handle of another shape, t < 1, a beta
+ * outside [0, 1), or eps, lr or max_grad_norm negative or not finite: SIGMAENV_EINVAL with sigmaenv_last_error set, before any launch. */
+#define SIGMAENV_OPTIM_MAX_NETS 4
+#define SIGMAENV_OPTIM_MAX_TENSORS 32
+typedef struct sigmaenv_optim_net {
+  sigmaenv_mlp32_t* mlp32;
+  sigmaenv_actor_t* actor;           /* optional (NULL): the bf16 handle of the same network */
+  float* const* weights;             /* [n_layers] device pointers, updated in place */
+  float* const* biases;
+  const float* const* grad_weights;  /* read */
+  const float* const* grad_biases;
+  float* const* exp_avg_weights;     /* updated in place */
+  float* const* exp_avg_biases;
+  float* const* exp_avg_sq_weights;
+  float* const* exp_avg_sq_biases;
+} sigmaenv_optim_net_t;
+typedef struct sigmaenv_optim_args {
+  int32_t n_networks;
+  int32_t reserved0;                 /* zero */
+  sigmaenv_optim_net_t net[SIGMAENV_OPTIM_MAX_NETS];
+  double lr, beta1, beta2, eps, max_grad_norm;
+  int64_t t;                         /* the step count of THIS step: 1 for the first */
+  float* workspace;
+  float* result;
+  int32_t reserved[4];               /* zero */
+} sigmaenv_optim_args_t;
+int sigmaenv_optim_workspace(sigmaenv_t* h, const sigmaenv_optim_args_t* a, uint64_t* n_floats);
+int sigmaenv_optim_step(sigmaenv_t* h, const sigmaenv_optim_args_t* a);
+int sigmaenv_mlp32_resolve_mode(sigmaenv_t* h, sigmaenv_mlp32_t* m);
+
 /* The priority module (sigmarl/modules/priority_module.py).  sigmaenv_priority_forward: priority_net (MultiAgentMLP depth 2: obs_dim -> 256 -> 256 -> 2, Tanh,
  * :34-51) on `obs` (device f32 [B * N, obs_dim], or NULL for SIGMAENV_BUF_OBS), NormalParamExtractor ("biased_softplus_1.0", as the actor's) and a 1-D
  * TanhNormal on [-1, 1] (:52-66): score = clamp(tanh(loc + scale z), -1 + 1e-6, 1 - 1e-6), z from draw 7100 of (seed, counter, env, agent) (0 when

@@ -124,6 +124,7 @@ class Mlp32:
         self._handles = {}
         self._handle_version = {}  # library path -> the version of the weights its handle holds (0: those of the constructor)
         self._version, self._loaded = 0, None  # ``load``: count, and (weights, biases, ready event, stream) of the device snapshot
+        self._stepped_source = None  # after ``learn.Adam.step``: the (weights, biases) a snapshot is taken from when a handle of another library needs one
         lin = [m for m in mlp.modules() if isinstance(m, torch.nn.Linear)]
         if not (2 <= len(lin) <= 4) or any(m.out_features != 256 for m in lin[:-1]) or lin[-1].out_features > 32:
             raise ValueError("expected 2-4 Linear layers with hidden width 256 and at most 32 outputs")
@@ -188,6 +189,7 @@ class Mlp32:
 
     def _pack(self, group):
         """The snapshot of the last ``load`` into the handle of ``group``'s library."""
+        self._ensure_snapshot(group[0])
         lib = group[0].lib
         h = self.handle(lib)
         wp, bp = self._device_pointers()
@@ -202,7 +204,24 @@ class Mlp32:
 
     def _snapshot(self, envs, ws, bs):
         """A device copy of the parameters (contiguous; ~1 MB) on the first env's stream, after what torch's current stream holds (the optimiser's kernels)."""
-        first = envs[0]
+        self._take_snapshot(envs[0], ws, bs)
+        self._version += 1
+
+    def _ensure_snapshot(self, env):
+        """``learn.Adam.step`` packs from the parameters themselves and leaves no snapshot: a handle of another library takes one when it is next used."""
+        if self._loaded is None:
+            self._take_snapshot(env, *self._stepped_source)
+
+    def _stepped(self, env, pairs):
+        """``learn.Adam.step`` has updated the parameters ``pairs`` in place and repacked this network's handle in ``env``'s library on ``env``'s stream: that
+        handle holds the new version, every other one is stale until its next use (``handle``), the mode in force is exact until ``resolve`` (``learn.Adam``)."""
+        self._version += 1
+        self._loaded, self._stepped_source = None, ([w.detach() for w, _ in pairs], [b.detach() for _, b in pairs])
+        self._handle_version[env.lib.path] = self._version
+        self._remember(pairs)
+        self.mode = "exact"
+
+    def _take_snapshot(self, first, ws, bs):
         with torch.cuda.device(first.device):
             first.stream.wait_stream(torch.cuda.current_stream(first.device))
             with torch.cuda.stream(first.stream):
@@ -211,7 +230,6 @@ class Mlp32:
                 ready = torch.cuda.Event()
                 ready.record(first.stream)
         self._loaded = (ws, bs, ready, first.stream)
-        self._version += 1
 
     def _mode_in_force(self, lib) -> str:
         return "split" if lib.mlp32_get_mode(self.handle(lib)) == capi.MLP32_SPLIT else "exact"
@@ -582,6 +600,7 @@ class Actor:
         return ent[1]
 
     def _pack_bf16(self, group):
+        self._mlp32._ensure_snapshot(group[0])
         lib = group[0].lib
         h = self._bf16_handle(lib)
         wp, bp = self._mlp32._device_pointers()

@@ -116,6 +116,23 @@ class PpoHeadArgs(C.Structure):
     ]
 
 
+OPTIM_MAX_NETS, OPTIM_MAX_TENSORS = 4, 32  # SIGMAENV_OPTIM_MAX_NETS, SIGMAENV_OPTIM_MAX_TENSORS
+
+
+class OptimNet(C.Structure):
+    """``sigmaenv_optim_net_t``: one network of ``sigmaenv_optim_step`` -- its handles and the per-layer device pointers of parameters, gradients and moments."""
+
+    _fields_ = [("mlp32", C.c_void_p), ("actor", C.c_void_p), ("weights", C.c_void_p), ("biases", C.c_void_p), ("grad_weights", C.c_void_p), ("grad_biases", C.c_void_p),
+                ("exp_avg_weights", C.c_void_p), ("exp_avg_biases", C.c_void_p), ("exp_avg_sq_weights", C.c_void_p), ("exp_avg_sq_biases", C.c_void_p)]
+
+
+class OptimArgs(C.Structure):
+    """``sigmaenv_optim_args_t`` (sigmaenv_optim_step): the networks, Adam's scalars, the step count, the workspace and the device result."""
+
+    _fields_ = [("n_networks", C.c_int32), ("reserved0", C.c_int32), ("net", OptimNet * OPTIM_MAX_NETS), ("lr", C.c_double), ("beta1", C.c_double), ("beta2", C.c_double),
+                ("eps", C.c_double), ("max_grad_norm", C.c_double), ("t", C.c_int64), ("workspace", C.c_void_p), ("result", C.c_void_p), ("reserved", C.c_int32 * 4)]
+
+
 PPO_SUMS = 5  # SIGMAENV_PPO_SUMS: partial sums per workgroup of 256 rows in sigmaenv_ppo_head's workspace
 PPO_RESULT = ("loss_objective", "loss_entropy", "loss_critic", "entropy", "clip_fraction", "kl_approx")  # result[0 .. 5]
 
@@ -242,6 +259,9 @@ _PRODUCT_ONLY = {
     "mlp32_backward_indexed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
                                          C.c_void_p, C.c_void_p]),
     "ppo_head": (C.c_int, [C.c_void_p, C.POINTER(PpoHeadArgs)]),
+    "optim_workspace": (C.c_int, [C.c_void_p, C.POINTER(OptimArgs), C.POINTER(C.c_uint64)]),
+    "optim_step": (C.c_int, [C.c_void_p, C.POINTER(OptimArgs)]),
+    "mlp32_resolve_mode": (C.c_int, [C.c_void_p, C.c_void_p]),
     "actor_forward_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64,
                                     C.c_int32]),
     "rollout_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64,

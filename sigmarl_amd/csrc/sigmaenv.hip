@@ -2660,6 +2660,8 @@ extern "C" int sigmaenv_trig_selftest(sigmaenv_t* h, int32_t kind, int32_t n, co
 #include "sigmaenv_mlp32.inc"
 #include "sigmaenv_load.inc"
 #include "sigmaenv_grad.inc"
+#include "sigmaenv_optim.h"
+#include "sigmaenv_optim.inc"
 #include "sigmaenv_wrappers.inc"
 #include "sigmaenv_learn.inc"
 #include "sigmaenv_ppo.inc"

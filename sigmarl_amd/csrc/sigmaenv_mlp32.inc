@@ -462,6 +462,8 @@ extern "C" int sigmaenv_mlp32_create(int32_t n_layers, const int32_t* dims, cons
   }
   m->split_ok = m->split_fits && !out_of_range;
   if (!m->split_ok) m->mode = SIGMAENV_MLP32_EXACT;
+  const uint32_t word = out_of_range ? 1u : 0u;  // (what a load of these weights would have reduced: sigmaenv_mlp32_resolve_mode may read it)
+  if (hipMemcpy(m->range_word, &word, 4, hipMemcpyHostToDevice) != hipSuccess) { sigmaenv_mlp32_destroy(m); return SIGMAENV_EHIP; }
   *out = m;
   return SIGMAENV_OK;
 }

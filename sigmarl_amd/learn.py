@@ -12,9 +12,12 @@ and the learner's side, ``_train_epoch`` / ``_train_on_batch`` (``sigmarl/mappo_
   ``Actor.apply`` / ``Critic.apply(index=)``   the networks on the frames of a minibatch, read from the records where they lie, with a ``grad_fn``
   ``ppo_head``                     ``sigmaenv_ppo_head``: torchrl's ``ClipPPOLoss`` as ``sigmarl/modules/optimization_module.py:44-66`` configures it, one fused launch
                                    from the networks' outputs and the records to the loss terms and both ``dout`` tensors
-  ``update``                       the epochs x minibatches loop: apply -> head -> backward -> ``clip_grad_norm_`` -> ``optim.step()`` -> ``load``
-Gradient clipping, Adam and the prioritized buffer's priorities stay in torch.  torchrl is absent here: GAE's and the loss's semantics are restated from its published
-behaviour (the arithmetic contracts are in ``include/sigmaenv.h``).
+  ``Adam``                         ``sigmaenv_optim_step``: ``clip_grad_norm_`` over all networks in one norm, ``torch.optim.Adam``'s step and the repack of every
+                                   network's weight forms, three launches and no host wait (``:421-426``); ``resolve`` = the one wait, before the next rollout
+  ``update``                       the epochs x minibatches loop: apply -> head -> backward -> ``Adam.step`` (the device route), or with a torch optimiser
+                                   -> ``clip_grad_norm_`` -> ``optim.step()`` -> ``load``
+The prioritized buffer's priorities stay in torch.  torchrl is absent here: GAE's and the loss's semantics are restated from its published behaviour (the
+arithmetic contracts are in ``include/sigmaenv.h``).
 """
 from __future__ import annotations
 
@@ -23,7 +26,7 @@ import ctypes as C
 import torch
 
 from . import capi
-from .actor import check_record
+from .actor import Actor, Mlp32, check_record, load_source, source_pairs
 
 TD_GAMMA = 0.9  # compute_td_error's discount as the trainer calls it (mappo_cavs.py:383, :454) -- not Parameters.gamma
 
@@ -182,6 +185,180 @@ def minibatches(n_frames: int, minibatch_size: int, generator: torch.Generator |
     return list(torch.randperm(n, device=dev, generator=generator).to(torch.int32).split(mb))
 
 
+class Adam:
+    """``torch.optim.Adam`` as the reference builds it (``sigmarl/modules/optimization_module.py:69``: ``weight_decay=0``, ``amsgrad=False``, ``maximize=False``)
+    with ``clip_grad_norm_`` in front and the networks' repack behind, on the device (``sigmaenv_optim_step``; every formula and the order of every sum:
+    ``include/sigmaenv.h``, ``sigmarl_amd/csrc/sigmaenv_optim.h``).  ``networks``: a sequence of ``(Actor | Mlp32, torch module)`` pairs -- the device network and
+    the module it was built or last loaded from, on ``env``'s device; at most 4 networks of together 32 tensors.  Owns ``exp_avg`` / ``exp_avg_sq`` of every
+    parameter (``state``: per network, per layer, weight then bias -- the order of ``module.parameters()``) and the step count ``t`` (the steps taken so far).
+    ``lr`` is a plain attribute: the reference's linear decay (``sigmarl/mappo_cavs.py:520-523``) sets it between updates."""
+
+    def __init__(self, env, networks, lr: float, betas=(0.9, 0.999), eps: float = 1e-8):
+        self.env, self.lr, self.betas, self.eps, self.t = env, float(lr), (float(betas[0]), float(betas[1])), float(eps), 0
+        self.networks = []
+        for k, pair in enumerate(networks):
+            try:
+                net, module = pair
+            except (TypeError, ValueError):
+                raise TypeError("Adam: networks is a sequence of (Actor | Mlp32, torch module) pairs") from None
+            if not isinstance(net, (Actor, Mlp32)):
+                raise TypeError(f"Adam: network {k} is neither an Actor nor an Mlp32")
+            self.networks.append((net, module))
+        n_tensors = sum(2 * (len(self._mlp32(net)._keep[0]) - 1) for net, _ in self.networks)
+        if not 1 <= len(self.networks) <= capi.OPTIM_MAX_NETS or n_tensors > capi.OPTIM_MAX_TENSORS:
+            raise ValueError(f"Adam: {len(self.networks)} networks of {n_tensors} tensors: 1 to {capi.OPTIM_MAX_NETS} networks of at most {capi.OPTIM_MAX_TENSORS} tensors")
+        self.state = [[(torch.zeros_like(p, memory_format=torch.contiguous_format), torch.zeros_like(p, memory_format=torch.contiguous_format)) for p in ps]
+                      for ps in self._checked(grads=False)[0]]
+        self._result = None
+
+    @staticmethod
+    def _mlp32(net) -> Mlp32:
+        return net._mlp32 if isinstance(net, Actor) else net
+
+    def parameters(self) -> list:
+        """Every parameter in the optimiser's order: per network, per layer, weight then bias."""
+        return [t for _, module in self.networks for q in source_pairs(module) for t in q]
+
+    def _checked(self, grads: bool):
+        """(parameters, gradients) per network, checked before any device call: float32 CUDA tensors on the env's device (``TypeError``), contiguous and of the
+        network's shapes (``ValueError``); with ``grads`` every parameter has a ``.grad`` of its own shape (a missing one: ``ValueError`` naming the parameter)."""
+        dev, ps, gs = self.env.device, [], []
+        for k, (net, module) in enumerate(self.networks):
+            load_source(self._mlp32(net)._keep[0], module, dev)
+            names = {id(t): n for n, t in module.named_parameters()} if isinstance(module, torch.nn.Module) else {}
+            par = [t for q in source_pairs(module) for t in q]
+            grd = []
+            for i, t in enumerate(par):
+                what = f"network {k} parameter {names.get(id(t), ('weight', 'bias')[i % 2] + ' of layer ' + str(i // 2))}"
+                if not t.is_contiguous():
+                    raise ValueError(f"Adam: {what} is not contiguous (the step updates it in place)")
+                if not grads:
+                    continue
+                g = t.grad
+                if g is None:
+                    raise ValueError(f"Adam.step: {what} has no .grad")
+                if not (g.is_cuda and g.dtype == torch.float32 and g.device == dev):
+                    raise TypeError(f"Adam.step: the .grad of {what} must be a float32 CUDA tensor on {dev}")
+                if g.shape != t.shape:
+                    raise ValueError(f"Adam.step: the .grad of {what} has shape {list(g.shape)}, the parameter {list(t.shape)}")
+                grd.append(g.contiguous())
+            ps.append(par)
+            gs.append(grd)
+        return ps, gs
+
+    def step(self, max_grad_norm: float) -> torch.Tensor:
+        """One optimiser step from the parameters' ``.grad``: the gradients of ALL networks clipped to ``max_grad_norm`` in one norm, Adam, and every weight form of
+        every network repacked from the updated parameters -- three launches on the env's stream after everything torch's current stream holds, which then waits
+        for them (``ppo_head``'s discipline); nothing waits on the host.  The gradients are then set to ``None`` (``optim.zero_grad()``).  The networks hold the
+        new weights without a ``load`` (``apply``'s stale-weight guard sees them fresh); each runs EXACT until ``resolve``; a handle of another library than the
+        env's is brought up to date when it is next used.  Refusals (before any launch): a missing ``.grad``, a CPU tensor, a wrong shape, ``t + 1 < 1``, a bad
+        scalar.  Returns the device result ``[total_norm, clip_coef]``."""
+        env, dev = self.env, self.env.device
+        t = int(self.t) + 1
+        mg = float(max_grad_norm)
+        if t < 1:
+            raise ValueError(f"Adam.step: the step count t = {t} must be >= 1")
+        b1, b2 = self.betas
+        for v, name in ((self.lr, "lr"), (self.eps, "eps"), (mg, "max_grad_norm")):
+            if not (v >= 0.0 and v != float("inf")):
+                raise ValueError(f"Adam.step: {name} = {v} must be finite and not negative")
+        if not (0.0 <= b1 < 1.0 and 0.0 <= b2 < 1.0):
+            raise ValueError(f"Adam.step: betas = {self.betas} must be in [0, 1)")
+        ps, gs = self._checked(grads=True)
+        a = capi.OptimArgs()
+        a.n_networks = len(self.networks)
+        keep, used = [], []
+        for k, (net, _) in enumerate(self.networks):
+            m32, n = self._mlp32(net), len(ps[k]) // 2
+            PA = C.c_void_p * n
+            e = a.net[k]
+            e.mlp32 = m32.handle(env.lib)
+            if isinstance(net, Actor) and (net.precision == "bf16" or env.lib.path in net._bf16):
+                e.actor = net._bf16_handle(env.lib)
+            mom = self.state[k]
+            cols = {"weights": ps[k][0::2], "biases": ps[k][1::2], "grad_weights": gs[k][0::2], "grad_biases": gs[k][1::2],
+                    "exp_avg_weights": [q[0] for q in mom[0::2]], "exp_avg_biases": [q[0] for q in mom[1::2]],
+                    "exp_avg_sq_weights": [q[1] for q in mom[0::2]], "exp_avg_sq_biases": [q[1] for q in mom[1::2]]}
+            for name, ts in cols.items():
+                arr = PA(*[x.data_ptr() for x in ts])
+                keep.append(arr)
+                setattr(e, name, C.cast(arr, C.c_void_p))
+                used += ts
+        a.lr, a.beta1, a.beta2, a.eps, a.max_grad_norm, a.t = self.lr, b1, b2, self.eps, mg, t
+        nf = C.c_uint64()
+        rc = env.lib.optim_workspace(env.h, C.byref(a), C.byref(nf))
+        if rc != 0:
+            raise RuntimeError(f"sigmaenv_optim_workspace failed with code {rc}: {env.lib.last_error(env.h).decode()}")
+        ws = torch.empty((max(int(nf.value), 1),), dtype=torch.float32, device=dev)
+        result = torch.empty((2,), dtype=torch.float32, device=dev)
+        a.workspace, a.result = ws.data_ptr(), result.data_ptr()
+        cur = torch.cuda.current_stream(dev)
+        with torch.cuda.device(dev):  # on the env's stream after what torch's current stream holds (the backward pass), which then waits for it
+            env.stream.wait_stream(cur)
+            rc = env.lib.optim_step(env.h, C.byref(a))
+            if rc != 0:
+                raise RuntimeError(f"sigmaenv_optim_step failed with code {rc}: {env.lib.last_error(env.h).decode()}")
+            cur.wait_stream(env.stream)
+        for x in used + [ws, result]:
+            x.record_stream(env.stream)
+        self.t = t
+        for k, (net, module) in enumerate(self.networks):
+            for p in ps[k]:
+                p.grad = None
+                torch.autograd.graph.increment_version(p)  # (the kernel wrote it in place: a graph that saved it must not be run backwards)
+            m32 = self._mlp32(net)
+            m32._stepped(env, source_pairs(module))
+            if a.net[k].actor:
+                net._bf16_version[env.lib.path] = m32._version
+        self._result = result
+        return result
+
+    def resolve(self) -> list:
+        """The mode in force of every network after the steps so far (``sigmaenv_mlp32_resolve_mode``): waits for each network's 4-byte range word on the env's
+        stream -- the only host wait of the device route, needed once before the next rollout -- and returns the modes (``"split"`` / ``"exact"``), which the
+        networks' ``mode`` then hold too."""
+        env, modes = self.env, []
+        for net, _ in self.networks:
+            m32 = self._mlp32(net)
+            rc = env.lib.mlp32_resolve_mode(env.h, m32.handle(env.lib, env))
+            if rc != 0:
+                raise RuntimeError(f"sigmaenv_mlp32_resolve_mode failed with code {rc}: {env.lib.last_error(env.h).decode()}")
+            m32.mode = m32._mode_in_force(env.lib)
+            modes.append(m32.mode)
+        return modes
+
+    def _torch_params(self, optim) -> list:
+        tp = [p for g in optim.param_groups for p in g["params"]]
+        mine = self.parameters()
+        if len(tp) != len(mine) or any(x is not y for x, y in zip(tp, mine)):
+            raise ValueError("Adam: the torch optimiser must hold the same parameters in the same order (per network, per layer, weight then bias)")
+        return tp
+
+    def to_torch(self, optim: torch.optim.Adam) -> None:
+        """The moments and the step count into ``optim`` (a ``torch.optim.Adam`` over the same parameters in the same order): copies, in torch's state format."""
+        tp = self._torch_params(optim)
+        flat = [q for mom in self.state for q in mom]
+        with torch.cuda.device(self.env.device):
+            for p, (m, v) in zip(tp, flat):
+                optim.state[p] = {"step": torch.tensor(float(self.t)), "exp_avg": m.clone(), "exp_avg_sq": v.clone()}
+
+    def from_torch(self, optim: torch.optim.Adam) -> None:
+        """The moments and the step count out of ``optim`` (copies); a parameter without state there has zero moments.  The step counts must agree."""
+        tp = self._torch_params(optim)
+        steps = {int(optim.state[p]["step"]) for p in tp if p in optim.state and "step" in optim.state[p]}
+        if len(steps) > 1:
+            raise ValueError(f"Adam.from_torch: the parameters' step counts differ: {sorted(steps)}")
+        flat = [q for mom in self.state for q in mom]
+        for p, (m, v) in zip(tp, flat):
+            st = optim.state.get(p, {})
+            for mine, key in ((m, "exp_avg"), (v, "exp_avg_sq")):
+                if key in st:
+                    mine.copy_(st[key])
+                else:
+                    mine.zero_()
+        self.t = steps.pop() if steps else 0
+
+
 def update(env, actor, critic, actor_module, critic_module, optim, batch: dict, params=None, *, num_epochs: int | None = None, minibatch_size: int | None = None,
            clip_epsilon: float | None = None, entropy_coeff: float | None = None, max_grad_norm: float | None = None, critic_coeff: float = 1.0, seed: int = 0,
            counter0: int = 0, generator: torch.Generator | None = None) -> list:
@@ -189,7 +366,8 @@ def update(env, actor, critic, actor_module, critic_module, optim, batch: dict, 
     steps of ``Actor.apply`` / ``Critic.apply(index=)`` -> ``ppo_head`` -> ``loss.backward()`` -> ``clip_grad_norm_`` over both modules' parameters ->
     ``optim.step()`` -> ``optim.zero_grad()`` -> ``actor.load`` / ``critic.load``; every epoch draws a new ``minibatches`` permutation and uses its full chunks.
     ``actor_module`` / ``critic_module`` are the torch modules the device networks were built or last loaded from (on the device), ``optim`` the optimiser over
-    their parameters.  ``num_epochs``, ``minibatch_size``, ``clip_epsilon``, ``entropy_coeff`` (``entropy_eps``) and ``max_grad_norm`` come from ``params`` (a
+    their parameters.  With ``optim`` a ``learn.Adam`` over both networks the step takes the device route instead: ``Adam.step(max_grad_norm)`` in place of the last
+    five, no ``load`` and no host wait inside the loop, one ``Adam.resolve()`` after the last minibatch.  ``num_epochs``, ``minibatch_size``, ``clip_epsilon``, ``entropy_coeff`` (``entropy_eps``) and ``max_grad_norm`` come from ``params`` (a
     ``Parameters``; default: the env's) unless given.  Step ``k`` keys its entropy draws with ``(seed, counter0 + k)``.  Returns the ``info`` of every step."""
     p = params if params is not None else getattr(env, "parameters", None)
 
@@ -208,6 +386,7 @@ def update(env, actor, critic, actor_module, critic_module, optim, batch: dict, 
     frames = T * B
     low, high = actor._keep[-2], actor._keep[-1]
     pars = list(actor_module.parameters()) + list(critic_module.parameters())
+    device_route = isinstance(optim, Adam)
     infos, k = [], 0
     for _ in range(num_epochs):
         for index in minibatches(frames, mb, generator, env.device)[: frames // mb]:
@@ -216,11 +395,16 @@ def update(env, actor, critic, actor_module, critic_module, optim, batch: dict, 
             loss, info = ppo_head(env, out, value, batch, index, low=low, high=high, clip_epsilon=clip_epsilon, entropy_coeff=entropy_coeff, critic_coeff=critic_coeff,
                                   seed=seed, counter=counter0 + k)
             loss.backward()
-            torch.nn.utils.clip_grad_norm_(pars, max_grad_norm)
-            optim.step()
-            optim.zero_grad()
-            actor.load(env, actor_module)
-            critic.load(env, critic_module)
+            if device_route:
+                optim.step(max_grad_norm)
+            else:
+                torch.nn.utils.clip_grad_norm_(pars, max_grad_norm)
+                optim.step()
+                optim.zero_grad()
+                actor.load(env, actor_module)
+                critic.load(env, critic_module)
             infos.append(info)
             k += 1
+    if device_route and k:
+        optim.resolve()
     return infos

@@ -3,13 +3,18 @@
 actor D -> 256^3 -> 4, critic N D -> 256^3 -> 1) and the reference's minibatch_size (default 512 frames = 8192 actor rows), on a learn.collect batch of T x B frames:
   device   Actor.apply / Critic.apply(index=) read the frames where they lie, learn.ppo_head (sigmaenv_ppo_head), loss.backward() (sigmaenv_mlp32_backward_indexed)
   torch    index_select gathers of the observations and the four records, the torch.nn modules, the same loss written in torch, autograd; fp32, same device
-Both routes end with the .grad of every parameter of both networks.  clip_grad_norm_, Adam and load are the same in both and are not timed.  HIP events around each
-call; one untimed call of each route, then REPS (default 3) repetitions with the two routes alternating inside one process.  A report, not a bound.  Writes the JSON
-to the path given (default profiles/ppo_update_timing.json) and prints it."""
+Both routes end with the .grad of every parameter of both networks; the tail of the update is not in these figures.  HIP events around each call; one untimed call
+of each route, then REPS (default 3) repetitions with the two routes alternating inside one process.
+``whole_update``, measured afterwards: the device route above followed by either tail of a minibatch update (tools/optim_step_timing.py times the tails alone) --
+  device   learn.Adam.step (sigmaenv_optim_step: clip, Adam, repack; no host wait, one Adam.resolve() at the end of a run)
+  parent   clip_grad_norm_ + torch.optim.Adam.step + zero_grad + actor.load + critic.load
+by HIP events around one update and by the host's wall clock over UPDATES (default 8) consecutive updates without a synchronisation in between; same alternation.
+A report, not a bound.  Writes the JSON to the path given (default profiles/ppo_update_timing.json) and prints it."""
 import json
 import math
 import os
 import sys
+import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -22,6 +27,7 @@ from sigmarl_amd.params import Parameters  # noqa: E402
 
 B, N, T, REPS = int(os.environ.get("B", 512)), int(os.environ.get("N", 16)), int(os.environ.get("T", 16)), int(os.environ.get("REPS", 3))
 MB = int(os.environ.get("MINIBATCH", Parameters().minibatch_size))
+UPDATES = int(os.environ.get("UPDATES", 8))
 LOW, HIGH, EPS, CE = [-1.0, -0.6], [1.0, 0.6], 0.2, 1e-4
 BIAS, LOG_SQRT_2PI, LOG2 = 0.5254587192925021, 0.91893853320467274, 0.69314718055994531
 
@@ -98,6 +104,45 @@ def main():
             ms[k].append(timed(fn))
     res = {"n_agents": N, "n_envs": B, "steps": T, "frames": frames, "minibatch_frames": M, "actor_rows": M * N, "critic_rows": M, "obs_dim": D, "reps": REPS,
            "ms": ms, "best_ms": {k: min(v) for k, v in ms.items()}}
+    # a whole minibatch update: the device route to the gradients, then either tail
+    dev_opt, par_opt = learn.Adam(env, [(actor, amod), (critic, cmod)], lr=3e-4), torch.optim.Adam(pars, lr=3e-4)
+
+    def whole_device():
+        device()
+        dev_opt.step(1.0)
+
+    def whole_parent():
+        device()
+        torch.nn.utils.clip_grad_norm_(pars, 1.0)
+        par_opt.step()
+        par_opt.zero_grad()
+        actor.load(env, amod)
+        critic.load(env, cmod)
+
+    whole = {"device": (whole_device, dev_opt.resolve), "parent": (whole_parent, lambda: None)}
+
+    def wall(fn, finish):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(UPDATES):
+            fn()
+        finish()
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) * 1e3 / UPDATES
+
+    for fn, finish in whole.values():
+        fn()
+        finish()
+    torch.cuda.synchronize()
+    ev, wl = {k: [] for k in whole}, {k: [] for k in whole}
+    for _ in range(REPS):
+        for k, (fn, finish) in whole.items():
+            ev[k].append(timed(fn))
+            finish()
+        for k, (fn, finish) in whole.items():
+            wl[k].append(wall(fn, finish))
+    res["whole_update"] = {"updates_per_wall_run": UPDATES, "event_ms": ev, "wall_ms_per_update": wl,
+                           "best": {"event_ms": {k: min(v) for k, v in ev.items()}, "wall_ms_per_update": {k: min(v) for k, v in wl.items()}}}
     actor.close()
     critic.close()
     env.close()
