@@ -685,6 +685,63 @@ int sigmaenv_optim_workspace(sigmaenv_t* h, const sigmaenv_optim_args_t* a, uint
 int sigmaenv_optim_step(sigmaenv_t* h, const sigmaenv_optim_args_t* a);
 int sigmaenv_mlp32_resolve_mode(sigmaenv_t* h, sigmaenv_mlp32_t* m);
 
+/* ---- the prioritized replay buffer (sigmaenv_prb.inc; the arithmetic: sigmaenv_prb.h) -----------------------------------------------------
+ * Parameters.is_prb: torchrl's TensorDictPrioritizedReplayBuffer(alpha = 0.7, beta = 0.6, priority_key = "td_error") sized frames_per_batch and overwritten whole
+ * by extend every iteration (sigmarl/mappo_cavs.py:321-332), its sample() before every minibatch (:397-407) and _update_priorities_after_training behind every
+ * optimiser step (:431-456), as a device object.  torchrl is third-party and absent: the formulas below are the specification, restated from the published
+ * behaviour of torchrl 0.9.0.  F = capacity, len <= F the filled length, q[f] the stored priority of frame f, M = n_index.
+ *   create    allocates everything the other calls use -- the leaves, the levels, the words total / q_min, the refresh workspace --: none of them allocates, frees
+ *             or waits on the host (sigmaenv_prb_get excepted).  alpha, beta, eps are rounded to fp32 once.  destroy frees the object (not h).
+ *   extend    REPLACES the content: len = n, q[f] = powf(td[f] + eps, alpha) for f < n (td: device f32 [n], the td_priority of sigmaenv_gae); no ring cursor.  Leaves
+ *             in [len, F) count as 0 for the sums and +inf for the minimum.  Then every level is rebuilt.
+ *   the hierarchy   fan-out 256: level 0 = the leaves, level k + 1 = one (sum, min) per 256 entries of level k until a level has <= 256 entries; total / q_min =
+ *             the sum / min of the one node over the top level.  A node's sum: lane l of 64 the chain ((e_{4l} + e_{4l+1}) + e_{4l+2}) + e_{4l+3}, then the
+ *             inclusive scan over the lanes I_l = I_l + I_{l-d} (l >= d), d = 1, 2, .., 32; the sum is I_63.  The order of every operation: sigmaenv_prb.h.
+ *   sample    with replacement, proportional to q.  Slot m: u_m = ((k >> 8) + 0.5) 2^-24 of the generator's word k keyed (seed, counter, env = m, agent = 0), draw
+ *             7400 (beside 7000 / 7100 / 7200 / 7300);  mass_m = u_m total;  index_out[m] = the lower-bound scan of the prefix sums -- the first f with
+ *             mass < q[0] + .. + q[f], clamped to len - 1 -- found by descending the levels: at a node the smallest child j with r < S_j (the children's
+ *             inclusive prefixes), then r - S_{j-1} below; if no child qualifies (rounding, u = 1, a NaN) the last child below len.  The index is always in
+ *             [0, len).  weight_out[m] = powf(q[index] / q_min, -beta) (<= 1; exactly 1 at a minimal leaf).  total and q_min are read on the device.
+ *             ClipPPOLoss of torchrl 0.9.0 does not read "_weight": the weights are an output and sigmaenv_ppo_head does not take them.
+ *   refresh   slot m, frame f = index[m]: with v = state_value[m], v' = next_state_value[m] (the critic after the step, on observation[f] and on the record row's
+ *             observation part), reward and done read IN PLACE from row f of slab [F, W] (W = N*(D+1)+1, offsets N*D + i and N*(D+1), contiguous frames):
+ *             x_m = (sum over i = 0 .. N-1, in that order, of |(r[f,i] + (td_gamma * v') * nd) - v|) / N, nd = 1 - done[f] -- sigmaenv_gae's td_priority expression;
+ *             min / max over the M slots OF THIS MINIBATCH (ordered partials, no atomics);  td_m = clamp(((x_m - min) / max(max - min, 1e-3)) * 10, 1e-3, 10);
+ *             q[f] = powf(td_m + eps, alpha) (duplicate slots of a frame write the same bits);  td_out (optional, device f32 [M]) := td_m;  then every level is
+ *             rebuilt in full: after refresh every level equals bit for bit what extend builds from the same leaves.  An index entry outside [0, len) is never
+ *             used as an address: its slot takes no part in min / max and writes nothing (td_out[m] included).  M <= max(F, 65536).
+ *   get       copies to the HOST and waits (tests, inspection, checkpoints): SIGMAENV_PRB_LEAVES f32 [len], _TOTAL / _QMIN f32 [1], _LEN / _N_LEVELS i32 [1] (levels,
+ *             the leaves included), _LEVEL_SUM + k / _LEVEL_MIN + k f32 [n_k] for k = 1 .. n_levels - 1 (n_0 = F, n_{k+1} = ceil(n_k / 256)).
+ * fp32, one IEEE operation per operator, no contraction; powf is the device's (OCML): the two powers are the only operations a host twin cannot reproduce to the
+ * bit.  No atomics: the same inputs give the same bits on every run.  Everything is enqueued on h's stream.
+ * A null handle, a null or misaligned tensor, M < 1, n < 1 or n > capacity, capacity outside [1, 2^30], alpha outside [0, 1], beta < 0, eps < 0, td_gamma outside
+ * [0, 1], sample / refresh on an empty buffer: SIGMAENV_EINVAL with sigmaenv_last_error set, before any launch. */
+#define SIGMAENV_PRB_LEAVES 0
+#define SIGMAENV_PRB_TOTAL 1
+#define SIGMAENV_PRB_QMIN 2
+#define SIGMAENV_PRB_LEN 3
+#define SIGMAENV_PRB_N_LEVELS 4
+#define SIGMAENV_PRB_LEVEL_SUM 16
+#define SIGMAENV_PRB_LEVEL_MIN 32
+typedef struct sigmaenv_prb sigmaenv_prb_t;
+typedef struct sigmaenv_prb_refresh_args {
+  int32_t n_index;                 /* M */
+  int32_t reserved0;               /* zero */
+  const int32_t* index;            /* device i32 [M] */
+  const float* state_value;        /* device f32 [M] */
+  const float* next_state_value;   /* device f32 [M] */
+  const float* slab;               /* device f32 [>= len, W] */
+  float* td_out;                   /* optional device f32 [M] */
+  float td_gamma;
+  int32_t reserved[5];             /* zero */
+} sigmaenv_prb_refresh_args_t;
+int sigmaenv_prb_create(sigmaenv_t* h, int64_t capacity, double alpha, double beta, double eps, sigmaenv_prb_t** out);
+void sigmaenv_prb_destroy(sigmaenv_prb_t* b);
+int sigmaenv_prb_extend(sigmaenv_t* h, sigmaenv_prb_t* b, const float* td, int64_t n);
+int sigmaenv_prb_sample(sigmaenv_t* h, sigmaenv_prb_t* b, int32_t n_index, uint64_t seed, uint64_t counter, int32_t* index_out, float* weight_out);
+int sigmaenv_prb_refresh(sigmaenv_t* h, sigmaenv_prb_t* b, const sigmaenv_prb_refresh_args_t* a);
+int sigmaenv_prb_get(sigmaenv_t* h, sigmaenv_prb_t* b, int32_t what, void* host_out);
+
 /* The priority module (sigmarl/modules/priority_module.py).  sigmaenv_priority_forward: priority_net (MultiAgentMLP depth 2: obs_dim -> 256 -> 256 -> 2, Tanh,
  * :34-51) on `obs` (device f32 [B * N, obs_dim], or NULL for SIGMAENV_BUF_OBS), NormalParamExtractor ("biased_softplus_1.0", as the actor's) and a 1-D
  * TanhNormal on [-1, 1] (:52-66): score = clamp(tanh(loc + scale z), -1 + 1e-6, 1 - 1e-6), z from draw 7100 of (seed, counter, env, agent) (0 when

@@ -133,6 +133,25 @@ class OptimArgs(C.Structure):
                 ("eps", C.c_double), ("max_grad_norm", C.c_double), ("t", C.c_int64), ("workspace", C.c_void_p), ("result", C.c_void_p), ("reserved", C.c_int32 * 4)]
 
 
+class PrbRefreshArgs(C.Structure):
+    """``sigmaenv_prb_refresh_args_t`` (sigmaenv_prb_refresh): a minibatch's frames, the critic's two values on them, the record and the optional TD-error output."""
+
+    _fields_ = [("n_index", C.c_int32), ("reserved0", C.c_int32), ("index", C.c_void_p), ("state_value", C.c_void_p), ("next_state_value", C.c_void_p),
+                ("slab", C.c_void_p), ("td_out", C.c_void_p), ("td_gamma", C.c_float), ("reserved", C.c_int32 * 5)]
+
+
+PRB_LEAVES, PRB_TOTAL, PRB_QMIN, PRB_LEN, PRB_N_LEVELS, PRB_LEVEL_SUM, PRB_LEVEL_MIN = 0, 1, 2, 3, 4, 16, 32  # SIGMAENV_PRB_*: what sigmaenv_prb_get copies
+PRB_FAN, PRB_MAX_CAPACITY, PRB_DRAW = 256, 1 << 30, 7400  # sigmaenv_prb.h
+
+
+def prb_level_sizes(capacity: int) -> list:
+    """``prb_level_sizes`` (sigmaenv_prb.h): the entries per level, the leaves first: ``n_0 = capacity``, ``n_{k+1} = ceil(n_k / 256)`` until a level has <= 256."""
+    n = [int(capacity)]
+    while n[-1] > PRB_FAN:
+        n.append((n[-1] + PRB_FAN - 1) // PRB_FAN)
+    return n
+
+
 PPO_SUMS = 5  # SIGMAENV_PPO_SUMS: partial sums per workgroup of 256 rows in sigmaenv_ppo_head's workspace
 PPO_RESULT = ("loss_objective", "loss_entropy", "loss_critic", "entropy", "clip_fraction", "kl_approx")  # result[0 .. 5]
 
@@ -262,6 +281,12 @@ _PRODUCT_ONLY = {
     "optim_workspace": (C.c_int, [C.c_void_p, C.POINTER(OptimArgs), C.POINTER(C.c_uint64)]),
     "optim_step": (C.c_int, [C.c_void_p, C.POINTER(OptimArgs)]),
     "mlp32_resolve_mode": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "prb_create": (C.c_int, [C.c_void_p, C.c_int64, C.c_double, C.c_double, C.c_double, C.POINTER(C.c_void_p)]),
+    "prb_destroy": (None, [C.c_void_p]),
+    "prb_extend": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]),
+    "prb_sample": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p]),
+    "prb_refresh": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(PrbRefreshArgs)]),
+    "prb_get": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
     "actor_forward_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64,
                                     C.c_int32]),
     "rollout_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64,

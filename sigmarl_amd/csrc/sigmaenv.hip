@@ -2665,4 +2665,6 @@ extern "C" int sigmaenv_trig_selftest(sigmaenv_t* h, int32_t kind, int32_t n, co
 #include "sigmaenv_wrappers.inc"
 #include "sigmaenv_learn.inc"
 #include "sigmaenv_ppo.inc"
+#include "sigmaenv_prb.h"
+#include "sigmaenv_prb.inc"
 #include "sigmaenv_cbf.inc"

@@ -1,0 +1,201 @@
+#!/usr/bin/env python
+"""What the prioritized replay buffer costs per minibatch, at F = 4096 x 128 frames and at the Parameters defaults (F = 4096), M = 512 slots, N = 4 agents:
+  device            PrioritizedBuffer.sample + sigmaenv_prb_refresh (given critic values): one sample launch, two refresh launches and the full rebuild of the levels
+  critic_passes     the two no-grad critic passes of PrioritizedBuffer.refresh over the sampled frames (observation and next observation), timed on their own
+  torch             the same on the same device in torch ops: cumsum + searchsorted, the weights, the TD expression, the minibatch normalisation, index_put_
+  torch_round_trip  the torch route with the round trip the reference's sampler makes: the sampled index and the new TD errors visit the host every minibatch
+``event_ms``: HIP events around one minibatch.  ``wall_ms_per_minibatch``: the host's wall clock over a run of UPDATES (default 32) consecutive minibatches without a
+synchronisation in between (the round-trip route waits by itself), divided by their number.  One untimed call of each route, then REPS (default 5) repetitions with
+the routes alternating inside one process.
+``update_loop``: the device-route minibatch update of tools/ppo_update_timing.py (apply -> head -> backward -> Adam.step; B = 512, T = 16, N = 16, 512-frame minibatches)
+as the loop runs it without a buffer -- the code of the commit before the buffer existed, unchanged by it -- next to the same step with buffer.sample in front and
+buffer.refresh behind, by the wall clock over UPDATES consecutive steps.
+``--powers``: instead of timing, the worst error in ulp of the device's two powf against float64 over the inputs of tests/test_gpu_prb.py (``pow_max_ulp_measured``:
+the source of that test's bar).  A report, not a bound; no test asserts a time.  Merges its figures into profiles/prb_ratios.json (or the path given) and prints them."""
+import json
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+import torch  # noqa: E402
+
+from sigmarl_amd import capi, learn  # noqa: E402
+from sigmarl_amd.actor import Actor, Critic, Mlp32, make_mlp  # noqa: E402
+from sigmarl_amd.env import SigmaEnv  # noqa: E402
+from sigmarl_amd.params import Parameters  # noqa: E402
+
+REPS, UPDATES, M = int(os.environ.get("REPS", 5)), int(os.environ.get("UPDATES", 32)), int(os.environ.get("MINIBATCH", 512))
+ALPHA, BETA, EPS, GAMMA = 0.7, 0.6, 1e-8, 0.9
+LOW, HIGH = [-1.0, -0.6], [1.0, 0.6]
+
+
+def merge(path, figures):
+    old = json.load(open(path)) if os.path.exists(path) else {}
+    old.update(figures)
+    with open(path, "w") as f:
+        json.dump(old, f, indent=1, sort_keys=True)
+        f.write("\n")
+    print(json.dumps(figures))
+
+
+def make_env(n_agents, n_envs):
+    return SigmaEnv(Parameters(n_agents=n_agents, scenario_type="cpm_entire", dt=0.05, is_use_mtv_distance=False, rew_method="distance", is_apply_mask=False,
+                               is_obs_noise=False, max_steps=128), n_envs=n_envs, device="cuda:0")
+
+
+def event_ms(fn):
+    torch.cuda.synchronize()
+    s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    s.record()
+    fn()
+    e.record()
+    torch.cuda.synchronize()
+    return s.elapsed_time(e)
+
+
+def wall_ms(fn, finish=lambda: None):
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(UPDATES):
+        fn()
+    finish()
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t0) * 1e3 / UPDATES
+
+
+def measure(routes, finish=None):
+    finish = finish or {}
+    for fn in routes.values():  # untimed: allocations, code loading
+        fn()
+    torch.cuda.synchronize()
+    ev, wl = {k: [] for k in routes}, {k: [] for k in routes}
+    for _ in range(REPS):
+        for k, fn in routes.items():
+            ev[k].append(event_ms(fn))
+        for k, fn in routes.items():
+            wl[k].append(wall_ms(fn, finish.get(k, lambda: None)))
+    return {"event_ms": ev, "wall_ms_per_minibatch": wl, "best": {"event_ms": {k: min(v) for k, v in ev.items()}, "wall_ms_per_minibatch": {k: min(v) for k, v in wl.items()}},
+            "spread": {"event_ms": {k: max(v) - min(v) for k, v in ev.items()}, "wall_ms_per_minibatch": {k: max(v) - min(v) for k, v in wl.items()}}}
+
+
+def buffer_routes(env, critic, F):
+    import ctypes as C
+
+    N, D = env.N, env.D
+    W = N * (D + 1) + 1
+    g = torch.Generator(device="cuda").manual_seed(F)
+    slab = torch.randn((F, W), device="cuda", generator=g)
+    slab[:, N * (D + 1)] = (torch.rand((F,), device="cuda", generator=g) < 0.1).float()
+    obs = torch.randn((F, N * D), device="cuda", generator=g)
+    td0 = torch.rand((F,), device="cuda", generator=g) * 10.0 + 1e-3
+    buf = learn.PrioritizedBuffer(env, F, ALPHA, BETA, EPS)
+    buf.extend(td0)
+    v, vn, td = (torch.randn((M,), device="cuda", generator=g) for _ in range(3))
+    state = {"k": 0}
+
+    def device():
+        idx, _ = buf.sample(M, 1, state["k"])
+        state["k"] += 1
+        a = capi.PrbRefreshArgs()
+        a.n_index, a.index, a.state_value, a.next_state_value, a.slab, a.td_out, a.td_gamma = M, idx.data_ptr(), v.data_ptr(), vn.data_ptr(), slab.data_ptr(), td.data_ptr(), GAMMA
+        buf._call("refresh", lambda: env.lib.prb_refresh(env.h, buf._h, C.byref(a)), (idx,))
+
+    index = buf.sample(M, 1, 0)[0]
+
+    def critic_passes():
+        with torch.no_grad():
+            Mlp32.apply(critic, env, rows=(obs, 0, 1, N * D, F, N * D), index=index, check_index=False)
+            Mlp32.apply(critic, env, rows=(slab, 0, 1, W, F, W), index=index, check_index=False)
+
+    q = (td0 + EPS) ** ALPHA
+    reward, done = slab[:, N * D:N * D + N], slab[:, N * (D + 1)]
+
+    def torch_route(round_trip=False):
+        c = q.cumsum(0)
+        idx = torch.searchsorted(c, torch.rand((M,), device="cuda") * c[-1], right=True).clamp_max(F - 1)
+        if round_trip:
+            idx = idx.cpu().cuda()
+        _ = (q[idx] / q.min()) ** -BETA
+        x = (reward[idx] + (GAMMA * vn * (1.0 - done[idx])).unsqueeze(1) - v.unsqueeze(1)).abs().mean(1)
+        lo, hi = x.min(), x.max()
+        t = (((x - lo) / (hi - lo).clamp_min(1e-3)) * 10.0).clamp(1e-3, 10.0)
+        if round_trip:
+            t = t.cpu().cuda()
+        q.index_put_((idx,), (t + EPS) ** ALPHA)
+
+    return {"device": device, "critic_passes": critic_passes, "torch": torch_route, "torch_round_trip": lambda: torch_route(True)}, buf
+
+
+def update_loop():
+    B, N, T = 512, 16, 16
+    env = make_env(N, B)
+    env.reset_random(seed=1)
+    D, frames = env.D, T * B
+    torch.manual_seed(0)
+    amod, cmod = make_mlp(D).cuda(), make_mlp(N * D, n_out=1).cuda()
+    actor, critic = Actor(amod, low=LOW, high=HIGH), Critic(cmod)
+    batch = learn.collect(env, actor, critic, T, gamma=0.99, lmbda=0.9, seed=1, counter0=0)
+    env.sync()
+    obs = batch["observation"]
+    perm = learn.minibatches(frames, M, torch.Generator(device="cuda").manual_seed(1))[0]
+    opt = learn.Adam(env, [(actor, amod), (critic, cmod)], lr=3e-4)
+    buf = learn.PrioritizedBuffer(env, frames)
+    buf.extend(batch["td_error"])
+    state = {"k": 0}
+
+    def step(index):
+        out = actor.apply(env, rows=(obs, 0, N, D, frames, N * D), index=index, check_index=False)
+        value = critic.apply(env, obs, index=index, check_index=False)
+        loss, _ = learn.ppo_head(env, out, value, batch, index, low=LOW, high=HIGH, clip_epsilon=0.2, entropy_coeff=1e-4, seed=1, counter=state["k"])
+        loss.backward()
+        opt.step(1.0)
+        state["k"] += 1
+
+    def plain():
+        step(perm)
+
+    def with_buffer():
+        index, _ = buf.sample(M, 1, state["k"])
+        step(index)
+        buf.refresh(critic, batch, index)
+
+    res = measure({"without_buffer": plain, "with_buffer": with_buffer}, {"without_buffer": opt.resolve, "with_buffer": opt.resolve})
+    res.update({"n_envs": B, "n_agents": N, "steps": T, "frames": frames, "minibatch_frames": M})
+    for n in (buf, actor, critic, env):
+        n.close()
+    return res
+
+
+def main():
+    args = [a for a in sys.argv[1:] if not a.startswith("--")]
+    path = args[0] if args else os.path.join(ROOT, "profiles", "prb_ratios.json")
+    if "--powers" in sys.argv:
+        import test_gpu_prb as t
+
+        envs = t.make_envs()
+        merge(path, {"pow_max_ulp_measured": t.measure_powers(envs),
+                     "pow_what": "worst |powf - float64| in float32 ulp over every leaf and weight of the cases of tests/test_gpu_prb.py; that test's bar is twice this, capped at 16"})
+        for e in envs.values():
+            e.close()
+        return
+    N = 4
+    env = make_env(N, 8)
+    torch.manual_seed(0)
+    cmod = make_mlp(N * env.D, n_out=1).cuda()
+    critic = Critic(cmod)
+    out = {"minibatch_slots": M, "n_agents": N, "reps": REPS, "minibatches_per_wall_run": UPDATES}
+    for name, F in (("frames_524288", 4096 * 128), ("frames_4096", 4096)):
+        routes, buf = buffer_routes(env, critic, F)
+        out[name] = measure(routes)
+        buf.close()
+    critic.close()
+    env.close()
+    out["update_loop"] = update_loop()
+    merge(path, {"timing": out})
+
+
+if __name__ == "__main__":
+    main()
