@@ -72,6 +72,8 @@ struct Smem {
   uint32_t* acc32;            // per boundary task: bits of the four minimal SQUARED corner distances, [S * 2][4]
   int* nearn;                 // per boundary task: number of segments within the circumradius, [S * 2]
   uint16_t* nearl;            // the tile's boundary segments within the circumradius, in any order: (boundary task << 8) | segment index, [S * NEAR_CAP]
+  float4* nearxy;             // end points (ax, ay, bx, by) of the first near_xy_cap(S, N) entries of that list, IN THE BYTES OF `dist` (16-byte aligned within it): the
+                              // matrix is dead from the end of a step until phase B1 of the next one rewrites all of it; the scan fills them, phase E reads them
   int* nearc;                 // their number, ONE word per tile; outside this carve-up (the step kernel points it at the free word of its tile's reset area)
   uint8_t* fresh;             // [S] 1 = the agent was (re)placed and has not been stepped since (boundary points of the observation: another index shift,
                               // world_state_rt.py:531-576 vs :686-724); the tile's copy of DevBufs::fresh, kept across the steps of one launch
@@ -83,6 +85,10 @@ struct Smem {
   // wider rows of the non-default observation switches without dropping below the 16 tiles per CU (one resident round at 4096 envs) the default row runs at.
   __host__ __device__ static __forceinline__ size_t scan_scratch_ints(int S) {
     return (size_t)S * 3 * 2 + (size_t)S * 2 * 4 + (size_t)S * 2 + (size_t)(ITEM_CAP(S) + 1) / 2 + (size_t)(S * NEAR_CAP + 1) / 2;
+  }
+  __host__ __device__ static __forceinline__ int near_xy_cap(int S, int N) {  // (up to 3 floats of `dist` go to the alignment)
+    const int room = (S * DIST_STRIDE(N) - 3) / 4, cap = S * NEAR_CAP;
+    return room < 0 ? 0 : (room < cap ? room : cap);
   }
   __host__ __device__ static __forceinline__ size_t stage_floats(int S, int D, bool lean) {
     const size_t o = ((size_t)S * D + 3) & ~(size_t)3, q = (scan_scratch_ints(S) + 3) & ~(size_t)3;
@@ -111,6 +117,7 @@ struct Smem {
     dright = f; f += S * 5;
     dbound = f; f += S;
     dist = f; f += S * DIST_STRIDE(N);
+    nearxy = reinterpret_cast<float4*>(dist + ((4 - (int)(((reinterpret_cast<uintptr_t>(dist) - reinterpret_cast<uintptr_t>(base)) >> 2) & 3)) & 3));
     thr = f; f += S * 3;   // step kernel: last step's position (x, y) of the slot, loaded early for the reward phase
     cs = f; f += S * 2;    // cos / sin of the yaw (shared by the vertices and the ego-view transforms)
     rew = f; f += S * 2;   // reward per slot, then done flag per env (rollout slab record)

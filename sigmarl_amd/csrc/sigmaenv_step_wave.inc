@@ -12,8 +12,9 @@
 //   S   the pruned scan as a balanced work list: lane per (agent, polyline) for the candidate chunks, then lane per (task, chunk) item,
 //                             per-task results merged by LDS atomics (see scan_tile_balanced).  Segments within the circumradius are
 //                             appended to ONE list per tile in LDS for the edge tests.
-//   E   lane per (listed segment, rectangle edge): the tile's list in passes of 64 tests, crossing tests (interX) ORed into the agent's flag;
-//                             a tile whose list overflowed: lane per (agent, side, edge) over every segment of the boundaries with a near one
+//   E   lane per listed segment: code and end points from LDS (the scan stored them beside the entry), the four rectangle edges' crossing tests (interX) ORed
+//                             into the agent's flag, in passes of 64 entries; a tile whose list overflowed: lane per (agent, side, edge) over every segment of the
+//                             boundaries with a near one
 //   B1  lane per unordered agent pair: mutual distance, rectangle-rectangle tests of close pairs
 //   C   lane per agent      : reward, short-term path, done / counters by ballots
 //   D   lane per item       : observation rows (observe_tile<WAVE>)
@@ -209,6 +210,7 @@ struct ScanItemOut {
   int bk;
   float bs0, bs1, bs2, bs3;
   unsigned near_bits;  // bit u: segment u of the lane's run lies within the circumradius (boundaries only)
+  Seg4 sg[SIGMAENV_CHUNK];  // the lane's run of segments as loaded (the first SEGS of them): the listed ones' end points go to LDS for phase E
 };
 
 // one chunk of one task: its SIGMAENV_CHUNK segments against the centre point (and, for a boundary, the four corner query points).
@@ -220,11 +222,11 @@ __device__ __forceinline__ void scan_chunk(const DevMap& m, const Smem& s, int s
                                            const float near_thr, ScanItemOut& o) {
   const float cgx = s.st[sl * 8], cgy = s.st[sl * 8 + 1];
   const unsigned kmax = (unsigned)(npt - 2 < 0 ? 0 : npt - 2);
-  Seg4 sg[SEGS];
+  Seg4 (&sg)[SIGMAENV_CHUNK] = o.sg;
 #pragma unroll
-  for (int u = 0; u < SEGS; ++u) {
+  for (int u = 0; u < SIGMAENV_CHUNK; ++u) {
     const unsigned k = min((unsigned)(ch * SIGMAENV_CHUNK + u0 + u), kmax);
-    sg[u] = *reinterpret_cast<const Seg4*>(m.center + (poly_off + 2u * k));
+    sg[u] = u < SEGS ? *reinterpret_cast<const Seg4*>(m.center + (poly_off + 2u * k)) : Seg4{0.f, 0.f, 0.f, 0.f};
   }
   // corner query points: agent 0 of every env still sees last step's vertices (world_state_rt_sim.py:439-448)
   const float* qv = first_of_env ? (s.vold + sl * 10) : (s.vnew + sl * 10);
@@ -293,13 +295,14 @@ template <bool FASTDIV>
 __device__ __forceinline__ void scan_tile_balanced(const DevMap& m, const CfgDerived& dv, const DevBufs& g, const Smem& s, const Tile& t, int G, int lane) {
   // tasks are numbered pl * SG + sl with SG = the slots of a FULL tile (kernel-uniform: division by multiplication); slots beyond a ragged
   // last tile stay idle
-  const int N = t.N, slots = t.slots, SG = G * N, n_tasks = SG * 3, cap = ITEM_CAP(SG), near_cap = SG * NEAR_CAP;
+  const int N = t.N, slots = t.slots, SG = G * N, n_tasks = SG * 3, cap = ITEM_CAP(SG), near_cap = SG * NEAR_CAP, xy_cap = Smem::near_xy_cap(SG, N);
   const float near_thr = m.rect_radius + 1e-4f;
   // The tile's list of near segments: the wavefront owns the tile, so the position of a lane's entries is the number listed so far (wavefront-uniform, in a register)
   // plus a prefix sum over the lanes of the pass -- no LDS counter.  (One counter per tile bumped by an atomic add per chunk serialises: up to 64 lanes on ONE address,
   // S2 +2,700 cycles per tile-step against the per-boundary counters it replaced, more than phase E gains; profiles/edge_list_phase_cycles.txt.)
+  // An entry is its code and, for the first xy_cap entries, the segment's end points as the lane holds them (one 16-byte store): phase E then needs no map load.
   int near_total = 0;
-  auto near_append = [&](unsigned nb, int code0) {  // all lanes; nb = 0: nothing to list
+  auto near_append = [&](unsigned nb, int code0, const Seg4 (&sg)[SIGMAENV_CHUNK]) {  // all lanes; nb = 0: nothing to list
     const int cnt = (int)__popc(nb);
     const int incl = wave_inclusive_sum(cnt, lane);
     int slot = near_total + incl - cnt;
@@ -308,6 +311,7 @@ __device__ __forceinline__ void scan_tile_balanced(const DevMap& m, const CfgDer
     for (int u = 0; u < SIGMAENV_CHUNK; ++u) {
       if ((nb >> u) & 1u) {
         if (slot < near_cap) s.nearl[slot] = (uint16_t)(code0 + u);
+        if (slot < xy_cap) s.nearxy[slot] = make_float4(sg[u].ax, sg[u].ay, sg[u].bx, sg[u].by);
         ++slot;
       }
     }
@@ -417,7 +421,7 @@ __device__ __forceinline__ void scan_tile_balanced(const DevMap& m, const CfgDer
 #endif
       // ---- S2: one lane per listed (task, chunk); a last round that fills at most half / a quarter of the wavefront gives every item two /
       // four lanes (two segments / one segment each) instead of leaving the lanes idle
-      auto item_part = [&](int it, auto segs_tag, int u0, unsigned& nb, int& code0) {
+      auto item_part = [&](int it, auto segs_tag, int u0, unsigned& nb, int& code0, Seg4 (&sgo)[SIGMAENV_CHUNK]) {
         constexpr int SEGS = decltype(segs_tag)::value;
         const unsigned code = s.items[it];
         const int tpm2 = (int)(code >> 6), ch = (int)(code & 63u);
@@ -428,26 +432,30 @@ __device__ __forceinline__ void scan_tile_balanced(const DevMap& m, const CfgDer
         scan_chunk<FASTDIV, SEGS>(m, s, sl2, pl2, poly_off, s.npts[sl2 * 3 + pl2], ch, u0, first, near_thr, o);
         scan_merge(s, sl2, pl2, o);
         nb = o.near_bits;
+#pragma unroll
+        for (int u = 0; u < SIGMAENV_CHUNK; ++u) sgo[u] = o.sg[u];
         code0 = ((sl2 * 2 + (pl2 - 1)) << 8) | (ch * SIGMAENV_CHUNK + u0);  // (boundary task << 8) | first segment of the lane's run
       };
       int it0 = 0;
       for (; it0 + 64 <= total; it0 += 64) {
         unsigned nb = 0u;
         int code0 = 0;
-        item_part(it0 + lane, std::integral_constant<int, SIGMAENV_CHUNK>{}, 0, nb, code0);
-        near_append(nb, code0);
+        Seg4 sgo[SIGMAENV_CHUNK];
+        item_part(it0 + lane, std::integral_constant<int, SIGMAENV_CHUNK>{}, 0, nb, code0, sgo);
+        near_append(nb, code0, sgo);
       }
       const int rem = total - it0;
       unsigned nb = 0u;
       int code0 = 0;
+      Seg4 sgo[SIGMAENV_CHUNK] = {};
       if (rem > 32) {
-        if (lane < rem) item_part(it0 + lane, std::integral_constant<int, SIGMAENV_CHUNK>{}, 0, nb, code0);
+        if (lane < rem) item_part(it0 + lane, std::integral_constant<int, SIGMAENV_CHUNK>{}, 0, nb, code0, sgo);
       } else if (rem > 16) {
-        if ((lane >> 1) < rem) item_part(it0 + (lane >> 1), std::integral_constant<int, SIGMAENV_CHUNK / 2>{}, (lane & 1) * (SIGMAENV_CHUNK / 2), nb, code0);
+        if ((lane >> 1) < rem) item_part(it0 + (lane >> 1), std::integral_constant<int, SIGMAENV_CHUNK / 2>{}, (lane & 1) * (SIGMAENV_CHUNK / 2), nb, code0, sgo);
       } else if (rem > 0) {
-        if ((lane >> 2) < rem) item_part(it0 + (lane >> 2), std::integral_constant<int, SIGMAENV_CHUNK / 4>{}, (lane & 3) * (SIGMAENV_CHUNK / 4), nb, code0);
+        if ((lane >> 2) < rem) item_part(it0 + (lane >> 2), std::integral_constant<int, SIGMAENV_CHUNK / 4>{}, (lane & 3) * (SIGMAENV_CHUNK / 4), nb, code0, sgo);
       }
-      if (rem > 0) near_append(nb, code0);
+      if (rem > 0) near_append(nb, code0, sgo);
       wave_sync();
     } while (__any(pending));
   }
@@ -781,37 +789,61 @@ __global__ void __launch_bounds__(256, STEP_WAVE_MIN_WAVES) sigmaenv_step_wave_k
   TSW(2);
   // ---- E: rectangle edge x listed boundary segment (interX, helper_scenario.py:1165-1196; world_state_rt_sim.py:398-411) --------
   {
-  STEP_TABLES(m, g);
-  (void)g;
-  if (m.nch > 0 && !SKIP(4) && !SKIP(2)) {  // (a skipped scan leaves no list)
-    const int total = __builtin_amdgcn_readfirstlane(*s.nearc), near_cap = G * N * NEAR_CAP;
+  // (the common path reads LDS only: the map's tables are fetched inside the two branches that load from the map)
+  STEP_KA(ka_e);
+  if (ka_e->m.nch > 0 && !SKIP(4) && !SKIP(2)) {  // (a skipped scan leaves no list)
+    const int total = __builtin_amdgcn_readfirstlane(*s.nearc), near_cap = G * N * NEAR_CAP, xy_cap = Smem::near_xy_cap(G * N, N);
 #ifdef SIGMAENV_PROFILE
-    if (g.dbg_ts && lane == 0) {  // list statistics of the tile, in the upper halves of the work-list words: entries, tile-steps whose list overflowed
-      g.dbg_ts[(size_t)tile_index * 16 + 8] += (unsigned long long)total << 32;
-      g.dbg_ts[(size_t)tile_index * 16 + 9] += (unsigned long long)(total > near_cap ? 1 : 0) << 32;
+    if (unsigned long long* ts_ = as_global(ka_e->g.dbg_ts); ts_ && lane == 0) {
+      // list statistics of the tile, in the upper halves of the work-list words: entries, tile-steps whose list overflowed; in the upper halves of the
+      // neighbour-level words 12 / 13: tile-steps that needed a second pass, tile-steps with an entry beyond the coordinate capacity (taken from the map)
+      ts_[(size_t)tile_index * 16 + 8] += (unsigned long long)total << 32;
+      ts_[(size_t)tile_index * 16 + 9] += (unsigned long long)(total > near_cap ? 1 : 0) << 32;
+#ifndef SIGMAENV_PROFILE_RT
+      ts_[(size_t)tile_index * 16 + 12] += (unsigned long long)((total <= near_cap && total > 64) ? 1 : 0) << 32;
+      ts_[(size_t)tile_index * 16 + 13] += (unsigned long long)((total <= near_cap && total > xy_cap) ? 1 : 0) << 32;
+#endif
     }
 #endif
     if (total <= near_cap) {
-      // one lane per (listed segment, rectangle edge), one test per lane and pass.  The flag of an agent is the OR over its entries and edges, so neither the
-      // order of the list nor the pass an entry falls into enters the result.  Every lane requests a segment (the last pass's idle lanes the last test's: no
-      // divergence before the load); only the test is predicated.  (Two passes per round with both segments requested up front are slower -- longer code, the
-      // second request's address arithmetic paid by every round: profiles/edge_list_ab.txt.)
-      const int n_tests = total * 4, e4 = lane & 3;
-      for (int base = 0; base < n_tests; base += 64) {
-        const int w = base + lane;
-        const unsigned code = s.nearl[min(w, n_tests - 1) >> 2];
+      // one lane per listed segment: its code and its end points from LDS (the scan's lane stored them as it held them), the four edges of its agent's rectangle
+      // tested in turn.  The flag of an agent is the OR over its entries and edges, so neither the order of the list nor the pass an entry falls into enters the
+      // result, and the tests are those of the lane-per-(entry, edge) form operand for operand.  An entry beyond the coordinate capacity takes its segment from
+      // the map by its code, as every entry did before; a pass without such an entry (wavefront-uniform) touches no table.
+      for (int base = 0; base < total; base += 64) {
+        const int w = base + lane, wc = min(w, total - 1);
+        const unsigned code = s.nearl[wc];
         const int bt = (int)(code >> 8), sl = bt >> 1, side = bt & 1;
-        const unsigned poly_off = (unsigned)(side + 1) * (unsigned)m.poly_stride + (unsigned)s.path[sl] * (unsigned)(m.P * 2);
-        const Seg4 sg = *reinterpret_cast<const Seg4*>(m.center + (poly_off + 2u * (code & 255u)));
-        if (w < n_tests) {
-          const float* pv = s.vnew + sl * 10 + 2 * e4;
-          const Edge ed = make_edge(pv[0], pv[1], pv[2], pv[3]);
-          const float lx = sg.bx - sg.ax, ly = sg.by - sg.ay;
-          const float S2 = lx * sg.ay - ly * sg.ax;
-          if (edge_hits_segment(ed, sg.ax, sg.ay, sg.bx, sg.by, lx, ly, S2)) s.flags[sl * 4 + 0] = 1;
+        float4 sg;
+        if (min(base + 63, total - 1) < xy_cap) {
+          sg = s.nearxy[wc];
+        } else {
+          STEP_KA(ka_f);
+          const float* center = as_global(ka_f->m.center);
+          const unsigned poly_off = (unsigned)(side + 1) * (unsigned)ka_f->m.poly_stride + (unsigned)s.path[sl] * (unsigned)(ka_f->m.P * 2);
+          if (wc < xy_cap) {
+            sg = s.nearxy[wc];
+          } else {
+            const Seg4 q = *reinterpret_cast<const Seg4*>(center + (poly_off + 2u * (code & 255u)));
+            sg = make_float4(q.ax, q.ay, q.bx, q.by);
+          }
+        }
+        if (w < total) {
+          const float lx = sg.z - sg.x, ly = sg.w - sg.y;
+          const float S2 = lx * sg.y - ly * sg.x;
+          const float* pv = s.vnew + sl * 10;
+          bool hit = false;
+#pragma unroll
+          for (int e4 = 0; e4 < 4; ++e4) {
+            const Edge ed = make_edge(pv[2 * e4], pv[2 * e4 + 1], pv[2 * e4 + 2], pv[2 * e4 + 3]);
+            hit |= edge_hits_segment(ed, sg.x, sg.y, sg.z, sg.w, lx, ly, S2);
+          }
+          if (hit) s.flags[sl * 4 + 0] = 1;
         }
       }
     } else {
+      STEP_TABLES(m, g);
+      (void)g;
       // the list overflowed (more than NEAR_CAP close segments per slot of the tile: the `dense` map of tests/synthetic_maps.py): lane per (agent, side, edge),
       // every real segment of each boundary that counted a near one -- a superset of the listed ones, which cannot change the OR
       for (int base = 0; base < t.slots * 2; base += 16) {

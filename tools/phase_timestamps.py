@@ -44,7 +44,8 @@ ts = stamp_rows()
 n = len(ts)
 sub = ts[:n, [1, 10, 11, 2]].astype(np.int64)  # scan: start, end of S1 (candidate masks), end of S2 (work-list rounds), end (S3)
 stats = (ts[:n, 8:10] & np.uint64(0xFFFFFFFF)).astype(np.int64)  # (the upper halves: phase E's list statistics, read above)
-lvl = ts[:n, 12:16].astype(np.int64)
+lvl = (ts[:n, 12:16] & np.uint64(0xFFFFFFFF)).astype(np.int64)
+passes = (ts[:n, 12:14] >> np.uint64(32)).astype(np.int64)  # (the upper halves of words 12 / 13: phase E's tile-steps with a second pass / with an entry taken from the map; all launches)
 ts = ts[:n, :8].astype(np.int64)
 ts = ts[ts[:, 0] > 0]
 d = np.diff(ts, axis=1)
@@ -61,6 +62,8 @@ if edge_steps and sum(int(e[:, 0].sum()) for e in edge_steps):
     print("edge list (%s): entries per tile-step mean %.1f p50 %.0f p99 %.0f max %.0f; overflowed tile-steps %d of %d" % (
         "per tile-step" if T == 1 else "per tile, mean of the %d-step launch" % T, ent.mean(), np.percentile(ent, 50), np.percentile(ent, 99), ent.max(),
         sum(int(e[:, 1].sum()) for e in edge_steps), len(ent) * T))
+    print("edge passes (all %d steps): tile-steps with a second pass of 64 lanes %d of %d (%.3f %%), with an entry beyond the coordinate capacity (segment from the map) %d of %d (%.3f %%)" % (
+        n_steps, passes[:, 0].sum(), n_steps * n, 100.0 * passes[:, 0].sum() / (n_steps * n), passes[:, 1].sum(), n_steps * n, 100.0 * passes[:, 1].sum() / (n_steps * n)))
 
 sub = sub[(sub[:, 0] > 0) & (sub[:, 1] > 0)]
 if len(sub):
