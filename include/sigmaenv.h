@@ -118,8 +118,8 @@ typedef struct sigmaenv_config {
   float obs_noise_level;        /* Parameters.obs_noise_level when Parameters.is_obs_noise, else 0 (no noise).  observation_provider_rt.py:613-618:
                                  * `obs + obs_noise_level * rand_like(obs)`, i.e. uniform noise in [0, level) on every element of every observation
                                  * row, drawn at every observation() call.  Here element k of agent i of env b receives level * u with
-                                 * u = (rng(obs_noise_seed, episodes_reset(b) * 65537 + timer.step(b), env_index_base + b, i, 9000 + k) >> 8) / 2^24
-                                 * (the counter-based generator the reset sampler uses): a pure function of the env's own counters, hence the same in the
+                                 * u = (rng(obs_noise_seed, episodes_reset(b) * 65537 + timer.step(b), env_index_base + b, i, DRAW_OBS_NOISE + k) >> 8) / 2^24
+                                 * (the counter-based generator the reset sampler uses; its draw table: sigmarl_amd/csrc/sigmaenv_dist.h): a pure function of the env's own counters, hence the same in the
                                  * fused / separate / n-step launches and for any sharding.  Applied on the DEVICE to SIGMAENV_BUF_OBS, to the rollout
                                  * record and therefore to what sigmaenv_actor_* / sigmaenv_rollout read. */
   uint32_t obs_noise_seed_lo, obs_noise_seed_hi; /* Parameters.random_seed */
@@ -365,7 +365,8 @@ void sigmaenv_actor_destroy(sigmaenv_actor_t* a);
 
 /* actions := policy(observation) for every agent row.  obs: device f32 [B*N, obs_dim] or NULL for the handle's SIGMAENV_BUF_OBS;
  * actions: device f32 [B,N,2]; log_prob (optional) device f32 [B,N]; loc_scale (optional) device f32 [B,N,4] = loc0, loc1, scale0,
- * scale1.  deterministic != 0: action = squash(loc).  seed / counter select the counter-based random stream (draws 7000, 7001).
+ * scale1.  deterministic != 0: action = squash(loc).  seed / counter select the counter-based random stream (draws DRAW_ACTOR, + 1 of the draw table,
+ * sigmarl_amd/csrc/sigmaenv_dist.h, which states every stream of the generator and the head's arithmetic once).
  * Everywhere in this header the generator takes `seed` with both 32-bit words and `counter` with its LOW 32 bits only: counter and counter + 2^32
  * give the same draws (2^32 + 5 draws what 5 draws), so a stream repeats after 2^32 steps of one seed (tests/policy_head_check.py restates it). */
 int sigmaenv_actor_forward(sigmaenv_t* h, sigmaenv_actor_t* a, const float* obs, float* actions, float* log_prob, float* loc_scale, uint64_t seed,
@@ -585,7 +586,7 @@ int sigmaenv_gae(sigmaenv_t* h, const sigmaenv_gae_args_t* a);
  *   objective      lw = logp - sample_log_prob[f, n];  A = advantage[f, n];  g1 = exp(lw) A;  g2 = exp(clamp(lw, log1p(-eps), log1p(eps))) A;
  *                  loss_objective = -mean_{m, n} min(g1, g2);  on a tie the unclamped branch carries the gradient
  *   entropy bonus  TanhNormal has no closed-form entropy: one reparameterised sample.  (z_0, z_1) by Box-Muller (z_0 the cosine branch) from the generator keyed
- *                  (seed, counter, env = f, agent = n), draws 7300 and 7301 (beside 7000 / 7001, 7100 / 7101, 7200);  x'_d = loc_d + sigma_d z_d;
+ *                  (seed, counter, env = f, agent = n), draws DRAW_ENTROPY, + 1 (the draw table of sigmaenv_dist.h);  x'_d = loc_d + sigma_d z_d;
  *                  logp' = sum_d [ -z_d^2 / 2 - log sigma_d - log sqrt(2 pi) - 2 (log 2 - x'_d - softplus(-2 x'_d)) - log h_d ]   (never clamped);
  *                  entropy = -mean logp';  loss_entropy = -entropy_coeff entropy;  the gradient flows through x' into loc and sigma
  *   critic         v = value[m] (the centralised critic's one value per frame is every agent's);  e = v - value_target[f, n];
@@ -698,7 +699,7 @@ int sigmaenv_mlp32_resolve_mode(sigmaenv_t* h, sigmaenv_mlp32_t* m);
  *             the sum / min of the one node over the top level.  A node's sum: lane l of 64 the chain ((e_{4l} + e_{4l+1}) + e_{4l+2}) + e_{4l+3}, then the
  *             inclusive scan over the lanes I_l = I_l + I_{l-d} (l >= d), d = 1, 2, .., 32; the sum is I_63.  The order of every operation: sigmaenv_prb.h.
  *   sample    with replacement, proportional to q.  Slot m: u_m = ((k >> 8) + 0.5) 2^-24 of the generator's word k keyed (seed, counter, env = m, agent = 0), draw
- *             7400 (beside 7000 / 7100 / 7200 / 7300);  mass_m = u_m total;  index_out[m] = the lower-bound scan of the prefix sums -- the first f with
+ *             DRAW_REPLAY (the draw table of sigmaenv_dist.h);  mass_m = u_m total;  index_out[m] = the lower-bound scan of the prefix sums -- the first f with
  *             mass < q[0] + .. + q[f], clamped to len - 1 -- found by descending the levels: at a node the smallest child j with r < S_j (the children's
  *             inclusive prefixes), then r - S_{j-1} below; if no child qualifies (rounding, u = 1, a NaN) the last child below len.  The index is always in
  *             [0, len).  weight_out[m] = powf(q[index] / q_min, -beta) (<= 1; exactly 1 at a minimal leaf).  total and q_min are read on the device.
@@ -744,13 +745,13 @@ int sigmaenv_prb_get(sigmaenv_t* h, sigmaenv_prb_t* b, int32_t what, void* host_
 
 /* The priority module (sigmarl/modules/priority_module.py).  sigmaenv_priority_forward: priority_net (MultiAgentMLP depth 2: obs_dim -> 256 -> 256 -> 2, Tanh,
  * :34-51) on `obs` (device f32 [B * N, obs_dim], or NULL for SIGMAENV_BUF_OBS), NormalParamExtractor ("biased_softplus_1.0", as the actor's) and a 1-D
- * TanhNormal on [-1, 1] (:52-66): score = clamp(tanh(loc + scale z), -1 + 1e-6, 1 - 1e-6), z from draw 7100 of (seed, counter, env, agent) (0 when
+ * TanhNormal on [-1, 1] (:52-66): score = clamp(tanh(loc + scale z), -1 + 1e-6, 1 - 1e-6), z from draws DRAW_PRIORITY, + 1 of (seed, counter, env, agent) (0 when
  * deterministic), log_prob = Normal(loc, scale).log_prob(x) - log(1 - tanh(x)^2).  scores / log_prob (optional) device f32 [B, N]; ranks (optional) device
  * i32 [B, N] = sigmaenv_priority_rank of the scores.  scratch: device f32 [B * N * 2].
  * sigmaenv_priority_rank (rank_agents, :118-135): ranks[b, :] = the agents of env b by descending score.  torch.argsort is not stable: here ties go to the
  * LOWER agent index first (a stable descending sort); a NaN score ranks below every number.
  * sigmaenv_priority_random (:147-153, prioritization_method "random"): ranks[b, :] = a uniform permutation of 0 .. N - 1 per env (inside-out Fisher-Yates on
- * draws 7200 + i of (seed, counter, env, i)). */
+ * draw DRAW_SHUFFLE of (seed, counter, env, agent = i): position i draws j in [0, i]). */
 int sigmaenv_priority_forward(sigmaenv_t* h, sigmaenv_mlp32_t* priority_net, const float* obs, float* scratch, float* scores, float* log_prob, int32_t* ranks,
                               uint64_t seed, uint64_t counter, int32_t deterministic);
 int sigmaenv_priority_rank(sigmaenv_t* h, const float* scores, int32_t* ranks);

@@ -141,7 +141,7 @@ class PrbRefreshArgs(C.Structure):
 
 
 PRB_LEAVES, PRB_TOTAL, PRB_QMIN, PRB_LEN, PRB_N_LEVELS, PRB_LEVEL_SUM, PRB_LEVEL_MIN = 0, 1, 2, 3, 4, 16, 32  # SIGMAENV_PRB_*: what sigmaenv_prb_get copies
-PRB_FAN, PRB_MAX_CAPACITY, PRB_DRAW = 256, 1 << 30, 7400  # sigmaenv_prb.h
+PRB_FAN, PRB_MAX_CAPACITY, PRB_DRAW = 256, 1 << 30, 7400  # sigmaenv_prb.h; PRB_DRAW = DRAW_REPLAY of the draw table (sigmaenv_dist.h)
 
 
 def prb_level_sizes(capacity: int) -> list:

@@ -45,8 +45,6 @@ using namespace sigmadev;
 static_assert(NS >= 1 && NS <= SIGMAENV_MAX_SHORT_TERM, "SIGMAENV_N_SHORT_TERM out of range");
 __device__ __constant__ uint32_t W_REF_BITS[NS] = SIGMAENV_W_REF_BITS;
 
-#define AUTO_RESET_MAX_TRIES 64
-
 // ---------------------------------------------------------------------------------------------------------------------
 // LDS carve-up for one workgroup: S = G*N agent slots (slot = env_local * N + agent)
 // ---------------------------------------------------------------------------------------------------------------------
@@ -1172,18 +1170,18 @@ __device__ __forceinline__ int reset_end_point(int testing, int tr, int n) {
   return end < 4 ? 4 : end;
 }
 __device__ __forceinline__ void reset_candidate(const DevMap& m, const ResetDraw& rd, int b, int i, int tr, int& path, int& pt, float& px, float& py,
-                                                uint32_t draw0 = 0u) {
-  path = rd.path_first + (int)__umulhi(rng_u32(rd.seed, rd.counter, (uint32_t)(rd.env_base + b), (uint32_t)i, draw0 + 2u * tr), (uint32_t)rd.path_count);
+                                                uint32_t draw0 = DRAW_RESET_TRY) {
+  path = rd.path_first + (int)rng_below(rng_u32(rd.seed, rd.counter, (uint32_t)(rd.env_base + b), (uint32_t)i, draw0 + 2u * tr), (uint32_t)rd.path_count);
   int n = m.n_center[path];
   const int end = reset_end_point(rd.testing, tr, n);
-  pt = 3 + (int)__umulhi(rng_u32(rd.seed, rd.counter, (uint32_t)(rd.env_base + b), (uint32_t)i, draw0 + 2u * tr + 1u), (uint32_t)(end - 3));
+  pt = 3 + (int)rng_below(rng_u32(rd.seed, rd.counter, (uint32_t)(rd.env_base + b), (uint32_t)i, draw0 + 2u * tr + 1u), (uint32_t)(end - 3));
   const float2 xy = reinterpret_cast<const float2*>(m.center)[(size_t)path * m.P + pt];
   px = xy.x;
   py = xy.y;
 }
 // cpm_mixed: the path list of sub-scenario `sid` (1-based; any other id -- 0 after a host-placed start -- takes the LAST list, the reference's
 // `if 1 / elif 2 / else` chain, world_state_rt_sim.py:345-356), and the sub-scenario a finished env draws
-// (torch.multinomial(cpm_scenario_probabilities), world_state_rt_sim.py:330-343 -- here the counter-based generator's draw 5000 of agent 0 against the
+// (torch.multinomial(cpm_scenario_probabilities), world_state_rt_sim.py:330-343 -- here the counter-based generator's DRAW_SCENARIO of agent 0 against the
 // cumulative distribution; specification shared with the oracle)
 __device__ __forceinline__ void scenario_list(const DevMap& m, int sid, int& first, int& count) {
   const int k = (sid >= 1 && sid <= m.n_lists) ? sid - 1 : (m.n_lists > 0 ? m.n_lists - 1 : 0);
@@ -1191,7 +1189,7 @@ __device__ __forceinline__ void scenario_list(const DevMap& m, int sid, int& fir
   count = (int)((m.list_count16 >> (16 * k)) & 0xFFFFull);
 }
 __device__ __forceinline__ int draw_scenario(const DevMap& m, uint64_t seed, uint64_t counter, int env_global) {
-  const float u = (float)(rng_u32(seed, counter, (uint32_t)env_global, 0u, 5000u) >> 8) * (1.0f / 16777216.0f);
+  const float u = rng_uniform(rng_u32(seed, counter, (uint32_t)env_global, 0u, DRAW_SCENARIO));
   int sid = m.n_lists;
   if (m.n_lists > 3 && u < m.cdf2) sid = 3;
   if (m.n_lists > 2 && u < m.cdf1) sid = 2;
@@ -1625,7 +1623,7 @@ __device__ __forceinline__ void auto_reset_tile(const sigmaenv_config_t& c, cons
     if (!s_full[e]) {
       // per-agent resets of an unfinished env (agents that left through an entry/exit, or collided in testing mode): agents in
       // index order, each against ALL other agents' current positions (is_reset_single_agent, world_state_rt_sim.py:287-309);
-      // the 64 lanes evaluate tries 0..63 (draws 2000 + 2t, 2001 + 2t), first feasible wins, else the last one
+      // the 64 lanes evaluate tries 0..63 (DRAW_AGENT_TRY), first feasible wins, else the last one
       unsigned long long rq = s_mask[e];
       while (rq) {
         const int i = __ffsll((long long)rq) - 1;
@@ -1634,7 +1632,7 @@ __device__ __forceinline__ void auto_reset_tile(const sigmaenv_config_t& c, cons
         int p2, q2;
         float x2, y2;
         if (mixed) scenario_list(m, g.path[(t.a0 + sl) * 4 + 1], rd.path_first, rd.path_count);  // the agent keeps its env's sub-scenario (:325-328)
-        reset_candidate(m, rd, b, i, lane, p2, q2, x2, y2, 2000u);
+        reset_candidate(m, rd, b, i, lane, p2, q2, x2, y2, DRAW_AGENT_TRY);
         bool ok = true;
         for (int j = 0; j < N; ++j) {
           if (j == i) continue;
@@ -1645,7 +1643,7 @@ __device__ __forceinline__ void auto_reset_tile(const sigmaenv_config_t& c, cons
         unsigned long long f2 = __ballot(ok);
         const int wl = f2 ? (__ffsll((long long)f2) - 1) : (AUTO_RESET_MAX_TRIES - 1);
         if (lane == wl) {
-          float u = (float)(rng_u32(seed, counter, (uint32_t)(c.env_index_base + b), (uint32_t)i, 3000u) >> 8) * (1.0f / 16777216.0f);
+          float u = rng_uniform(rng_u32(seed, counter, (uint32_t)(c.env_index_base + b), (uint32_t)i, DRAW_AGENT_SPEED));
           place_from_start_table(m, g, s, t, sl, p2, q2, u * c.max_speed, rd.path_first, false, 0, fin);
         }
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -1700,7 +1698,7 @@ __device__ __forceinline__ void auto_reset_tile(const sigmaenv_config_t& c, cons
     }
     if (lane < N) {  // finalise the accepted starts, one lane per agent (world_state_rt_sim.py:189-213)
       const int i = lane, sl = e * N + i;
-      float u = (float)(rng_u32(seed, counter, (uint32_t)(c.env_index_base + b), (uint32_t)i, 1000u) >> 8) * (1.0f / 16777216.0f);
+      float u = rng_uniform(rng_u32(seed, counter, (uint32_t)(c.env_index_base + b), (uint32_t)i, DRAW_RESET_SPEED));
       place_from_start_table(m, g, s, t, sl, my_path, my_pt, u * c.max_speed, rd.path_first, true, sid, fin);
     }
   }

@@ -99,41 +99,21 @@ __device__ __forceinline__ void actor_output_layer(const __bf16* __restrict__ w_
   }
 }
 
-// NormalParamExtractor + TanhNormal of the actor (decision_making_module.py:50-82), one agent row.  torchrl / tensordict are third-party and
-// absent; restated from their published behaviour:
-//   scale = clamp_min(softplus(raw + inv_softplus(1.0 - 0.01)) + 0.01, 1e-4)      ("biased_softplus_1.0": bias 1.0, min_val 0.01, scale_lb 1e-4)
-//   x = loc + scale * z;  y = clamp(tanh(x), -1 + 1e-6, 1 - 1e-6) (SafeTanhTransform, eps = finfo(float32).resolution);
-//   action = low + (y + 1) / 2 * (high - low)
-//   log_prob = sum_d [ Normal(loc, scale).log_prob(x) - 2 (log 2 - x - softplus(-2 x)) - log((high - low) / 2) ]
+// NormalParamExtractor + TanhNormal of the actor (decision_making_module.py:50-82), one agent row: the head of sigmaenv_dist.h in two dimensions
 __device__ __forceinline__ void actor_distribution(const float (&low)[2], const float (&high)[2], int row, int n_agents, int env_base, float loc0, float loc1, float raw0, float raw1,
                                                    float* __restrict__ actions, float* __restrict__ log_prob, float* __restrict__ loc_scale, uint64_t seed,
                                                    uint64_t counter, int deterministic) {
-  const float BIAS = 0.5254587192925021f;  // ln(e^0.99 - 1)
-  auto softplus = [](float v) { return v > 20.0f ? v : log1pf(expf(v)); };
-  const float sc0 = fmaxf(softplus(raw0 + BIAS) + 0.01f, 1e-4f), sc1 = fmaxf(softplus(raw1 + BIAS) + 0.01f, 1e-4f);
+  const float sc0 = tn_scale(raw0), sc1 = tn_scale(raw1);
   if (loc_scale) *reinterpret_cast<float4*>(loc_scale + (size_t)row * 4) = make_float4(loc0, loc1, sc0, sc1);
   float z0 = 0.0f, z1 = 0.0f;
-  if (!deterministic) {  // Box-Muller from two draws of the env's counter-based generator (row = env * n_agents + agent)
+  if (!deterministic) {  // one normal pair of the env's counter-based generator (row = env * n_agents + agent)
     const uint32_t env = (uint32_t)(env_base + row / n_agents), agent = (uint32_t)(row - (row / n_agents) * n_agents);  // env: index in the whole batch (sigmaenv_config_t.env_index_base)
-    const float u1 = ((float)(rng_u32(seed, counter, env, agent, 7000u) >> 8) + 0.5f) * (1.0f / 16777216.0f);
-    const float u2 = ((float)(rng_u32(seed, counter, env, agent, 7001u) >> 8) + 0.5f) * (1.0f / 16777216.0f);
-    const float rad = sqrtf(-2.0f * logf(u1));
-    float sn, cs;
-    sincosf(6.283185307179586f * u2, &sn, &cs);
-    z0 = rad * cs; z1 = rad * sn;
+    rng_normal_pair(seed, counter, env, agent, DRAW_ACTOR, &z0, &z1);
   }
   const float x0 = loc0 + sc0 * z0, x1 = loc1 + sc1 * z1;
-  const float EPS = 1e-6f;
-  const float y0 = fminf(fmaxf(tanhf(x0), -1.0f + EPS), 1.0f - EPS), y1 = fminf(fmaxf(tanhf(x1), -1.0f + EPS), 1.0f - EPS);
   const float h0 = 0.5f * (high[0] - low[0]), h1 = 0.5f * (high[1] - low[1]);
-  *reinterpret_cast<float2*>(actions + (size_t)row * 2) = make_float2(low[0] + (y0 + 1.0f) * h0, low[1] + (y1 + 1.0f) * h1);
-  if (log_prob) {
-    const float LOG_SQRT_2PI = 0.91893853320467274f, LOG2 = 0.69314718055994531f;
-    const float j0 = 2.0f * (LOG2 - x0 - softplus(-2.0f * x0)), j1 = 2.0f * (LOG2 - x1 - softplus(-2.0f * x1));
-    const float lp0 = -0.5f * z0 * z0 - logf(sc0) - LOG_SQRT_2PI - j0 - logf(h0);
-    const float lp1 = -0.5f * z1 * z1 - logf(sc1) - LOG_SQRT_2PI - j1 - logf(h1);
-    log_prob[row] = lp0 + lp1;
-  }
+  *reinterpret_cast<float2*>(actions + (size_t)row * 2) = make_float2(tn_affine(low[0], tn_squash(x0), h0), tn_affine(low[1], tn_squash(x1), h1));
+  if (log_prob) log_prob[row] = (tn_log_density(z0, logf(sc0), x0) - logf(h0)) + (tn_log_density(z1, logf(sc1), x1) - logf(h1));
 }
 
 // weights global (L2) -> LDS, eight 16-byte loads in flight per thread (the copy is a chain of L2 round trips otherwise)

@@ -14,10 +14,11 @@
 
 #include "../../include/sigmaenv.h"
 #include "../../include/sigma_trig_f32.h"
+#include "sigmaenv_dist.h"  // rng_u32, the draw table and the word-to-number conversions
 
 #define NS SIGMAENV_N_SHORT_TERM
 #define PI32 3.14159274101257324f
-#define TWO_PI32 6.28318548202514648f
+#define TWO_PI32 (2.0f * PI32) /* exact: float32(2 pi) */
 
 namespace sigmadev {
 
@@ -550,19 +551,6 @@ __device__ __forceinline__ void row16_or2_u32(unsigned& a, unsigned& b) {
                : "+v"(a), "+v"(b));
 }
 
-// counter-based RNG (specification shared with the oracle): 32-bit multiplicative mix + murmur3 finalisers over (seed, counter, env, agent, draw)
-__device__ __forceinline__ uint32_t rng_u32(uint64_t seed, uint64_t counter, uint32_t env, uint32_t agent, uint32_t draw) {
-  uint32_t h = (uint32_t)seed ^ ((uint32_t)(seed >> 32) * 0x9E3779B9u);
-  h ^= ((uint32_t)counter + 0x7F4A7C15u) * 0x85EBCA6Bu;
-  h ^= (env + 0x165667B1u) * 0xC2B2AE35u;
-  h ^= (agent + 0x27D4EB2Fu) * 0x9E3779B1u;
-  h ^= (draw + 0x61C88647u) * 0x85EBCA77u;
-  h ^= h >> 16; h *= 0x85EBCA6Bu; h ^= h >> 13; h *= 0xC2B2AE35u; h ^= h >> 16;   /* murmur3 fmix32, twice */
-  h += 0x9E3779B9u;
-  h ^= h >> 16; h *= 0x85EBCA6Bu; h ^= h >> 13; h *= 0xC2B2AE35u; h ^= h >> 16;
-  return h;
-}
-
 // observation noise of element k of agent `agent` of env `env_global` at the env's counters (episodes_reset, timer.step): level * U[0, 1)
 // (observation_provider_rt.py:613-618; specification shared with the oracle, see sigmaenv_config_t.obs_noise_level).  The reference draws rand_like on EVERY
 // observation() call: the observations a step or a reset produces are told apart by the env's own counters, and an observation that is TAKEN AGAIN at the same
@@ -570,8 +558,7 @@ __device__ __forceinline__ uint32_t rng_u32(uint64_t seed, uint64_t counter, uin
 __device__ __forceinline__ float obs_noise(const sigmaenv_config_t& c, int env_global, int agent, int k, int episodes, int step, uint32_t salt) {
   const uint64_t seed = ((uint64_t)c.obs_noise_seed_hi << 32) | c.obs_noise_seed_lo;
   const uint64_t counter = (uint64_t)(uint32_t)episodes * 65537ull + (uint64_t)(uint32_t)step + (uint64_t)(salt * 0x632BE5ABu);
-  const float u = (float)(rng_u32(seed, counter, (uint32_t)env_global, (uint32_t)agent, 9000u + (uint32_t)k) >> 8) * (1.0f / 16777216.0f);
-  return c.obs_noise_level * u;
+  return c.obs_noise_level * rng_uniform(rng_u32(seed, counter, (uint32_t)env_global, (uint32_t)agent, DRAW_OBS_NOISE + (uint32_t)k));
 }
 
 }  // namespace sigmadev

@@ -30,8 +30,6 @@ struct HeadArgs {
   uint64_t seed, counter;
 };
 
-__device__ __forceinline__ float softplus(float v) { return v > 20.0f ? v : log1pf(expf(v)); }
-
 // v + the other 63 lanes' v: the same tree in every lane (fp32 addition commutes), so every lane ends with the same bits
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
@@ -54,33 +52,26 @@ __global__ void __launch_bounds__(256) sigmaenv_ppo_head_kernel(HeadArgs a) {
       const float4 o = reinterpret_cast<const float4*>(a.out)[r];
       const float2 act = reinterpret_cast<const float2*>(a.action)[fr];
       const float old = a.old_logp[fr], A = a.adv[fr], vt = a.vtarget[fr], v = a.value[m];
-      const float BIAS = 0.5254587192925021f, LOG_SQRT_2PI = 0.91893853320467274f, LOG2 = 0.69314718055994531f, EPS = 1e-6f;
-      // the entropy sample's draw: actor_distribution's Box-Muller with the frame as the env and draws 7300 / 7301
-      const float u1 = ((float)(rng_u32(a.seed, a.counter, (uint32_t)f, (uint32_t)n, 7300u) >> 8) + 0.5f) * (1.0f / 16777216.0f);
-      const float u2 = ((float)(rng_u32(a.seed, a.counter, (uint32_t)f, (uint32_t)n, 7301u) >> 8) + 0.5f) * (1.0f / 16777216.0f);
-      const float rad = sqrtf(-2.0f * logf(u1));
-      float sn, cs;
-      sincosf(6.283185307179586f * u2, &sn, &cs);
-      const float loc[2] = {o.x, o.y}, raw[2] = {o.z, o.w}, ac[2] = {act.x, act.y}, z[2] = {rad * cs, rad * sn};
+      // the entropy sample's draw: actor_distribution's normal pair with the frame as the env
+      float z[2];
+      rng_normal_pair(a.seed, a.counter, (uint32_t)f, (uint32_t)n, DRAW_ENTROPY, &z[0], &z[1]);
+      const float loc[2] = {o.x, o.y}, raw[2] = {o.z, o.w}, ac[2] = {act.x, act.y};
       float sig[2], dsdr[2], q[2], xs[2], lp = 0.0f, lps = 0.0f;
 #pragma unroll
       for (int d = 0; d < 2; ++d) {
-        const float w = raw[d] + BIAS;
-        const float s0 = softplus(w) + 0.01f;
-        sig[d] = fmaxf(s0, 1e-4f);
-        dsdr[d] = s0 < 1e-4f ? 0.0f : 1.0f / (1.0f + expf(-w));  // d sigma / d raw = sigmoid(raw + bias); 0 where the 1e-4 floor acts
+        const float s0 = tn_raw_scale(raw[d]);
+        sig[d] = fmaxf(s0, TN_SCALE_LB);
+        dsdr[d] = tn_scale_slope(raw[d], s0);
         const float h = 0.5f * (a.high[d] - a.low[d]), logh = logf(h), logs = logf(sig[d]);
         // log-probability of the recorded action through the inverse transform
-        const float y = fminf(fmaxf((ac[d] - a.low[d]) / h - 1.0f, -1.0f + EPS), 1.0f - EPS);
+        const float y = tn_clamp((ac[d] - a.low[d]) / h - 1.0f);
         const float x = 0.5f * (log1pf(y) - log1pf(-y));
         q[d] = (x - loc[d]) / sig[d];
-        const float jac = 2.0f * (LOG2 - x - softplus(-2.0f * x));
-        const float lpd = -0.5f * q[d] * q[d] - logs - LOG_SQRT_2PI - jac - logh;
+        const float lpd = tn_log_density(q[d], logs, x) - logh;
         lp = d ? lp + lpd : lpd;
         // the entropy sample (never clamped: actor_distribution's expression)
         xs[d] = loc[d] + sig[d] * z[d];
-        const float jacs = 2.0f * (LOG2 - xs[d] - softplus(-2.0f * xs[d]));
-        const float lpsd = -0.5f * z[d] * z[d] - logs - LOG_SQRT_2PI - jacs - logh;
+        const float lpsd = tn_log_density(z[d], logs, xs[d]) - logh;
         lps = d ? lps + lpsd : lpsd;
       }
       const float lw = lp - old;

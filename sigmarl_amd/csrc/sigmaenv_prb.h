@@ -5,7 +5,7 @@
 // functions on the device; a host program runs them on the host (tests/test_prb_check.py holds them bit for bit to the float32 twin of tests/prb_check.py and,
 // within derived bounds, to float64).
 //
-// Plain C++: no HIP include and no other file of the library.  The library compiles it as __host__ __device__ __forceinline__; a host program defines SIGMA_HD as
+// Plain C++: no HIP include and, of the library, only sigmaenv_dist.h (the generator's draw table and uniforms, plain C++ as well).  The library compiles it as __host__ __device__ __forceinline__; a host program defines SIGMA_HD as
 // `static inline` first and includes this header alone.  Every operator below is ONE IEEE fp32 operation in the order written (-ffp-contract=off; `/` is the
 // correctly rounded one; fp32 denormals are kept).
 //
@@ -28,7 +28,7 @@
 // 256 node < cnt_k holds at every level by induction (len >= 1), so the leaf index lies in [0, len) whatever the data: it is never formed from arithmetic on mass.
 //
 // The elements.
-//   u        = ((k >> 8) + 0.5f) * 2^-24 of the generator's word k, draw 7400 keyed (seed, counter, env = slot m, agent = 0);  mass = u * total            prb_uniform
+//   u        = rng_uniform_mid of the generator's word k, draw DRAW_REPLAY keyed (seed, counter, env = slot m, agent = 0) (sigmaenv_dist.h);  mass = u * total   prb_uniform
 //   priority = powf(td + eps, alpha)                       extend and refresh;  powf: the device's is OCML's __ocml_pow_f32, a host's its libm's           prb_priority
 //   weight   = powf(q[index] / q_min, -beta)               (-beta: fl(beta) negated);  the same powf                                                      prb_weight
 //   x        = (sum over i = 0 .. N - 1, in that order, of |(r_i + (td_gamma * v_next) * nd) - v|) / N,  nd = 1 - done      (sigmaenv_gae's td_priority)   prb_x
@@ -39,6 +39,8 @@
 #include <math.h>
 #include <stdint.h>
 
+#include "sigmaenv_dist.h"  // the generator's draw table and its uniforms: as stand-alone as this header
+
 #ifndef SIGMA_HD
 #define SIGMA_HD __host__ __device__ __forceinline__
 #endif
@@ -46,7 +48,7 @@
 #define PRB_FAN 256        /* entries of one node */
 #define PRB_MAX_LEVELS 4   /* levels, the leaves included: capacity <= 2^30 */
 #define PRB_MAX_CAPACITY (1 << 30)
-#define PRB_DRAW 7400u     /* the sampler's draw id, beside 7000 / 7100 / 7200 / 7300 */
+#define PRB_DRAW DRAW_REPLAY /* the sampler's draw id */
 
 // the sums as the descent reads them: sum[0] = the leaves, sum[k] = level k (what lies below len at a level follows from len: prb_cnt)
 struct PrbLevels {
@@ -147,7 +149,7 @@ static inline int prb_descend(const PrbLevels& L, int len, float mass) {
 }
 
 // ---- the elements ----------------------------------------------------------------------------------------------------------------------------------------------------
-SIGMA_HD float prb_uniform(uint32_t k) { return ((float)(k >> 8) + 0.5f) * (1.0f / 16777216.0f); }
+SIGMA_HD float prb_uniform(uint32_t k) { return rng_uniform_mid(k); }
 SIGMA_HD float prb_priority(float td, float eps, float alpha) { return powf(td + eps, alpha); }
 SIGMA_HD float prb_weight(float q, float q_min, float neg_beta) { return powf(q / q_min, neg_beta); }
 // reward[0 .. N) of the frame, its done flag, the critic's two values

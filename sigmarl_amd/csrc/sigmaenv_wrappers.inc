@@ -16,30 +16,22 @@
 namespace wrap {
 
 // NormalParamExtractor + 1-D TanhNormal on [-1, 1] of the priority actor (priority_module.py:34-66), one agent row; `out2` = (loc, raw scale).  With the
-// trivial bounds torchrl applies no affine map: the score is the clamped tanh itself.
+// trivial bounds torchrl applies no affine map: the score is the clamped tanh itself (the head of sigmaenv_dist.h in one dimension).
 __global__ void __launch_bounds__(256) sigmaenv_priority_head_kernel(const float* __restrict__ out2, int R, int n_agents, int env_base, float* __restrict__ scores,
                                                                      float* __restrict__ log_prob, uint64_t seed, uint64_t counter, int deterministic) {
   sigma_poison_lds();
   const int row = blockIdx.x * blockDim.x + threadIdx.x;
   if (row >= R) return;
   const float2 o = reinterpret_cast<const float2*>(out2)[row];
-  const float BIAS = 0.5254587192925021f;  // ln(e^0.99 - 1), as actor_distribution
-  auto softplus = [](float v) { return v > 20.0f ? v : log1pf(expf(v)); };
-  const float sc = fmaxf(softplus(o.y + BIAS) + 0.01f, 1e-4f);
+  const float sc = tn_scale(o.y);
   float z = 0.0f;
-  if (!deterministic) {  // Box-Muller (cosine branch) from two draws of the env's counter-based generator
+  if (!deterministic) {  // the cosine branch of a normal pair of the env's counter-based generator
     const uint32_t env = (uint32_t)(env_base + row / n_agents), agent = (uint32_t)(row - (row / n_agents) * n_agents);
-    const float u1 = ((float)(rng_u32(seed, counter, env, agent, 7100u) >> 8) + 0.5f) * (1.0f / 16777216.0f);
-    const float u2 = ((float)(rng_u32(seed, counter, env, agent, 7101u) >> 8) + 0.5f) * (1.0f / 16777216.0f);
-    z = sqrtf(-2.0f * logf(u1)) * cosf(6.283185307179586f * u2);
+    z = rng_normal_cos(seed, counter, env, agent, DRAW_PRIORITY);
   }
   const float x = o.x + sc * z;
-  const float EPS = 1e-6f;
-  scores[row] = fminf(fmaxf(tanhf(x), -1.0f + EPS), 1.0f - EPS);
-  if (log_prob) {
-    const float LOG_SQRT_2PI = 0.91893853320467274f, LOG2 = 0.69314718055994531f;
-    log_prob[row] = -0.5f * z * z - logf(sc) - LOG_SQRT_2PI - 2.0f * (LOG2 - x - softplus(-2.0f * x));
-  }
+  scores[row] = tn_squash(x);
+  if (log_prob) log_prob[row] = tn_log_density(z, logf(sc), x);
 }
 
 // rank_agents (priority_module.py:118-135): position of agent i in env b = the number of agents that sort before it (higher score, or equal score and lower
@@ -68,7 +60,7 @@ __global__ void __launch_bounds__(256) sigmaenv_priority_random_kernel(int B, in
   if (b >= B) return;
   int32_t* r = ranks + (size_t)b * N;
   for (int i = 0; i < N; ++i) {
-    const int j = (int)__umulhi(rng_u32(seed, counter, (uint32_t)(env_base + b), (uint32_t)i, 7200u), (uint32_t)(i + 1));
+    const int j = (int)rng_below(rng_u32(seed, counter, (uint32_t)(env_base + b), (uint32_t)i, DRAW_SHUFFLE), (uint32_t)(i + 1));
     if (j != i) r[i] = r[j];
     r[j] = i;
   }

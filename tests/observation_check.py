@@ -70,6 +70,7 @@ from policy_head_check import rng_u32
 from sigmarl_amd import capi
 
 U = 2.0 ** -24
+NOISE_DRAW = 9000  # sigmaenv_dist.h DRAW_OBS_NOISE: element k of a row draws NOISE_DRAW + k
 C1 = 1.01
 TINY = 2.0 ** -150
 ROOT_TINY = 2.0 ** -74.5
@@ -353,7 +354,7 @@ def noise_draws(cfg, bufs, D):
     seed = (int(cfg.obs_noise_seed_hi) << 32) | int(cfg.obs_noise_seed_lo)
     counter = ((tim[:, 3] & 0xFFFFFFFF) * 65537 + (tim[:, 0] & 0xFFFFFFFF)).astype(np.uint64)
     env = (int(cfg.env_index_base) + np.arange(B)).astype(np.uint32)
-    h = rng_u32(seed, counter[:, None, None], env[:, None, None], np.arange(N, dtype=np.uint32)[None, :, None], (9000 + np.arange(D)).astype(np.uint32)[None, None, :])
+    h = rng_u32(seed, counter[:, None, None], env[:, None, None], np.arange(N, dtype=np.uint32)[None, :, None], (NOISE_DRAW + np.arange(D)).astype(np.uint32)[None, None, :])
     draw = (np.asarray(h, np.uint32) >> np.uint32(8)).astype(np.float64) * 2.0 ** -24
     return float(level) * draw
 

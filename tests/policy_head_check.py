@@ -41,7 +41,7 @@ CLAMP_HI = np.float32(1.0) - EPS32             # 1 - 17 * 2^-24
 CLAMP_LO = np.float32(-1.0) + EPS32
 TWO_PI32 = np.float32(6.283185307179586)
 
-ACTOR_DRAWS, PRIORITY_DRAWS, SHUFFLE_DRAW = (7000, 7001), (7100, 7101), 7200
+ACTOR_DRAWS, PRIORITY_DRAWS, SHUFFLE_DRAW = (7000, 7001), (7100, 7101), 7200  # sigmaenv_dist.h: DRAW_ACTOR, DRAW_PRIORITY (+ 1 each), DRAW_SHUFFLE
 _M = 0xFFFFFFFF
 
 
@@ -75,7 +75,7 @@ def stream_key(env, agent):
 
 
 def rng_u32(seed, counter, env, agent, draw):
-    """sigmaenv_device.h rng_u32, vectorised (arguments broadcast): ``seed`` enters with both 32-bit words, ``counter`` with its low 32 bits only."""
+    """sigmaenv_dist.h rng_u32, vectorised (arguments broadcast): ``seed`` enters with both 32-bit words, ``counter`` with its low 32 bits only."""
     with np.errstate(over="ignore"):
         h = _u32(seed) ^ (_hi32(seed) * np.uint32(0x9E3779B9))
         h = h ^ ((_u32(counter) + np.uint32(0x7F4A7C15)) * np.uint32(0x85EBCA6B))
@@ -127,7 +127,8 @@ def random_ranks(seed, counter, env, N):
 
 
 # ---- the head -----------------------------------------------------------------------------------------------------------------------
-def _softplus(v, dtype, shortcut=True):
+def softplus(v, dtype, shortcut=True):
+    """float32: the kernels' v > 20 ? v : log1p(exp(v)); float64: exact at either side of the switch"""
     v = np.asarray(v, dtype)
     with np.errstate(over="ignore"):
         s = np.log1p(np.exp(np.minimum(v, dtype(80.0))))
@@ -136,10 +137,22 @@ def _softplus(v, dtype, shortcut=True):
     return np.where(v > 30.0, v + np.log1p(np.exp(-np.maximum(v, 30.0))), s)  # (exact in float64 at either side)
 
 
+def raw_scale_of(raw, dtype=np.float64):
+    """softplus(raw + ln(e^0.99 - 1)) + 0.01: the scale before its 1e-4 floor"""
+    return softplus(np.asarray(raw, dtype) + dtype(BIAS), dtype) + dtype(0.01)
+
+
 def scale_of(raw, dtype=np.float64):
     """NormalParamExtractor "biased_softplus_1.0": max(softplus(raw + ln(e^0.99 - 1)) + 0.01, 1e-4)"""
-    raw = np.asarray(raw, dtype)
-    return np.maximum(_softplus(raw + dtype(BIAS), dtype) + dtype(0.01), dtype(1e-4))
+    return np.maximum(raw_scale_of(raw, dtype), dtype(1e-4))
+
+
+def log_density(q, log_scale, x, dtype):
+    """(-q^2 / 2 - log scale - log sqrt(2 pi) - 2 (log 2 - x - softplus(-2 x)), softplus(-2 x)) per dimension, q = (x - loc) / scale (a sample's own x: q = z):
+    the TanhNormal log-density without the - log h of the affine map, in the kernels' operation order"""
+    f = dtype
+    sp = softplus(f(-2.0) * x, f)
+    return f(-0.5) * q * q - log_scale - f(LOG_SQRT_2PI) - f(2.0) * (f(LOG2) - x - sp), sp
 
 
 def head(loc, scale, z, low=None, high=None, dtype=np.float64, zmag=None):
@@ -158,9 +171,7 @@ def head(loc, scale, z, low=None, high=None, dtype=np.float64, zmag=None):
         log_h = np.log(h)
     else:
         h, action, log_h = f(1.0), y, f(0.0)
-    sp = _softplus(f(-2.0) * x, f)
-    jac = f(2.0) * (f(LOG2) - x - sp)
-    lp_d = f(-0.5) * z * z - np.log(scale) - f(LOG_SQRT_2PI) - jac
+    lp_d, sp = log_density(z, np.log(scale), x, f)
     if affine:
         lp_d = lp_d - log_h
     lp = lp_d[:, 0] + lp_d[:, 1] if lp_d.shape[-1] == 2 else lp_d[:, 0]

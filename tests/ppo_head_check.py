@@ -38,7 +38,7 @@ import policy_head_check as phc
 MARGIN = 4.0
 FULL_ROWS = 1000
 U23 = 2.0 ** -23
-ENTROPY_DRAWS = (7300, 7301)
+ENTROPY_DRAWS = (7300, 7301)  # sigmaenv_dist.h: DRAW_ENTROPY, + 1
 BIAS, LOG_SQRT_2PI, LOG2 = phc.BIAS, phc.LOG_SQRT_2PI, phc.LOG2
 RESULT = ("loss_objective", "loss_entropy", "loss_critic", "entropy", "clip_fraction", "kl_approx")
 DEFECTS = ("ratio_clip", "tie_clamped_neg", "no_dsigma_draw", "entropy_no_sigma_grad", "smooth_l1_half", "critic_mean", "index_on_out")
@@ -93,14 +93,6 @@ def sum_depth(rows):
     return 6 + 3 + -(-G // 64) + 6
 
 
-def _softplus(v, f):
-    with np.errstate(over="ignore"):
-        s = np.log1p(np.exp(np.minimum(v, f(80.0))))
-    if f == np.float32:
-        return np.where(v > f(20.0), v, s)
-    return np.where(v > 30.0, v + np.log1p(np.exp(-np.maximum(v, 30.0))), s)
-
-
 def draws(case, dtype=np.float64, magnitude=False):
     """(z [M, N, 2]) of the entropy sample: key (seed, counter, env = frame, agent), draws 7300 / 7301"""
     M, N = case["out"].shape[:2]
@@ -137,7 +129,7 @@ def head(case, dtype=np.float64, defect=None):
     z = draws(case, f)
     loc, raw = o[..., :2], o[..., 2:]
     w = raw + f(BIAS)
-    s0 = _softplus(w, f) + f(0.01)
+    s0 = phc.raw_scale_of(raw, f)
     sig = np.maximum(s0, f(1e-4))
     with np.errstate(over="ignore"):
         dsdr = np.where(s0 < f(1e-4), f(0.0), f(1.0) / (f(1.0) + np.exp(-w)))
@@ -147,14 +139,12 @@ def head(case, dtype=np.float64, defect=None):
     y = np.minimum(np.maximum((act - low) / h - f(1.0), f(-1.0) + EPS), f(1.0) - EPS)
     x = f(0.5) * (np.log1p(y) - np.log1p(-y))
     q = (x - loc) / sig
-    sp = _softplus(f(-2.0) * x, f)
-    jac = f(2.0) * (f(LOG2) - x - sp)
-    lpd = f(-0.5) * q * q - logs - f(LOG_SQRT_2PI) - jac - logh
+    lpd, sp = phc.log_density(q, logs, x, f)
+    lpd = lpd - logh
     lp = lpd[..., 0] + lpd[..., 1]
     xs = loc + sig * z
-    sps = _softplus(f(-2.0) * xs, f)
-    jacs = f(2.0) * (f(LOG2) - xs - sps)
-    lpsd = f(-0.5) * z * z - logs - f(LOG_SQRT_2PI) - jacs - logh
+    lpsd, sps = phc.log_density(z, logs, xs, f)
+    lpsd = lpsd - logh
     lps = lpsd[..., 0] + lpsd[..., 1]
     lw = lp - old
     cl = np.minimum(np.maximum(lw, lo), hi)
@@ -407,7 +397,7 @@ def synthetic_case(M=512, N=3, F=700, seed=1, entropy_coeff=0.01, critic_coeff=1
     lo_, hi_ = np.asarray(low, np.float64), np.asarray(high, np.float64)
     hh = 0.5 * (hi_ - lo_)
     y = np.clip((rec["action"].astype(np.float64) - lo_) / hh - 1.0, -1 + 1e-6, 1 - 1e-6)
-    sig = np.maximum(_softplus(outF[..., 2:].astype(np.float64) + BIAS, np.float64) + 0.01, 1e-4)
+    sig = phc.scale_of(outF[..., 2:], np.float64)
     outF[..., :2] = (np.arctanh(y) - sig * g.standard_normal((F, N, 2)) * 1.2).astype(np.float32)
     out, value = outF[index], valueF[index]
     rec = records_for(out, value, index, F, N, seed + 1, low, high)

@@ -11,7 +11,7 @@ import numpy as np
 
 import policy_head_check as ph
 
-FAN, DRAW = 256, 7400
+FAN, DRAW = 256, 7400  # DRAW: sigmaenv_dist.h DRAW_REPLAY
 ALPHA, BETA, EPS, TD_GAMMA = 0.7, 0.6, 1e-8, 0.9
 f32, f64 = np.float32, np.float64
 U = 2.0 ** -24  # the unit roundoff of float32

@@ -62,7 +62,8 @@ def test_level_sizes_and_the_draw_id():
         assert capi.prb_level_sizes(c) == pc.level_sizes(c)
     assert capi.PRB_DRAW == pc.DRAW == 7400 and capi.PRB_FAN == pc.FAN == 256
     hdr = open(os.path.join(ROOT, "sigmarl_amd", "csrc", "sigmaenv_prb.h")).read()
-    assert "#define PRB_DRAW 7400u" in hdr and "#define PRB_FAN 256" in hdr and "#define PRB_MAX_LEVELS 4" in hdr
+    table = open(os.path.join(ROOT, "sigmarl_amd", "csrc", "sigmaenv_dist.h")).read()  # (PRB_DRAW is the draw table's entry)
+    assert "#define PRB_DRAW DRAW_REPLAY " in hdr and "#define DRAW_REPLAY 7400u" in table and "#define PRB_FAN 256" in hdr and "#define PRB_MAX_LEVELS 4" in hdr
 
 
 def test_refusals_before_any_device_call():
