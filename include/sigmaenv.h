@@ -572,6 +572,41 @@ typedef struct sigmaenv_gae_args {
 } sigmaenv_gae_args_t;
 int sigmaenv_gae(sigmaenv_t* h, const sigmaenv_gae_args_t* a);
 
+/* ---- the episode return of a rollout's records (sigmaenv_episode.inc; the arithmetic: sigmaenv_episode.h) ----------------------------------
+ * sigmaenv_episode_return: the RewardSum transform the reference wraps its env in (sigmarl/mappo_cavs.py:178-183: the agents' reward summed into
+ * "episode_reward", reset by the env's done flag) and the number every iteration reports and gates its intermediate models on, episode_reward[done].mean()
+ * (_log_and_save, :468-478; _save_intermediate_model, :498-515), on the records of n_steps rollout steps of this handle.  torchrl is third-party and absent:
+ * RewardSum is restated from its published behaviour, as GAE is.
+ *   slab, slab_stride   as in sigmaenv_gae_args_t: the reward of agent i and the done flag are read IN PLACE at offsets N*D + i and N*(D+1) of the env's row; a
+ *                       record buffer wider than the handle is addressed by pointing slab at the handle's first env and passing the buffer's stride
+ *   carry               device f32 [B, N], in and out: the running return of every agent's open episode on entry (zeros before the first rollout) and on exit
+ *   episode_reward      optional device f32 [n_steps, B, N]: the record E
+ *   result              device f32 [4]: mean, S, K, 0
+ * Element contract: fp32, one IEEE addition per step, no reassociation, forwards over t -- E[t,b,i] = c + r[t,b,i] with c = carry[b,i] at t = 0; after step t
+ * c = (done[t,b] != 0) ? 0 : E[t,b,i]; on exit carry[b,i] = the last c.  The frame that finishes an episode carries the whole episode's return, the next frame
+ * starts from zero; a per-agent re-placement that does not set the env's done flag resets nothing (nor does it in the reference).  The recurrence is sequential in t
+ * on purpose: the record equals the step-by-step fp32 sum bit for bit, which a parallel scan over t would not.
+ * Reduction contract: K = the number of (t,b) with done set, result[2] = (float)K (exact: n_steps * B >= 2^24 is refused);  result[1] = S, the fp32 sum of E[t,b,i]
+ * over the done frames and all i in the order of sigmaenv_episode.h -- within a frame the chain over i = 0 .. N-1 from 0; per env the chain over its done steps, t
+ * ascending, from 0; over the envs one workgroup of 256 lanes: lane l the chain over b = l, l + 256, .. from 0, per wavefront the butterfly v += v[lane ^ m], m = 32,
+ * 16, .., 1, then ((w0 + w1) + w2) + w3 (the longest chain: N + n_steps + ceil(B / 256) + 9 additions);  result[0] = S / (K * N) with K * N formed in fp32 and one
+ * division, NaN when K = 0 (the reference's mean of an empty selection is NaN too);  result[3] = 0.  No atomics: a function of the inputs and (n_steps, B, N)
+ * alone, whatever the scheduling or the launch shape.  Two launches on the handle's stream; nothing waits.  The first call allocates 2 B words: do not make it
+ * inside a stream capture.
+ * n_steps < 1, n_steps * B >= 2^24, a null slab, carry or result, a misaligned tensor, a stride below the handle's block: SIGMAENV_EINVAL with sigmaenv_last_error
+ * set, before any launch. */
+typedef struct sigmaenv_episode_args {
+  int32_t n_steps;
+  int32_t reserved0;               /* zero */
+  const float* slab;
+  int64_t slab_stride;             /* floats between the record blocks of consecutive steps; 0: B * (N*(D+1)+1) */
+  float* carry;                    /* device f32 [B, N], in and out */
+  float* episode_reward;           /* optional device f32 [n_steps, B, N] */
+  float* result;                   /* device f32 [4] */
+  int32_t reserved[6];             /* zero */
+} sigmaenv_episode_args_t;
+int sigmaenv_episode_return(sigmaenv_t* h, const sigmaenv_episode_args_t* a);
+
 /* ---- the clip-PPO loss head of a minibatch update (sigmaenv_ppo.inc) ---------------------------------------------------------------------
  * sigmaenv_ppo_head: torchrl's ClipPPOLoss as sigmarl/modules/optimization_module.py:44-66 configures it (clip_epsilon, entropy_coeff = entropy_eps,
  * normalize_advantage = False, the default smooth-L1 critic loss, samples_mc_entropy = 1) for one minibatch of frames (sigmarl/mappo_cavs.py:389-407, _train_epoch /

@@ -104,6 +104,19 @@ class GaeArgs(C.Structure):
     ]
 
 
+class EpisodeArgs(C.Structure):
+    """``sigmaenv_episode_args_t`` (sigmaenv_episode_return): a rollout's records, the running returns carried between rollouts, the record and the statistics."""
+
+    _fields_ = [
+        ("n_steps", C.c_int32), ("reserved0", C.c_int32), ("slab", C.c_void_p), ("slab_stride", C.c_int64), ("carry", C.c_void_p),
+        ("episode_reward", C.c_void_p), ("result", C.c_void_p), ("reserved", C.c_int32 * 6),
+    ]
+
+
+EPR_LANES, EPR_MAX_FRAMES = 256, 1 << 24  # sigmaenv_episode.h
+EPISODE_RESULT = ("episode_reward_mean", "episode_reward_sum", "episodes_done")  # result[0 .. 2]
+
+
 class PpoHeadArgs(C.Structure):
     """``sigmaenv_ppo_head_args_t`` (sigmaenv_ppo_head): a minibatch's network outputs, the learner's records, the ``dout`` tensors and the loss terms."""
 
@@ -299,6 +312,7 @@ _PRODUCT_ONLY = {
     "priority_rank": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "priority_random": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p]),
     "gae": (C.c_int, [C.c_void_p, C.POINTER(GaeArgs)]),
+    "episode_return": (C.c_int, [C.c_void_p, C.POINTER(EpisodeArgs)]),
     "launch_shape": (C.c_int, [C.c_void_p, C.POINTER(LaunchShape)]),
 }
 

@@ -1778,6 +1778,7 @@ struct sigmaenv {
   float* rollout_obs_rec = nullptr;   // root-observation record of sigmaenv_rollout* (sigmaenv_set_rollout_obs_record): step t copies SIGMAENV_BUF_OBS to base + t * stride
   size_t rollout_obs_stride = 0;      // floats between its blocks (0: B * N * D)
   uint32_t* learn_minmax = nullptr;   // [2] bits of the min / max of sigmaenv_gae's raw TD errors (sigmaenv_learn.inc), allocated by the first call that asks for priorities
+  float* episode_ws = nullptr;        // [B] f32 sums, then [B] i32 counts of the envs' done frames (sigmaenv_episode.inc), allocated by the first sigmaenv_episode_return
   int grid = 1;
   void* bufs[SIGMAENV_BUF_COUNT] = {nullptr};
   size_t buf_bytes[SIGMAENV_BUF_COUNT] = {0};
@@ -2669,6 +2670,8 @@ extern "C" int sigmaenv_trig_selftest(sigmaenv_t* h, int32_t kind, int32_t n, co
 #include "sigmaenv_optim.inc"
 #include "sigmaenv_wrappers.inc"
 #include "sigmaenv_learn.inc"
+#include "sigmaenv_episode.h"
+#include "sigmaenv_episode.inc"
 #include "sigmaenv_ppo.inc"
 #include "sigmaenv_prb.h"
 #include "sigmaenv_prb.inc"

@@ -16,6 +16,10 @@ and the learner's side, ``_train_epoch`` / ``_train_on_batch`` (``sigmarl/mappo_
                                    network's weight forms, three launches and no host wait (``:421-426``); ``resolve`` = the one wait, before the next rollout
   ``update``                       the epochs x minibatches loop: apply -> head -> backward -> ``Adam.step`` (the device route), or with a torch optimiser
                                    -> ``clip_grad_norm_`` -> ``optim.step()`` -> ``load``
+  ``EpisodeReturns``               ``sigmaenv_episode_return``: the ``RewardSum`` record ``episode_reward`` and its done-frame mean, the number every iteration reports
+                                   (``sigmarl/mappo_cavs.py:178-183``, ``:468-478``), carried across rollouts on the device
+  ``train_iteration`` / ``train``  the trainer's iteration (``:126-150``) from those parts -- collect, the episode statistics, extend, update, the learning rate of
+                                   the next iteration (``lr_at``: ``_update_learning_rate``, ``:517-525``) -- and the loop over it with the counter bookkeeping
 and, with ``Parameters.is_prb``, the reference's second buffer (``sigmarl/mappo_cavs.py:321-332``, ``:397-407``, ``:431-456``):
   ``PrioritizedBuffer``            ``sigmaenv_prb_*``: the priorities of the batch's frames as a device object -- ``extend`` from ``collect``'s ``td_error``, ``sample``
                                    with replacement in place of the permutation chunk, ``refresh`` of the sampled frames' priorities behind every optimiser step;
@@ -78,13 +82,16 @@ def gae(env, slab: torch.Tensor, state_value: torch.Tensor, next_state_value: to
 
 
 def collect(env, actor, critic, T: int, params=None, gamma: float | None = None, lmbda: float | None = None, td_gamma: float = TD_GAMMA, td_error: bool = True,
-            seed: int = 0, counter0: int = 0, **rollout_kw) -> dict:
+            seed: int = 0, counter0: int = 0, returns: "EpisodeReturns | None" = None, **rollout_kw) -> dict:
     """One learner-ready batch: ``T`` steps of the device rollout (``Actor.rollout``, ``rollout_kw`` = its wrapper / path / precision arguments), the critic on
     both sides of every step, GAE and the TD-error priorities -- enqueued on the env's stream, nothing copied in between.  ``gamma`` / ``lmbda`` come from
     ``params`` (a ``Parameters``; default: the env's) unless given.  Returns device tensors under the reference tensordict's keys:
     ``observation [T,B,N,D]``, ``action [T,B,N,2]``, ``sample_log_prob [T,B,N]``, ``("next", "observation") [T,B,N,D]``, ``("next", "reward") [T,B,N]``,
     ``("next", "done") [T,B]`` (the record's float flag) -- the three zero-copy views of the record, which is returned whole as ``"slab"`` --, ``state_value`` /
-    ``("next", "state_value") [T,B]`` (one value per env: every agent's), ``advantage`` / ``value_target [T,B,N]``, ``td_error [T,B]``."""
+    ``("next", "state_value") [T,B]`` (one value per env: every agent's), ``advantage`` / ``value_target [T,B,N]``, ``td_error [T,B]``.  With ``returns`` (an ``EpisodeReturns`` of this env, which carries the
+    open episodes' sums from one call to the next) the batch gains ``("next", "episode_reward") [T,B,N]`` and ``"episode_stats"`` (``EpisodeReturns.update``)."""
+    if returns is not None and not (isinstance(returns, EpisodeReturns) and returns.env is env):
+        raise TypeError("collect(): returns must be a learn.EpisodeReturns of this env")
     p = params if params is not None else getattr(env, "parameters", None)
     if p is None and (gamma is None or lmbda is None):
         raise ValueError("collect(): gamma and lmbda, or a Parameters to take them from")
@@ -108,7 +115,89 @@ def collect(env, actor, critic, T: int, params=None, gamma: float | None = None,
     }
     if td is not None:
         out["td_error"] = td
+    if returns is not None:
+        out[("next", "episode_reward")], out["episode_stats"] = returns.update(slab, T)
     return out
+
+
+class EpisodeReturns:
+    """The reference's ``RewardSum`` transform (``sigmarl/mappo_cavs.py:178-183``) and the number every iteration reports, ``episode_reward[done].mean()``
+    (``_log_and_save``, ``:468-478``), on the device (``sigmaenv_episode_return``; every formula and the order of every sum: ``include/sigmaenv.h``,
+    ``sigmarl_amd/csrc/sigmaenv_episode.h``).  Owns ``carry [B, N]``: the running return of every agent's open episode, zeros at first, carried from one rollout's
+    records to the next.  ``reset()`` zeros it: call it after any ``env.reset_*`` made outside the rollout (the rollout's own resets set the done flag the record
+    holds; a reset from outside leaves no trace in the records)."""
+
+    def __init__(self, env):
+        self.env = env
+        self.carry = torch.zeros((env.B, env.N), dtype=torch.float32, device=env.device)
+
+    def reset(self) -> None:
+        self.carry.zero_()
+
+    def update(self, slab: torch.Tensor, T: int | None = None, env_first: int = 0, episode_reward=None):
+        """The records ``slab [T, Bt, W]`` of the rollout that followed the last one this object saw (``Bt >= env.B``: the env owns the envs ``[env_first,
+        env_first + env.B)`` of the buffer, as for ``gae``): returns ``(episode_reward [T,B,N], stats)`` -- ``episode_reward[t,b,i]`` the return of agent ``i``'s
+        episode up to and including step ``t`` (the frame that finishes an episode carries the whole of it), ``stats`` = ``{"episode_reward_mean",
+        "episode_reward_sum", "episodes_done"}``, device scalars (views of one ``result`` tensor): the mean over the done frames and all agents (NaN when no frame is
+        done), the sum, the number of done frames.  ``episode_reward``: ``None`` = a new tensor, the tensor to fill, or ``False`` = not recorded (``None`` is
+        returned in its place; ``stats`` and ``carry`` are the same).  ``carry`` is advanced in place.  Enqueued on the env's stream; nothing waits."""
+        env = self.env
+        B, N, D = env.B, env.N, env.D
+        W = N * (D + 1) + 1
+        if not isinstance(slab, torch.Tensor) or not (slab.is_cuda and slab.dtype == torch.float32 and slab.is_contiguous() and slab.dim() == 3 and slab.shape[2] == W):
+            raise TypeError(f"slab must be a contiguous float32 CUDA tensor [T, Bt, {W}]")
+        Ts, Bt, e0 = slab.shape[0], slab.shape[1], int(env_first)
+        T = Ts if T is None else int(T)
+        if not 1 <= T <= Ts or not 0 <= e0 <= Bt - B:
+            raise ValueError(f"slab {list(slab.shape)}: {T} steps within its {Ts} (at least one), and envs [{e0}, {e0 + B}) inside its {Bt}")
+        kw = dict(dtype=torch.float32, device=slab.device)
+        if episode_reward is None:
+            er = torch.empty((T, B, N), **kw)
+        elif episode_reward is False:
+            er = None
+        else:
+            er = check_record(episode_reward, (T, B, N), "episode_reward")
+        result = torch.empty((4,), **kw)
+        a = episode_args(env, T, slab.data_ptr() + 4 * e0 * W, Bt * W, self.carry.data_ptr(), result.data_ptr(), er.data_ptr() if er is not None else None)
+        cur = torch.cuda.current_stream(env.device)
+        with torch.cuda.device(env.device):  # on the env's stream after what torch's current stream holds, which then waits for it (ppo_head's discipline)
+            env.stream.wait_stream(cur)
+            rc = env.lib.episode_return(env.h, C.byref(a))
+            if rc != 0:
+                raise RuntimeError(f"sigmaenv_episode_return failed with code {rc}: {env.lib.last_error(env.h).decode()}")
+            cur.wait_stream(env.stream)
+        for t in (slab, self.carry, result) + ((er,) if er is not None else ()):
+            t.record_stream(env.stream)
+        return er, {k: result[i] for i, k in enumerate(capi.EPISODE_RESULT)}
+
+    @staticmethod
+    def mean(stats: dict) -> float:
+        """The one host read: the reference's reported number, ``round(episode_reward[done].mean().item(), 2)`` -- NaN when no episode ended in the batch."""
+        return round(float(stats["episode_reward_mean"]), 2)
+
+
+def episode_args(env, T: int, slab_ptr, slab_stride: int, carry_ptr, result_ptr, episode_reward_ptr=None) -> "capi.EpisodeArgs":
+    """``sigmaenv_episode_args_t`` for ``T`` steps of ``env``'s records at the device address ``slab_ptr``, after the refusals the library makes before any launch
+    (``ValueError``): ``T < 1``, ``T * B >= 2^24`` (the done-frame count is reported as a float), a stride below the handle's own block ``B * W`` (0 = that
+    block), a null ``slab``, ``carry`` or ``result``, an address that is not 4-byte aligned."""
+    T, B, stride = int(T), int(env.B), int(slab_stride)
+    own = B * (env.N * (env.D + 1) + 1)
+    if T < 1:
+        raise ValueError(f"episode return: n_steps = {T} must be >= 1")
+    if T * B >= capi.EPR_MAX_FRAMES:
+        raise ValueError(f"episode return: n_steps * B = {T * B} must stay below 2^24")
+    if stride != 0 and stride < own:
+        raise ValueError(f"episode return: slab_stride = {stride} is below the handle's own record block of {own} floats")
+    for ptr, what in ((slab_ptr, "slab"), (carry_ptr, "carry"), (result_ptr, "result")):
+        if not ptr:
+            raise ValueError(f"episode return: {what} is null")
+    for ptr in (slab_ptr, carry_ptr, result_ptr, episode_reward_ptr):
+        if ptr and int(ptr) & 3:
+            raise ValueError("episode return: a tensor that is not 4-byte aligned")
+    a = capi.EpisodeArgs()
+    a.n_steps, a.slab, a.slab_stride, a.carry, a.result = T, slab_ptr, stride, carry_ptr, result_ptr
+    a.episode_reward = episode_reward_ptr if episode_reward_ptr else None
+    return a
 
 
 # ---- the learner's side: minibatches of frames, the clip-PPO head, the update loop --------------------------------------------------------
@@ -195,7 +284,8 @@ class Adam:
     ``include/sigmaenv.h``, ``sigmarl_amd/csrc/sigmaenv_optim.h``).  ``networks``: a sequence of ``(Actor | Mlp32, torch module)`` pairs -- the device network and
     the module it was built or last loaded from, on ``env``'s device; at most 4 networks of together 32 tensors.  Owns ``exp_avg`` / ``exp_avg_sq`` of every
     parameter (``state``: per network, per layer, weight then bias -- the order of ``module.parameters()``) and the step count ``t`` (the steps taken so far).
-    ``lr`` is a plain attribute: the reference's linear decay (``sigmarl/mappo_cavs.py:520-523``) sets it between updates."""
+    ``lr`` is a plain attribute: the reference's linear decay (``sigmarl/mappo_cavs.py:520-523``) sets it between updates (``lr_at`` / ``set_lr``, which
+    ``train_iteration`` calls)."""
 
     def __init__(self, env, networks, lr: float, betas=(0.9, 0.999), eps: float = 1e-8):
         self.env, self.lr, self.betas, self.eps, self.t = env, float(lr), (float(betas[0]), float(betas[1])), float(eps), 0
@@ -579,3 +669,99 @@ def update(env, actor, critic, actor_module, critic_module, optim, batch: dict, 
     if device_route and k:
         optim.resolve()
     return infos
+
+
+# ---- the trainer's iteration and the loop over it ---------------------------------------------------------------------------------------------
+def lr_at(params, i_iter: int) -> float:
+    """The learning rate iteration ``i_iter`` (1-based) trains at under the reference's linear decay AS IT RUNS (``_update_learning_rate``,
+    ``sigmarl/mappo_cavs.py:517-525``): the value set at the end of iteration ``k`` is ``lr_min + (lr - lr_min) * (1 - pbar.n / n_iters)`` and ``pbar.n`` is read
+    BEFORE ``pbar.update()``, so it is ``k - 1`` there.  The schedule therefore lags one iteration: iterations 1 and 2 both train at ``lr`` (iteration 2 at
+    ``lr_min + (lr - lr_min) * 1.0``, the same number up to one rounding), iteration ``k >= 2`` at ``lr_min + (lr - lr_min) * (1 - (k - 2) / n_iters)``, and the last
+    iteration ``n_iters`` never reaches ``lr_min``.  Python floats, the reference's own expression."""
+    k = int(i_iter)
+    if k <= 1:
+        return float(params.lr)
+    lr_decay = (params.lr - params.lr_min) * (1 - ((k - 2) / params.n_iters))
+    return params.lr_min + lr_decay
+
+
+def set_lr(optim, lr: float) -> None:
+    """``lr`` into the optimiser: the ``lr`` attribute of a ``learn.Adam``, every ``param_groups[...]["lr"]`` of a torch optimiser."""
+    if isinstance(optim, Adam):
+        optim.lr = float(lr)
+    else:
+        for g in optim.param_groups:
+            g["lr"] = lr
+
+
+def steps_per_iteration(params, frames: int, num_epochs: int | None = None, minibatch_size: int | None = None) -> int:
+    """The optimiser steps ``update`` takes on a batch of ``frames`` frames: ``num_epochs * (frames // minibatch_size)``."""
+    ne = int(num_epochs if num_epochs is not None else params.num_epochs)
+    mb = int(minibatch_size if minibatch_size is not None else params.minibatch_size)
+    return ne * (int(frames) // mb)
+
+
+def train_iteration(env, actor, critic, actor_module, critic_module, optim, returns: EpisodeReturns, params=None, *, i_iter: int = 1, buffer: PrioritizedBuffer | None = None,
+                    frames_per_batch: int | None = None, seed: int = 0, counter0: int = 0, generator: torch.Generator | None = None, td_gamma: float = TD_GAMMA,
+                    rollout_kw: dict | None = None, **update_kw):
+    """Iteration ``i_iter`` (1-based) of the reference's training loop (``sigmarl/mappo_cavs.py:126-150``) from its parts:
+      1. ``collect`` with ``T = frames_per_batch // env.B`` steps (``frames_per_batch``: ``params``' unless given; not a multiple of ``env.B``: ``ValueError``) and
+         ``returns``: the rollout, the critic's values, GAE, the TD-error priorities, the episode returns;
+      2. the episode statistics (``batch["episode_stats"]``, device scalars: nothing is read here);
+      3. with ``Parameters.is_prb`` (a ``buffer``, a ``PrioritizedBuffer`` of ``frames_per_batch`` frames, is then required): ``buffer.extend(batch["td_error"])``;
+      4. ``update`` (``update_kw``: its ``num_epochs``, ``minibatch_size``, ``clip_epsilon``, ``entropy_coeff``, ``max_grad_norm``, ``critic_coeff``);
+      5. the learning rate of the NEXT iteration, ``lr_at(params, i_iter + 1)``, into ``optim`` (``set_lr``).
+    The counters, stated once: with ``j = i_iter - 1`` the rollout's steps are keyed ``(seed, counter0 + j * T + t)`` and the update's steps ``(seed, counter0 + j *
+    steps_per_iteration + k)`` -- within a draw id of ``sigmaenv_dist.h`` no ``(seed, counter)`` is used twice across iterations, and the rollout's draw ids, the
+    entropy sample's and the replay sampler's are different entries of that table, so the two counter ranges may overlap.  Returns ``(batch, infos, stats)``."""
+    p = params if params is not None else getattr(env, "parameters", None)
+    if p is None:
+        raise ValueError("train_iteration(): a Parameters (frames_per_batch, the discounts, the schedule)")
+    k = int(i_iter)
+    if k < 1:
+        raise ValueError(f"train_iteration(): i_iter = {i_iter} is 1-based")
+    fpb = int(frames_per_batch if frames_per_batch is not None else p.frames_per_batch)
+    if fpb < env.B or fpb % env.B:
+        raise ValueError(f"train_iteration(): frames_per_batch = {fpb} is not a multiple of the env's {env.B} envs")
+    if bool(getattr(p, "is_prb", False)) and buffer is None:
+        raise ValueError("train_iteration(): Parameters.is_prb needs a PrioritizedBuffer (buffer=)")
+    T = fpb // env.B
+    steps = steps_per_iteration(p, fpb, update_kw.get("num_epochs"), update_kw.get("minibatch_size"))
+    batch = collect(env, actor, critic, T, params=p, td_gamma=td_gamma, td_error=True, seed=seed, counter0=counter0 + (k - 1) * T, returns=returns, **(rollout_kw or {}))
+    stats = batch["episode_stats"]
+    if buffer is not None:
+        buffer.extend(batch["td_error"])
+    infos = update(env, actor, critic, actor_module, critic_module, optim, batch, params=p, seed=seed, counter0=counter0 + (k - 1) * steps, generator=generator,
+                   buffer=buffer, td_gamma=td_gamma, **update_kw)
+    set_lr(optim, lr_at(p, k + 1))
+    return batch, infos, stats
+
+
+def train(env, actor, critic, actor_module, critic_module, optim, params=None, *, n_iters: int | None = None, on_iteration=None, returns: EpisodeReturns | None = None,
+          buffer: PrioritizedBuffer | None = None, episode_reward_mean_list: list | None = None, **iteration_kw) -> list:
+    """The reference's training loop (``sigmarl/mappo_cavs.py:121-150``): ``train_iteration`` for ``i_iter = 1 .. n_iters`` (``params.n_iters`` unless given; the
+    schedule always runs over ``params.n_iters``) with one ``EpisodeReturns`` carried through (a new one unless given).  After every iteration, as ``_log_and_save``
+    and ``_save_intermediate_model`` (``:468-515``) do: ``mean = EpisodeReturns.mean(stats)`` -- the one host read of the iteration -- is appended to
+    ``episode_reward_mean_list``; ``params.episode_reward_mean_current = mean``; ``improved = mean > params.episode_reward_intermediate`` (compared after the
+    rounding; never true for a NaN); if improved ``params.episode_reward_intermediate = mean``, else ``params.episode_reward_mean_current`` falls back to the best
+    so far, as the reference's does.  Then ``on_iteration(i_iter, batch, infos, mean, improved)`` if given: the place where a caller saves models -- this loop writes
+    no files.  The optimiser starts from whatever ``lr`` it holds (``params.lr`` in the reference).  Returns ``episode_reward_mean_list``."""
+    p = params if params is not None else getattr(env, "parameters", None)
+    if p is None:
+        raise ValueError("train(): a Parameters")
+    n = int(n_iters if n_iters is not None else p.n_iters)
+    returns = returns if returns is not None else EpisodeReturns(env)
+    means = episode_reward_mean_list if episode_reward_mean_list is not None else []
+    for i_iter in range(1, n + 1):
+        batch, infos, stats = train_iteration(env, actor, critic, actor_module, critic_module, optim, returns, p, i_iter=i_iter, buffer=buffer, **iteration_kw)
+        mean = EpisodeReturns.mean(stats)
+        means.append(mean)
+        p.episode_reward_mean_current = mean
+        improved = mean > p.episode_reward_intermediate
+        if improved:
+            p.episode_reward_intermediate = mean
+        else:
+            p.episode_reward_mean_current = p.episode_reward_intermediate
+        if on_iteration is not None:
+            on_iteration(i_iter, batch, infos, mean, improved)
+    return means

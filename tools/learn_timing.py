@@ -4,6 +4,8 @@
            .contiguous() of the observation part + Critic.forward on the same rows
   rollout  the fp32 device rollout with and without the root-observation record (one B N D copy per step)
   gae      the sigmaenv_gae launch (advantage + value target), with the TD priorities, and its bytes moved / time against the HBM figures
+  episode  EpisodeReturns.update (sigmaenv_episode_return: the RewardSum record and its done-frame mean) on the same records, with and without the record, next
+           to gae; and the host restatement it replaces: the rewards and done flags copied to the CPU and the loop over t there (a host clock: the copy waits)
   collect  learn.collect per step, beside the plain rollout per step (tools/wrapper_timing.py's figure on the same box)
 HIP events around each call, after CONDITION_MS (default 200) of the same work so that the device is at its sustained clocks; REPS (default 3)
 repetitions with the compared routes alternating inside one process.  A report, not a pass criterion.  Prints one JSON line."""
@@ -99,6 +101,38 @@ res["gae_bytes"] = gae_bytes
 res["gae_bytes_per_s"] = gae_bytes / g
 res["gae_fraction_of_hbm_spec"] = gae_bytes / g / HBM_SPEC
 res["gae_fraction_of_hbm_copy"] = gae_bytes / g / HBM_COPY
+
+# the episode return on the same records, next to gae (alternating with it), and the host restatement it replaces
+returns = learn.EpisodeReturns(env)
+er = torch.empty((T, B, N), **kw)
+res["ms"]["episode"] = compare({"gae": lambda: learn.gae(env, slab, sv, nv, p.gamma, p.lmbda, advantage=adv, value_target=vt),
+                                "episode_return": lambda: returns.update(slab, T, episode_reward=er),
+                                "episode_return_no_record": lambda: returns.update(slab, T, episode_reward=False)})
+episode_bytes = T * B * (N + 1) * 4 + T * B * N * 4 + 2 * B * N * 4  # rewards + done read (the rows' cache lines hold more), the record written, the carry both ways
+e = min(res["ms"]["episode"]["episode_return"]) * 1e-3
+res["episode_bytes"] = episode_bytes
+res["episode_bytes_per_s"] = episode_bytes / e
+res["episode_fraction_of_hbm_copy"] = episode_bytes / e / HBM_COPY
+res["episodes_done_in_the_records"] = float(returns.update(slab, T, episode_reward=False)[1]["episodes_done"])
+
+
+def host_restatement():
+    """what a user did without the entry point: [T, B, N] rewards and [T, B] done flags to the CPU, the RewardSum loop over t and the done-frame mean there"""
+    t0 = time.perf_counter()
+    r, d = slab[:, :, N * D: N * D + N].cpu(), slab[:, :, N * D + N].cpu() != 0
+    c, E = torch.zeros((B, N)), torch.empty((T, B, N))
+    for t in range(T):
+        E[t] = c + r[t]
+        c = torch.where(d[t][:, None], torch.zeros(()), E[t])
+    mean = float(E[d].mean()) if d.any() else float("nan")
+    return (time.perf_counter() - t0) * 1e3, mean
+
+
+host_restatement()
+host = [host_restatement() for _ in range(REPS)]
+res["ms"]["episode"]["host_restatement_wall"] = [h[0] for h in host]
+returns.reset()  # (the host restatement starts from a zero carry)
+res["episode_mean"] = {"device": float(returns.update(slab, T, episode_reward=False)[1]["episode_reward_mean"]), "host_restatement": host[0][1]}
 
 
 def collect():
