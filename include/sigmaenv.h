@@ -475,6 +475,20 @@ int sigmaenv_mlp32_backward_indexed(sigmaenv_t* h, sigmaenv_mlp32_t* m, const fl
                                     int64_t block_stride, const int32_t* index, int32_t n_index, const float* acts, const float* dout, float* workspace,
                                     float* const* grad_w, float* const* grad_b);
 
+/* The three calls that read input rows, on PADDED rows: the network's input row is in_dim / seg_dst segments of width seg_dst, the row in memory the same number of
+ * segments of width seg_src <= seg_dst; network column a * seg_dst + j is the row's float a * seg_src + j for j < seg_src and 0 for j >= seg_src.  The base critic's
+ * next rows under prioritized action propagation: per agent the obs_dim floats of the record's next observation, then 2 n_nearing zeros (the reference's
+ * ("next", base_observation) is the env's own output with the placeholder columns zero) -- staged without a padded copy in memory.  row_stride >= the width of the
+ * row in memory; otherwise the arguments, the refusals and the orders of the calls without _pad, and bit for bit their results on the rows gathered and padded
+ * dense.  seg_src < 1, seg_dst < seg_src or seg_dst not a divisor of in_dim: SIGMAENV_EINVAL. */
+int sigmaenv_mlp32_forward_rows_pad(sigmaenv_t* h, sigmaenv_mlp32_t* m, const float* in, int32_t rows_per_block, int64_t row_stride, int32_t n_blocks, int64_t block_stride,
+                                    int32_t seg_src, int32_t seg_dst, float* out);
+int sigmaenv_mlp32_forward_save_indexed_pad(sigmaenv_t* h, sigmaenv_mlp32_t* m, const float* in, int32_t rows_per_block, int64_t row_stride, int32_t n_blocks,
+                                            int64_t block_stride, const int32_t* index, int32_t n_index, int32_t seg_src, int32_t seg_dst, float* out, float* acts);
+int sigmaenv_mlp32_backward_indexed_pad(sigmaenv_t* h, sigmaenv_mlp32_t* m, const float* in, int32_t rows_per_block, int64_t row_stride, int32_t n_blocks,
+                                        int64_t block_stride, const int32_t* index, int32_t n_index, int32_t seg_src, int32_t seg_dst, const float* acts,
+                                        const float* dout, float* workspace, float* const* grad_w, float* const* grad_b);
+
 /* n_steps x (sigmaenv_actor_forward; sigmaenv_step_autoreset) enqueued back to back (SyncDataCollectorCustom.rollout,
  * sigmarl/helper_training.py:687-788, without its per-step Python): actions_buf device f32 [B,N,2] scratch; optional records:
  * slab_base device f32 [n_steps, B, N*(D+1)+1], logp_base device f32 [n_steps, B, N], actions_rec device f32 [n_steps, B, N, 2].
@@ -519,7 +533,10 @@ int sigmaenv_rollout_f32(sigmaenv_t* h, sigmaenv_mlp32_t* m, const float* low, c
  *   3. the step on the combined actions.  The collector calls the policy once more on the turn observations (:743): a re-draw from the same distributions;
  *      the turn draws are kept here.
  *   Records (optional): rank_rec i32 [n_steps, B, N]; score_rec / score_logp_rec f32 [n_steps, B, N] (SIGMAENV_PRIORITY_NET); tentative_rec as above = the
- *   neighbour actions each agent saw at its turn.  Communication noise (is_communication_noise, :1240-1254) is not built.
+ *   neighbour actions each agent saw at its turn; base_obs_rec f32 [n_steps, B, N, obs_dim + 2 K] = the compact row every agent was evaluated on in its
+ *   turn (its SIGMAENV_BUF_OBS row, then the 2 K neighbour-action columns: info()["base_observation"], helper_training.py:1305-1312), written by the turn's gather;
+ *   every agent has one turn per step, so every row is written exactly once per step -- unless ranks_given names no agent for it, which leaves the row as it
+ *   was; a rank entry outside [0, N) is never an address.  Communication noise (is_communication_noise, :1240-1254) is not built.
  * A first call per handle allocates a workspace (grown when a later call needs more): do not make that first call inside a stream capture. */
 #define SIGMAENV_WRAP_PLAIN 0
 #define SIGMAENV_WRAP_OPPONENT 1
@@ -537,6 +554,7 @@ typedef struct sigmaenv_rollout_opts {
   float* score_rec;                  /* optional device f32 [n_steps, B, N] */
   float* score_logp_rec;             /* optional device f32 [n_steps, B, N] */
   int32_t reserved[4];               /* zero */
+  float* base_obs_rec;               /* optional device f32 [n_steps, B, N, obs_dim + 2 K] (SIGMAENV_WRAP_PRIORITIZED) */
 } sigmaenv_rollout_opts_t;
 int sigmaenv_rollout_f32_ex(sigmaenv_t* h, sigmaenv_mlp32_t* m, const float* low, const float* high, float* scratch, int32_t n_steps, float* actions_buf,
                             float* slab_base, float* logp_base, float* actions_rec, uint64_t seed, uint64_t counter0, int32_t path_first, int32_t path_count,
@@ -660,6 +678,38 @@ typedef struct sigmaenv_ppo_head_args {
   int32_t reserved[4];             /* zero */
 } sigmaenv_ppo_head_args_t;
 int sigmaenv_ppo_head(sigmaenv_t* h, const sigmaenv_ppo_head_args_t* a);
+
+/* sigmaenv_ppo_head_1d: the same loss for the priority module (sigmarl/modules/priority_module.py:93-126: a second ClipPPOLoss over the priority actor, a 1-D
+ * TanhNormal on [-1, 1], and its own centralised critic).  Everything above holds in one dimension with the trivial bounds; what differs:
+ *   shapes         out, dout_actor [M, N, 2] = (loc, raw scale), 8-byte aligned; the recorded score s = scores[f, n] and score_log_prob [F, N] take the place of
+ *                  action and sample_log_prob; advantage, value_target [F, N] and value [M] are the PRIORITY critic's
+ *   log-prob       torchrl applies no affine map on [-1, 1]: y = clamp(s, +-(1 - 1e-6)) -- not (s + 1) / 1 - 1, which rounds --, x = atanh(y) as above, and
+ *                  logp = -(x - loc)^2 / (2 sigma^2) - log sigma - log sqrt(2 pi) - 2 (log 2 - x - softplus(-2 x)): no - log h term
+ *                  (sigmaenv_priority_head_kernel's expressions, sigmaenv_dist.h)
+ *   entropy draw   z = the cosine branch of a normal pair (cosf, as the priority head draws its score) keyed (seed, counter, env = f, agent = n), draws
+ *                  DRAW_PRIORITY_ENTROPY, + 1: both heads can run on one (seed, counter) without sharing a draw
+ *   outputs        dout_actor[m, n, 0:2] = d(loss_objective + loss_entropy) / d (loc, raw);  dout_critic, result, the workspace, the order of every sum, the
+ *                  treatment of index entries outside [0, F) and the refusals: as above (no bounds to refuse). */
+typedef struct sigmaenv_ppo_head_1d_args {
+  int32_t n_index;                 /* M */
+  int32_t n_frames;                /* F */
+  const int32_t* index;
+  const float* out;
+  const float* value;
+  const float* scores;
+  const float* score_log_prob;
+  const float* advantage;
+  const float* value_target;
+  float* dout_actor;
+  float* dout_critic;
+  float* result;
+  float* workspace;
+  float clip_epsilon, entropy_coeff, critic_coeff;
+  int32_t reserved0;               /* zero */
+  uint64_t seed, counter;
+  int32_t reserved[4];             /* zero */
+} sigmaenv_ppo_head_1d_args_t;
+int sigmaenv_ppo_head_1d(sigmaenv_t* h, const sigmaenv_ppo_head_1d_args_t* a);
 
 /* ---- the optimiser step of a minibatch update (sigmaenv_optim.inc; the arithmetic: sigmaenv_optim.h) ---------------------------------------
  * sigmaenv_optim_step: the last three lines of _train_on_batch (sigmarl/mappo_cavs.py:421-426) -- torch.nn.utils.clip_grad_norm_(loss_module.parameters(),

@@ -303,23 +303,44 @@ class Mlp32:
             raise RuntimeError(f"sigmaenv_mlp32_forward failed with code {rc}: {env.lib.last_error(env.h).decode()}")
         return out
 
+    def _pad(self, pad, what):
+        """``pad = (src, dst)`` checked: the network's input row is ``in_dim / dst`` segments of width ``dst``, the row in memory as many of width ``src <= dst``;
+        returns ``(src, dst, the width of the row in memory)``.  ``None``: ``(0, 0, in_dim)``."""
+        if pad is None:
+            return 0, 0, self.in_dim
+        try:
+            src, dst = (int(v) for v in pad)
+        except (TypeError, ValueError):
+            raise TypeError(f"{what}: pad is (source segment width, destination segment width)") from None
+        if src < 1 or dst < src or self.in_dim % dst:
+            raise ValueError(f"{what}: pad = ({src}, {dst}) needs 1 <= src <= dst and dst a divisor of the input width {self.in_dim}")
+        return src, dst, self.in_dim // dst * src
+
     def forward_rows(self, env: SigmaEnv, base: torch.Tensor, offset: int, rows_per_block: int, row_stride: int, n_blocks: int = 1, block_stride: int = 0,
-                     out: torch.Tensor | None = None) -> torch.Tensor:
+                     out: torch.Tensor | None = None, pad=None) -> torch.Tensor:
         """``sigmaenv_mlp32_forward_rows``: the network on rows that lie inside ``base`` (any contiguous float32 CUDA tensor, read as flat floats) -- row
         ``t * rows_per_block + b`` starts at float ``offset + t * block_stride + b * row_stride`` -- without copying them out; 4-byte alignment suffices.  Returns
-        ``[n_blocks, rows_per_block, out_dim]``, bit for bit what ``forward`` gives the same rows copied dense.  Enqueued on the env's stream."""
+        ``[n_blocks, rows_per_block, out_dim]``, bit for bit what ``forward`` gives the same rows copied dense.  Enqueued on the env's stream.
+        ``pad = (src, dst)`` (``sigmaenv_mlp32_forward_rows_pad``): the rows in memory are ``in_dim / dst`` segments of ``src`` floats, each read as ``dst`` columns
+        of which the last ``dst - src`` are zero -- bit for bit ``forward`` on the rows copied dense and padded, without that copy."""
         if not (base.is_cuda and base.dtype == torch.float32 and base.is_contiguous()):
             raise TypeError("the rows must lie in a contiguous float32 CUDA tensor")
         offset, rpb, rs, nb, bs = int(offset), int(rows_per_block), int(row_stride), int(n_blocks), int(block_stride)
-        if rpb < 0 or nb < 0 or offset < 0 or rs < self.in_dim or bs < 0:
-            raise ValueError(f"forward_rows: counts and offsets must be >= 0 and row_stride >= the input width {self.in_dim}")
-        if rpb and nb and offset + (nb - 1) * bs + (rpb - 1) * rs + self.in_dim > base.numel():
+        src, dst, width = self._pad(pad, "forward_rows")
+        if rpb < 0 or nb < 0 or offset < 0 or rs < width or bs < 0:
+            raise ValueError(f"forward_rows: counts and offsets must be >= 0 and row_stride >= the width of a row in memory, {width}")
+        if rpb and nb and offset + (nb - 1) * bs + (rpb - 1) * rs + width > base.numel():
             raise ValueError("forward_rows: the last row ends beyond the tensor")
         if out is None:
             out = torch.empty((nb, rpb, self.out_dim), dtype=torch.float32, device=base.device)
         elif not (out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.numel() == nb * rpb * self.out_dim):
             raise TypeError(f"out must be a contiguous float32 CUDA tensor of {nb * rpb * self.out_dim} elements")
         if rpb == 0 or nb == 0:
+            return out
+        if pad is not None:
+            rc = env.lib.mlp32_forward_rows_pad(env.h, self.handle(env.lib, env), C.c_void_p(base.data_ptr() + 4 * offset), rpb, rs, nb, bs, src, dst, C.c_void_p(out.data_ptr()))
+            if rc != 0:
+                raise RuntimeError(f"sigmaenv_mlp32_forward_rows_pad failed with code {rc}: {env.lib.last_error(env.h).decode()}")
             return out
         rc = env.lib.mlp32_forward_rows(env.h, self.handle(env.lib, env), C.c_void_p(base.data_ptr() + 4 * offset), rpb, rs, nb, bs, C.c_void_p(out.data_ptr()))
         if rc != 0:
@@ -340,7 +361,9 @@ class Mlp32:
                 raise ValueError(f"apply: index entries in [{lo}, {hi}] are not all inside the record's {n_blocks} blocks")
         return index
 
-    def _rows_spec(self, x, rows, env=None, index=None, check_index=True):
+    def _rows_spec(self, x, rows, env=None, index=None, check_index=True, pad=None):
+        if pad is not None and index is None:
+            raise TypeError("apply: pad (padded rows) is built for rows picked by index")
         if index is not None and rows is None:
             raise TypeError("apply: index picks blocks of rows = (base, offset, rows_per_block, row_stride, n_blocks, block_stride)")
         if (x is None) == (rows is None):
@@ -357,12 +380,15 @@ class Mlp32:
         if base.requires_grad:
             raise NotImplementedError("apply: the gradient with respect to the input is not built (rows base requires_grad)")
         offset, rpb, rs, nb, bs = int(offset), int(rpb), int(rs), int(nb), int(bs)
-        if rpb < 0 or nb < 0 or offset < 0 or rs < self.in_dim or bs < 0:
-            raise ValueError(f"apply: counts and offsets must be >= 0 and row_stride >= the input width {self.in_dim}")
-        if rpb and nb and offset + (nb - 1) * bs + (rpb - 1) * rs + self.in_dim > base.numel():
+        src, dst, width = self._pad(pad, "apply")
+        if rpb < 0 or nb < 0 or offset < 0 or rs < width or bs < 0:
+            raise ValueError(f"apply: counts and offsets must be >= 0 and row_stride >= the width of a row in memory, {width}")
+        if rpb and nb and offset + (nb - 1) * bs + (rpb - 1) * rs + width > base.numel():
             raise ValueError("apply: the last row ends beyond the tensor")
         if index is not None:
             index = self._index(env, index, nb, check_index)
+            if pad is not None:
+                return (base, offset, rpb, rs, nb, bs, index, (src, dst)), (index.numel(), rpb, self.out_dim)
             return (base, offset, rpb, rs, nb, bs, index), (index.numel(), rpb, self.out_dim)
         return (base, offset, rpb, rs, nb, bs, None), (nb, rpb, self.out_dim)
 
@@ -372,7 +398,7 @@ class Mlp32:
 
     def _forward_save(self, env, spec):
         """(y [rows, out_dim], acts [n_layers - 1, rows, 256]) on the env's stream, ordered after and before torch's current stream."""
-        base, offset, rpb, rs, nb, bs, index = spec
+        base, offset, rpb, rs, nb, bs, index, *pad = spec  # (an eighth entry: (src, dst) of padded rows, with an index)
         n, dev = rpb * (nb if index is None else index.numel()), env.device
         cur = torch.cuda.current_stream(dev)
         y = torch.empty((n, self.out_dim), dtype=torch.float32, device=dev)
@@ -383,6 +409,9 @@ class Mlp32:
             src = C.c_void_p(base.data_ptr() + 4 * offset)
             if index is None:
                 self._chk_grad(env, env.lib.mlp32_forward_save(env.h, h, src, rpb, rs, nb, bs, C.c_void_p(y.data_ptr()), C.c_void_p(acts.data_ptr())), "mlp32_forward_save")
+            elif pad:
+                self._chk_grad(env, env.lib.mlp32_forward_save_indexed_pad(env.h, h, src, rpb, rs, nb, bs, C.c_void_p(index.data_ptr()), index.numel(), pad[0][0], pad[0][1],
+                                                                          C.c_void_p(y.data_ptr()), C.c_void_p(acts.data_ptr())), "mlp32_forward_save_indexed_pad")
             else:
                 self._chk_grad(env, env.lib.mlp32_forward_save_indexed(env.h, h, src, rpb, rs, nb, bs, C.c_void_p(index.data_ptr()), index.numel(), C.c_void_p(y.data_ptr()),
                                                                       C.c_void_p(acts.data_ptr())), "mlp32_forward_save_indexed")
@@ -393,7 +422,7 @@ class Mlp32:
 
     def _backward(self, env, spec, acts, dout):
         """(grad_w, grad_b) lists in ``torch.nn.Linear`` layout: ``sigmaenv_mlp32_backward`` on the env's stream, ordered as ``_forward_save``."""
-        base, offset, rpb, rs, nb, bs, index = spec
+        base, offset, rpb, rs, nb, bs, index, *pad = spec
         n, dev = rpb * (nb if index is None else index.numel()), env.device
         dims = [int(d) for d in self._keep[0]]
         cur = torch.cuda.current_stream(dev)
@@ -413,6 +442,9 @@ class Mlp32:
                                                                    PA(*[t.data_ptr() for t in gw]), PA(*[t.data_ptr() for t in gb]))
             if index is None:
                 self._chk_grad(env, env.lib.mlp32_backward(env.h, h, src, rpb, rs, nb, bs, *tail), "mlp32_backward")
+            elif pad:
+                self._chk_grad(env, env.lib.mlp32_backward_indexed_pad(env.h, h, src, rpb, rs, nb, bs, C.c_void_p(index.data_ptr()), index.numel(), pad[0][0], pad[0][1], *tail),
+                               "mlp32_backward_indexed_pad")
             else:
                 self._chk_grad(env, env.lib.mlp32_backward_indexed(env.h, h, src, rpb, rs, nb, bs, C.c_void_p(index.data_ptr()), index.numel(), *tail), "mlp32_backward_indexed")
             cur.wait_stream(env.stream)
@@ -420,14 +452,15 @@ class Mlp32:
             t.record_stream(env.stream)
         return gw, gb
 
-    def apply(self, env: SigmaEnv, x: torch.Tensor | None = None, *, rows=None, index: torch.Tensor | None = None, check_index: bool = True) -> torch.Tensor:
+    def apply(self, env: SigmaEnv, x: torch.Tensor | None = None, *, rows=None, index: torch.Tensor | None = None, check_index: bool = True, pad=None) -> torch.Tensor:
         """The network with a ``grad_fn``: ``y = apply(env, x)`` for dense ``x [..., in_dim]`` (``y [..., out_dim]``) or ``apply(env, rows=(base, offset,
         rows_per_block, row_stride, n_blocks, block_stride))`` for rows read where they lie, as ``forward_rows`` addresses them (``y [n_blocks, rows_per_block,
         out_dim]``) -- a minibatch of whole time slices of a rollout record.  With ``index`` (a contiguous int32 CUDA tensor ``[M]``, with ``rows``): a minibatch of
         BLOCKS, block ``m`` of the result being block ``index[m]`` of the record (``y [M, rows_per_block, out_dim]``; ``sigmaenv_mlp32_forward_save_indexed`` /
         ``sigmaenv_mlp32_backward_indexed``) -- shuffled frames, duplicates allowed --, bit for bit what the same rows gathered dense give.  An entry outside
         ``[0, n_blocks)`` raises ``ValueError`` before any launch (``index.min()`` / ``max()``: one host wait; ``check_index=False`` skips it, and the kernels then
-        read such a block as zeros).  A ``torch.autograd.Function`` whose inputs are the parameters of the module the
+        read such a block as zeros).  ``pad = (src, dst)`` (with ``index``; ``forward_rows``'s): the rows in memory are segments of ``src`` floats read as ``dst``
+        columns, the rest zero -- values and gradients bit for bit those of the rows gathered and padded dense.  A ``torch.autograd.Function`` whose inputs are the parameters of the module the
         network was built or last ``load``ed from (float32 CUDA tensors on the env's device): ``loss.backward()`` fills their ``.grad``, so ``clip_grad_norm_`` and
         ``torch.optim.Adam`` work unchanged.  The forward is the EXACT fp32 chain whatever mode the network runs in (``sigmaenv_mlp32_forward_save``); the gradient
         with respect to the input is not built (``x.requires_grad``: ``NotImplementedError``).
@@ -437,7 +470,7 @@ class Mlp32:
 
         Streams: the kernels run on the env's stream after everything torch's current stream holds, and torch's current stream then waits for them -- forwards
         and backwards alike (``load``'s discipline)."""
-        spec, shape = self._rows_spec(x, rows, env, index, check_index)
+        spec, shape = self._rows_spec(x, rows, env, index, check_index, pad)
         for t in self._params:
             if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.device == env.device):
                 raise TypeError(f"apply: the network's parameters must be float32 CUDA tensors on {env.device}: load(env, module) with the module on the device first")
@@ -466,14 +499,26 @@ class Critic(Mlp32):
         v = self.forward(env, o.reshape(env.B, env.N * env.D))
         return v.reshape(env.B, 1, 1).expand(env.B, env.N, 1)
 
+    def _padded(self, env, pad, what):
+        """``pad = (D, Dc)`` of a critic on base observations (prioritized action propagation: ``N (D + 2 K)`` inputs) checked; returns ``Dc``, the agent's width"""
+        if pad is None:
+            return env.D
+        src, dst, _ = self._pad(pad, what)
+        if src != env.D or self.in_dim != env.N * dst:
+            raise ValueError(f"{what}: pad = ({src}, {dst}) is not (obs_dim = {env.D}, the critic's input width / n_agents = {self.in_dim // env.N})")
+        return dst
+
     def rollout_values(self, env: SigmaEnv, slab: torch.Tensor, obs_rec: torch.Tensor, T: int, env_first: int = 0, state_value: torch.Tensor | None = None,
-                       next_state_value: torch.Tensor | None = None):
+                       next_state_value: torch.Tensor | None = None, pad=None):
         """The critic's two passes of GAE over the records of a ``T``-step rollout, read where they lie (``forward_rows``: no slice, no staging copy):
         ``state_value [T, B]`` from the root observations ``obs_rec [T, Bt, N, D]`` and ``next_state_value [T, B]`` from the observation part of the record rows
         ``slab [T, Bt, W]``.  ``Bt >= env.B``: the buffers of the whole batch, of which ``env`` owns the envs ``[env_first, env_first + env.B)`` (an env shard;
-        ``Bt = env.B`` and 0 for a single handle).  Both sides are computed (as torchrl's GAE runs its value network on both); nothing is reused across steps."""
-        T, B, N, D = int(T), env.B, env.N, env.D
-        W, e0 = N * (D + 1) + 1, int(env_first)
+        ``Bt = env.B`` and 0 for a single handle).  Both sides are computed (as torchrl's GAE runs its value network on both); nothing is reused across steps.
+        ``pad = (D, Dc)``: the base critic under prioritized action propagation, centralised on ``N Dc`` inputs -- ``obs_rec`` is then the base-observation record
+        ``[T, Bt, N, Dc]`` (``Actor.rollout(base_obs=)``), and the next rows are the record's next observations with every agent's ``Dc - D`` placeholder columns
+        zero (the reference's ``("next", base_observation)`` is the env's own output, not the policy-modified row), staged padded without a padded copy."""
+        T, B, N, D = int(T), env.B, env.N, self._padded(env, pad, "rollout_values")
+        W, e0 = N * (env.D + 1) + 1, int(env_first)
         if self.in_dim != N * D or self.out_dim != 1:
             raise ValueError(f"the critic maps n_agents * obs_dim = {N * D} inputs to 1 value, not {self.in_dim} to {self.out_dim}")
         if T < 1 or slab.dim() != 3 or slab.shape[0] < T or slab.shape[2] != W:
@@ -484,32 +529,38 @@ class Critic(Mlp32):
         if obs_rec.dim() < 2 or obs_rec.shape[0] < T or obs_rec.shape[1] != Bt or obs_rec[0, 0].numel() != N * D:
             raise TypeError(f"obs_rec must be [>= {T}, {Bt}, {N}, {D}]")
         sv = self.forward_rows(env, obs_rec, e0 * N * D, B, N * D, T, Bt * N * D, out=state_value)
-        nv = self.forward_rows(env, slab, e0 * W, B, W, T, Bt * W, out=next_state_value)
+        nv = self.forward_rows(env, slab, e0 * W, B, W, T, Bt * W, out=next_state_value, pad=pad)
         return sv.view(T, B), nv.view(T, B)
 
 
     def apply(self, env: SigmaEnv, record: torch.Tensor, T: int | None = None, env_first: int = 0, t_first: int = 0, index: torch.Tensor | None = None,  # noqa: D102
-              check_index: bool = True) -> torch.Tensor:
+              check_index: bool = True, pad=None) -> torch.Tensor:
         """``[T, B]`` state values with a ``grad_fn`` (``Mlp32.apply``) of the time slices ``[t_first, t_first + T)`` of a rollout record, read where they lie as
         ``rollout_values`` reads them: ``record`` is the root-observation record ``obs_rec [>= t_first + T, Bt, N, D]`` or the record rows ``slab [.., Bt, W]``
         (their observation part: the next observations); ``env`` owns the envs ``[env_first, env_first + env.B)`` of the buffer.  With ``index`` (int32 CUDA ``[M]``,
         ``Mlp32.apply``): the ``T * B`` frames ``f = t * B + b`` of those slices are blocks of one row each and the result is ``[M]``, the values of the frames
-        ``index[m]`` (the record must be the env's own: ``Bt == env.B``)."""
-        B, N, D = env.B, env.N, env.D
+        ``index[m]`` (the record must be the env's own: ``Bt == env.B``).  ``pad = (D, Dc)`` (``rollout_values``'s): the critic on base observations -- ``record``
+        is the base-observation record ``[.., Bt, N, Dc]``, read as it lies, or ``slab``, whose next observations are read padded (with ``index``)."""
+        B, N, D = env.B, env.N, self._padded(env, pad, "apply")
+        W = N * (env.D + 1) + 1
         if self.in_dim != N * D or self.out_dim != 1:
             raise ValueError(f"the critic maps n_agents * obs_dim = {N * D} inputs to 1 value, not {self.in_dim} to {self.out_dim}")
         if not isinstance(record, torch.Tensor) or record.dim() < 3:
             raise TypeError("record must be obs_rec [T, Bt, N, D] or slab [T, Bt, W]")
         Bt, width = record.shape[1], record[0, 0].numel()
-        if width not in (N * D, N * (D + 1) + 1):
-            raise TypeError(f"record rows of {width} floats: neither [N, D] observations nor record rows of {N * (D + 1) + 1}")
+        if width not in (N * D, W):
+            raise TypeError(f"record rows of {width} floats: neither [N, {D}] observations nor record rows of {W}")
+        if width != W or record.dim() != 3:
+            pad = None  # (the base-observation record holds the padded rows themselves)
         T, e0, t0 = int(record.shape[0] - t_first if T is None else T), int(env_first), int(t_first)
         if T < 0 or t0 < 0 or t0 + T > record.shape[0] or not 0 <= e0 <= Bt - B:
             raise ValueError(f"time slices [{t0}, {t0 + T}) / envs [{e0}, {e0 + B}) are not inside the record {list(record.shape)}")
         if index is not None:
             if Bt != B:
                 raise ValueError(f"apply: frames are indexed in the env's own record (Bt == B = {B}), not in a buffer of {Bt} envs")
-            return super().apply(env, rows=(record, t0 * Bt * width, 1, width, T * B, width), index=index, check_index=check_index).view(-1)
+            return super().apply(env, rows=(record, t0 * Bt * width, 1, width, T * B, width), index=index, check_index=check_index, pad=pad).view(-1)
+        if pad is not None:
+            raise TypeError("apply: the padded next rows of slab are built for frames picked by index")
         return super().apply(env, rows=(record, (t0 * Bt + e0) * width, B, width, T, Bt * width)).view(T, B)
 
 
@@ -682,7 +733,7 @@ class Actor:
                 actions: torch.Tensor | None = None, seed: int = 0, counter0: int = 0, path_first: int | None = None, path_count: int | None = None,
                 deterministic: bool = False, precision: str | None = None, slab_ptr: int | None = None, wrapper: str | None = None,
                 priority=None, tentative: torch.Tensor | None = None, ranks: torch.Tensor | None = None, scores: torch.Tensor | None = None,
-                score_log_prob: torch.Tensor | None = None, obs_rec: torch.Tensor | None = None):
+                score_log_prob: torch.Tensor | None = None, obs_rec: torch.Tensor | None = None, base_obs: torch.Tensor | None = None):
         """``n_steps`` x (policy -> fused step + record + resets) enqueued back to back; optional records ``slab [T,B,W]``,
         ``log_prob [T,B,N]``, ``actions [T,B,N,2]`` (CUDA float32, contiguous).  ``slab_ptr``: the record target as a raw device address instead of ``slab`` (an env
         shard's first row inside a ``[T, B_total, W]`` buffer of the whole batch, with ``env.set_rollout_slab_stride(B_total * W)``).  ``precision`` (default: the actor's): "fp32" = the reference's
@@ -692,7 +743,9 @@ class Actor:
         ``"plain"`` = the same through ``sigmaenv_rollout_f32_ex``; ``"opponent"`` = opponent modelling (the env needs ``is_using_opponent_modeling``);
         ``"prioritized"`` = prioritized action propagation (the actor takes obs_dim + 2 n_nearing inputs) with ``priority`` = a ``PriorityNet``, ``"random"``
         or a rank tensor [B,N] int32 (CUDA).  Records: ``tentative [T,B,N,K,2]`` (the neighbour actions the policy saw), ``ranks [T,B,N]`` int32,
-        ``scores`` / ``score_log_prob [T,B,N]`` (``PriorityNet`` only).  Step semantics: include/sigmaenv.h, sigmaenv_rollout_f32_ex.
+        ``scores`` / ``score_log_prob [T,B,N]`` (``PriorityNet`` only), ``base_obs [T,B,N,D + 2 K]`` (``"prioritized"`` only): the row every agent was evaluated on in
+        its turn -- its ``env.obs`` row, then the 2 K neighbour-action columns it saw (the reference's ``base_observation``) --, written by the turn's gather, every
+        row once per step.  Step semantics: include/sigmaenv.h, sigmaenv_rollout_f32_ex.
 
         ``obs_rec [T,B,N,D]`` (any precision, any wrapper): the root observations -- row t = ``env.obs`` as the final actor forward of step t read it, i.e. the
         ``observation`` of the collector's tensordict (the record row of step t - 1 holds it only where nothing was re-placed).  ``None``: the handle's setting is
@@ -703,7 +756,7 @@ class Actor:
             env.set_rollout_obs_record(obs_rec)
             try:
                 return self.rollout(env, n_steps, slab, log_prob, actions, seed, counter0, path_first, path_count, deterministic, precision, slab_ptr, wrapper, priority,
-                                    tentative, ranks, scores, score_log_prob)
+                                    tentative, ranks, scores, score_log_prob, base_obs=base_obs)
             finally:
                 env.set_rollout_obs_record(None)  # (the copies are enqueued: the setting is only read while the loop enqueues)
         if path_first is None:
@@ -714,7 +767,7 @@ class Actor:
         if wrapper is not None:
             if (precision or self.precision) != "fp32":
                 raise ValueError("the rollout wrappers run the fp32 actor (precision='fp32')")
-            opts = self._wrapper_opts(env, int(n_steps), wrapper, priority, tentative, ranks, scores, score_log_prob)
+            opts = self._wrapper_opts(env, int(n_steps), wrapper, priority, tentative, ranks, scores, score_log_prob, base_obs)
             lo, hi = self._keep[-2], self._keep[-1]
             rc = env.lib.rollout_f32_ex(env.h, self._mlp32.handle(env.lib, env), lo.ctypes.data_as(C.c_void_p), hi.ctypes.data_as(C.c_void_p), p(self._scratch_out4(env)),
                                          int(n_steps), p(scratch), p_slab, p(log_prob), p(actions), int(seed), int(counter0), int(path_first), int(path_count),
@@ -722,6 +775,8 @@ class Actor:
             if rc != 0:
                 raise RuntimeError(f"sigmaenv_rollout_f32_ex failed with code {rc}: {env.lib.last_error(env.h).decode()}")
             return
+        if base_obs is not None:
+            raise ValueError("base_obs belongs to wrapper='prioritized'")
         if (precision or self.precision) == "fp32":
             lo, hi = self._keep[-2], self._keep[-1]
             rc = env.lib.rollout_f32(env.h, self._mlp32.handle(env.lib, env), lo.ctypes.data_as(C.c_void_p), hi.ctypes.data_as(C.c_void_p), p(self._scratch_out4(env)), int(n_steps),
@@ -735,7 +790,7 @@ class Actor:
         if rc != 0:
             raise RuntimeError(f"sigmaenv_rollout failed with code {rc}: {env.lib.last_error(env.h).decode()}")
 
-    def _wrapper_opts(self, env: SigmaEnv, T: int, wrapper: str, priority, tentative, ranks, scores, score_log_prob) -> capi.RolloutOpts:
+    def _wrapper_opts(self, env: SigmaEnv, T: int, wrapper: str, priority, tentative, ranks, scores, score_log_prob, base_obs=None) -> capi.RolloutOpts:
         opts = capi.RolloutOpts()
         opts.wrapper = {"plain": capi.WRAP_PLAIN, "opponent": capi.WRAP_OPPONENT, "prioritized": capi.WRAP_PRIORITIZED}[wrapper]
 
@@ -748,9 +803,12 @@ class Actor:
 
         opts.tentative_rec = rec(tentative, (T, env.B, env.N, env.K, 2), torch.float32, "tentative")
         if wrapper != "prioritized":
-            if priority is not None or ranks is not None or scores is not None or score_log_prob is not None:
-                raise ValueError("priority / ranks / scores / score_log_prob belong to wrapper='prioritized'")
+            if priority is not None or ranks is not None or scores is not None or score_log_prob is not None or base_obs is not None:
+                raise ValueError("priority / ranks / scores / score_log_prob / base_obs belong to wrapper='prioritized'")
             return opts
+        if base_obs is not None and not hasattr(env.lib, "ppo_head_1d"):  # (SIGMAENV_LIB_OLD_ABI: a build from before the record reads a shorter struct)
+            raise RuntimeError("base_obs: this build of the library does not write the base-observation record")
+        opts.base_obs_rec = rec(base_obs, (T, env.B, env.N, env.D + 2 * env.K), torch.float32, "base_obs")
         opts.rank_rec = rec(ranks, (T, env.B, env.N), torch.int32, "ranks")
         if isinstance(priority, PriorityNet):
             opts.priority_source = capi.PRIORITY_NET

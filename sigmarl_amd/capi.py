@@ -90,7 +90,7 @@ class RolloutOpts(C.Structure):
     _fields_ = [
         ("wrapper", C.c_int32), ("priority_source", C.c_int32), ("priority_net", C.c_void_p), ("ranks_given", C.c_void_p),
         ("tentative_rec", C.c_void_p), ("rank_rec", C.c_void_p), ("score_rec", C.c_void_p), ("score_logp_rec", C.c_void_p),
-        ("reserved", C.c_int32 * 4),
+        ("reserved", C.c_int32 * 4), ("base_obs_rec", C.c_void_p),
     ]
 
 
@@ -124,6 +124,18 @@ class PpoHeadArgs(C.Structure):
         ("n_index", C.c_int32), ("n_frames", C.c_int32), ("index", C.c_void_p), ("out", C.c_void_p), ("value", C.c_void_p), ("action", C.c_void_p),
         ("sample_log_prob", C.c_void_p), ("advantage", C.c_void_p), ("value_target", C.c_void_p), ("dout_actor", C.c_void_p), ("dout_critic", C.c_void_p),
         ("result", C.c_void_p), ("workspace", C.c_void_p), ("low", C.c_float * 2), ("high", C.c_float * 2),
+        ("clip_epsilon", C.c_float), ("entropy_coeff", C.c_float), ("critic_coeff", C.c_float), ("reserved0", C.c_int32),
+        ("seed", C.c_uint64), ("counter", C.c_uint64), ("reserved", C.c_int32 * 4),
+    ]
+
+
+class PpoHead1dArgs(C.Structure):
+    """``sigmaenv_ppo_head_1d_args_t`` (sigmaenv_ppo_head_1d): the priority module's minibatch -- ``out [M, N, 2]``, the recorded scores and their log-probabilities."""
+
+    _fields_ = [
+        ("n_index", C.c_int32), ("n_frames", C.c_int32), ("index", C.c_void_p), ("out", C.c_void_p), ("value", C.c_void_p), ("scores", C.c_void_p),
+        ("score_log_prob", C.c_void_p), ("advantage", C.c_void_p), ("value_target", C.c_void_p), ("dout_actor", C.c_void_p), ("dout_critic", C.c_void_p),
+        ("result", C.c_void_p), ("workspace", C.c_void_p),
         ("clip_epsilon", C.c_float), ("entropy_coeff", C.c_float), ("critic_coeff", C.c_float), ("reserved0", C.c_int32),
         ("seed", C.c_uint64), ("counter", C.c_uint64), ("reserved", C.c_int32 * 4),
     ]
@@ -166,6 +178,7 @@ def prb_level_sizes(capacity: int) -> list:
 
 
 PPO_SUMS = 5  # SIGMAENV_PPO_SUMS: partial sums per workgroup of 256 rows in sigmaenv_ppo_head's workspace
+PRIORITY_ENTROPY_DRAW = 7350  # DRAW_PRIORITY_ENTROPY of the draw table (sigmaenv_dist.h): sigmaenv_ppo_head_1d's entropy sample
 PPO_RESULT = ("loss_objective", "loss_entropy", "loss_critic", "entropy", "clip_fraction", "kl_approx")  # result[0 .. 5]
 
 
@@ -290,7 +303,13 @@ _PRODUCT_ONLY = {
     "mlp32_forward_save_indexed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
     "mlp32_backward_indexed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
                                          C.c_void_p, C.c_void_p]),
+    "mlp32_forward_rows_pad": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_void_p]),
+    "mlp32_forward_save_indexed_pad": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_int64, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
+                                                 C.c_void_p, C.c_void_p]),
+    "mlp32_backward_indexed_pad": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_int64, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
+                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "ppo_head": (C.c_int, [C.c_void_p, C.POINTER(PpoHeadArgs)]),
+    "ppo_head_1d": (C.c_int, [C.c_void_p, C.POINTER(PpoHead1dArgs)]),
     "optim_workspace": (C.c_int, [C.c_void_p, C.POINTER(OptimArgs), C.POINTER(C.c_uint64)]),
     "optim_step": (C.c_int, [C.c_void_p, C.POINTER(OptimArgs)]),
     "mlp32_resolve_mode": (C.c_int, [C.c_void_p, C.c_void_p]),

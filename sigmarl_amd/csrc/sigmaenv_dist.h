@@ -43,12 +43,13 @@ SIGMA_HD uint32_t rng_u32(uint64_t seed, uint64_t counter, uint32_t env, uint32_
 #define DRAW_PRIORITY 7100u      /* u1, + 1: u2 of the priority score's normal (cosine branch)                   priority_head       (env, agent) */
 #define DRAW_SHUFFLE 7200u       /* the random priority order: position i draws j in [0, i]                      priority_random     (env, agent = i) */
 #define DRAW_ENTROPY 7300u       /* u1, + 1: u2 of the PPO entropy sample                                        ppo_head            (env = frame, agent) */
+#define DRAW_PRIORITY_ENTROPY 7350u /* u1, + 1: u2 of the priority PPO entropy sample (cosine branch)           ppo_head_1d         (env = frame, agent) */
 #define DRAW_REPLAY 7400u        /* the replay sampler's uniform                                                 prb sample          (env = slot m, 0) */
 #define DRAW_OBS_NOISE 9000u     /* + k: element k of an observation row; open-ended, so the highest             obs_noise           (env, agent) */
 static_assert(DRAW_RESET_TRY + 2u * AUTO_RESET_MAX_TRIES <= DRAW_RESET_SPEED && DRAW_RESET_SPEED < DRAW_AGENT_TRY, "full-env reset tries run into the next stream");
 static_assert(DRAW_AGENT_TRY + 2u * AUTO_RESET_MAX_TRIES <= DRAW_AGENT_SPEED && DRAW_AGENT_SPEED < DRAW_SCENARIO, "single-agent reset tries run into the next stream");
 static_assert(DRAW_SCENARIO < DRAW_ACTOR && DRAW_ACTOR + 1u < DRAW_PRIORITY && DRAW_PRIORITY + 1u < DRAW_SHUFFLE && DRAW_SHUFFLE < DRAW_ENTROPY &&
-              DRAW_ENTROPY + 1u < DRAW_REPLAY && DRAW_REPLAY < DRAW_OBS_NOISE, "the streams overlap, or the open-ended noise range is not the highest");
+              DRAW_ENTROPY + 1u < DRAW_PRIORITY_ENTROPY && DRAW_PRIORITY_ENTROPY + 1u < DRAW_REPLAY && DRAW_REPLAY < DRAW_OBS_NOISE, "the streams overlap, or the open-ended noise range is not the highest");
 
 // ---- a word -> a number ------------------------------------------------------------------------------------------------------------------------------------------------
 // U[0, 1): (k >> 8) * 2^-24, exact in fp32; never 1

@@ -129,8 +129,10 @@ struct DwLayer {
 // INDEXED (INPUT only; sigmaenv_mlp32_backward_indexed): a third instantiation whose input rows are blocks picked by `ix` (Mlp32Index, sigmaenv_mlp32.inc).  A lane loads
 // the index entry of each of its rows once (the 32 lanes of a half-wavefront read the same word) and both of its columns from that row; a row whose entry is outside the
 // record contributes zeros to dW_0, as a row past the range does.  g, the partition and the order of the chains are those of the other two.
-template <bool INPUT, bool INDEXED = false>
-__global__ void __launch_bounds__(256) sigmaenv_mlp32_dw_kernel(DwLayer p, Mlp32Rows rw, Mlp32Index ix) {
+// PAD (with INDEXED; sigmaenv_mlp32_backward_indexed_pad): a fourth instantiation whose input rows are padded (Mlp32Pad, sigmaenv_mlp32.inc): a lane's two columns map
+// to their segments' source floats, or are zero in the padding -- dW_0's columns of the padding are exact zeros, as the dense call on the padded copy gives them.
+template <bool INPUT, bool INDEXED = false, bool PAD = false>
+__global__ void __launch_bounds__(256) sigmaenv_mlp32_dw_kernel(DwLayer p, Mlp32Rows rw, Mlp32Index ix, Mlp32Pad pd) {
   sigma_poison_lds();
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, m = lane & 31, h = lane >> 5;
   const int nkb = (p.K + GRAD_BLK - 1) / GRAD_BLK;
@@ -160,13 +162,19 @@ __global__ void __launch_bounds__(256) sigmaenv_mlp32_dw_kernel(DwLayer p, Mlp32
       if constexpr (INDEXED) {
         const long long off = ok ? mlp32_indexed_row_offset((int)row, rw, ix) : -1ll;
         a_ok = off >= 0;
-        ap = p.a + (a_ok ? off : 0ll) + k0 + m;
+        if constexpr (PAD) ap = p.a + (a_ok ? off : 0ll);  // (the row: mlp32_pad_load maps the columns)
+        else ap = p.a + (a_ok ? off : 0ll) + k0 + m;
       } else if constexpr (INPUT) ap = mlp32_row_ptr<true>(p.a, ok ? (int)row : 0, 0, rw) + k0 + m;
       else ap = p.a + (size_t)row * MLP32_H + k0 + m;
       gv[0][u] = ok && lf0 ? gp[0] : 0.0f;
       gv[1][u] = ok && lf1 ? gp[32] : 0.0f;
-      av[0][u] = a_ok && lk0 ? ap[0] : 0.0f;
-      av[1][u] = a_ok && lk1 ? ap[32] : 0.0f;
+      if constexpr (PAD) {
+        av[0][u] = a_ok && lk0 ? mlp32_pad_load(ap, k0 + m, pd) : 0.0f;
+        av[1][u] = a_ok && lk1 ? mlp32_pad_load(ap, k0 + 32 + m, pd) : 0.0f;
+      } else {
+        av[0][u] = a_ok && lk0 ? ap[0] : 0.0f;
+        av[1][u] = a_ok && lk1 ? ap[32] : 0.0f;
+      }
     }
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
@@ -234,18 +242,20 @@ static int mlp32_grad_load(sigmaenv_t* h, sigmaenv_mlp32* m, const float* const*
 }
 
 static int mlp32_grad_rows(sigmaenv_t* h, const sigmaenv_mlp32* m, const char* what, const float* in, int32_t rows_per_block, int64_t row_stride, int32_t n_blocks,
-                           int64_t block_stride, Mlp32Rows* rw, int64_t* rows) {
+                           int64_t block_stride, Mlp32Rows* rw, int64_t* rows, const Mlp32Pad* pad = nullptr) {
   if (rows_per_block < 0 || n_blocks < 0 || (int64_t)rows_per_block * n_blocks > INT32_MAX) { h->err = std::string(what) + ": negative counts or more than 2^31 - 1 rows"; return SIGMAENV_EINVAL; }
   *rows = (int64_t)rows_per_block * n_blocks;
+  if (pad && (pad->src < 1 || pad->dst < pad->src || m->in_dim % pad->dst)) { h->err = std::string(what) + ": 1 <= seg_src <= seg_dst, and seg_dst divides the network's input width"; return SIGMAENV_EINVAL; }
   if (*rows == 0) return SIGMAENV_OK;
-  if (!in || ((uintptr_t)in & 3) || row_stride < m->in_dim || (n_blocks > 1 && block_stride < 0)) {
+  const int64_t width = pad ? (int64_t)(m->in_dim / pad->dst) * pad->src : m->in_dim;  // the row in memory
+  if (!in || ((uintptr_t)in & 3) || row_stride < width || (n_blocks > 1 && block_stride < 0)) {
     h->err = std::string(what) + ": a null input or one that is not 4-byte aligned, row_stride below the network's input width or a negative block_stride";
     return SIGMAENV_EINVAL;
   }
   rw->rpb = rows_per_block;
   rw->row_stride = row_stride;
   rw->block_stride = block_stride;
-  rw->aligned = ((uintptr_t)in & 15) == 0 && (row_stride & 3) == 0 && (block_stride & 3) == 0;
+  rw->aligned = !pad && ((uintptr_t)in & 15) == 0 && (row_stride & 3) == 0 && (block_stride & 3) == 0;
   return SIGMAENV_OK;
 }
 
@@ -260,27 +270,38 @@ static int mlp32_grad_index(sigmaenv_t* h, const char* what, int32_t n_blocks, i
 
 // index == nullptr: the rows' blocks are the record's blocks 0 .. n_blocks - 1 (sigmaenv_mlp32_forward_save); else the n_index blocks index[.] of its n_blocks
 static int mlp32_forward_save_impl(sigmaenv_t* h, sigmaenv_mlp32* m, const char* what, const float* in, int32_t rows_per_block, int64_t row_stride, int32_t n_blocks,
-                                   int64_t block_stride, const int32_t* index, int32_t n_index, float* out, float* acts) {
+                                   int64_t block_stride, const int32_t* index, int32_t n_index, float* out, float* acts, const Mlp32Pad* pad = nullptr) {
   if (!h) return SIGMAENV_EINVAL;
   if (!m) { h->err = std::string(what) + ": null network handle"; return SIGMAENV_EINVAL; }
+  if (pad && !index) { h->err = std::string(what) + ": padded rows are built for the indexed forward"; return SIGMAENV_EINVAL; }
   Mlp32Rows rw{};
   Mlp32Index ix{};
   int64_t rows = 0;
   if (index || n_index)
     if (const int rc = mlp32_grad_index(h, what, n_blocks, block_stride, index, n_index, &ix)) return rc;
-  if (const int rc = mlp32_grad_rows(h, m, what, in, rows_per_block, row_stride, ix.index ? n_index : n_blocks, block_stride, &rw, &rows)) return rc;
+  if (const int rc = mlp32_grad_rows(h, m, what, in, rows_per_block, row_stride, ix.index ? n_index : n_blocks, block_stride, &rw, &rows, pad)) return rc;
   if (rows == 0) return SIGMAENV_OK;
   if (!out || !acts || ((uintptr_t)out & 3) || ((uintptr_t)acts & 15)) { h->err = std::string(what) + ": null out / acts, or acts not 16-byte aligned"; return SIGMAENV_EINVAL; }
   HIPCHK(h, hipSetDevice(h->device));
-  const void* kfn = ix.index ? reinterpret_cast<const void*>(sigmaenv_mlp32_kernel<true, true, true>) : reinterpret_cast<const void*>(sigmaenv_mlp32_kernel<true, true>);
+  const void* kfn = pad ? reinterpret_cast<const void*>(sigmaenv_mlp32_kernel<true, true, true, true>)
+                        : ix.index ? reinterpret_cast<const void*>(sigmaenv_mlp32_kernel<true, true, true>) : reinterpret_cast<const void*>(sigmaenv_mlp32_kernel<true, true>);
   HIPCHK(h, hipFuncSetAttribute(kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)m->smem));
   const dim3 grid((unsigned)((rows + MLP32_ROWS - 1) / MLP32_ROWS));
+  if (pad) {
 #ifdef SIGMAENV_PROFILE
-  if (ix.index) hipLaunchKernelGGL((sigmaenv_mlp32_kernel<true, true, true>), grid, dim3(256), m->smem, h->stream, m->w, in, (int)rows, m->in_dim, out, rw, acts, ix, (unsigned long long*)nullptr, 0);
-  else hipLaunchKernelGGL((sigmaenv_mlp32_kernel<true, true>), grid, dim3(256), m->smem, h->stream, m->w, in, (int)rows, m->in_dim, out, rw, acts, ix, (unsigned long long*)nullptr, 0);
+    hipLaunchKernelGGL((sigmaenv_mlp32_kernel<true, true, true, true>), grid, dim3(256), m->smem, h->stream, m->w, in, (int)rows, m->in_dim, out, rw, acts, ix, *pad, (unsigned long long*)nullptr, 0);
 #else
-  if (ix.index) hipLaunchKernelGGL((sigmaenv_mlp32_kernel<true, true, true>), grid, dim3(256), m->smem, h->stream, m->w, in, (int)rows, m->in_dim, out, rw, acts, ix);
-  else hipLaunchKernelGGL((sigmaenv_mlp32_kernel<true, true>), grid, dim3(256), m->smem, h->stream, m->w, in, (int)rows, m->in_dim, out, rw, acts, ix);
+    hipLaunchKernelGGL((sigmaenv_mlp32_kernel<true, true, true, true>), grid, dim3(256), m->smem, h->stream, m->w, in, (int)rows, m->in_dim, out, rw, acts, ix, *pad);
+#endif
+    HIPCHK(h, hipGetLastError());
+    return SIGMAENV_OK;
+  }
+#ifdef SIGMAENV_PROFILE
+  if (ix.index) hipLaunchKernelGGL((sigmaenv_mlp32_kernel<true, true, true>), grid, dim3(256), m->smem, h->stream, m->w, in, (int)rows, m->in_dim, out, rw, acts, ix, Mlp32Pad{}, (unsigned long long*)nullptr, 0);
+  else hipLaunchKernelGGL((sigmaenv_mlp32_kernel<true, true>), grid, dim3(256), m->smem, h->stream, m->w, in, (int)rows, m->in_dim, out, rw, acts, ix, Mlp32Pad{}, (unsigned long long*)nullptr, 0);
+#else
+  if (ix.index) hipLaunchKernelGGL((sigmaenv_mlp32_kernel<true, true, true>), grid, dim3(256), m->smem, h->stream, m->w, in, (int)rows, m->in_dim, out, rw, acts, ix, Mlp32Pad{});
+  else hipLaunchKernelGGL((sigmaenv_mlp32_kernel<true, true>), grid, dim3(256), m->smem, h->stream, m->w, in, (int)rows, m->in_dim, out, rw, acts, ix, Mlp32Pad{});
 #endif
   HIPCHK(h, hipGetLastError());
   return SIGMAENV_OK;
@@ -295,6 +316,13 @@ extern "C" int sigmaenv_mlp32_forward_save_indexed(sigmaenv_t* h, sigmaenv_mlp32
   if (h && !index && n_index == 0) return SIGMAENV_OK;  // (an empty minibatch: no row)
   return mlp32_forward_save_impl(h, m, "mlp32_forward_save_indexed", in, rows_per_block, row_stride, n_blocks, block_stride, index, n_index, out, acts);
 }
+// the same on padded rows (Mlp32Pad, sigmaenv_mlp32.inc): the row in memory holds in_dim / seg_dst segments of seg_src floats
+extern "C" int sigmaenv_mlp32_forward_save_indexed_pad(sigmaenv_t* h, sigmaenv_mlp32* m, const float* in, int32_t rows_per_block, int64_t row_stride, int32_t n_blocks,
+                                                       int64_t block_stride, const int32_t* index, int32_t n_index, int32_t seg_src, int32_t seg_dst, float* out, float* acts) {
+  if (h && !index && n_index == 0) return SIGMAENV_OK;
+  const Mlp32Pad pd{seg_src, seg_dst};
+  return mlp32_forward_save_impl(h, m, "mlp32_forward_save_indexed_pad", in, rows_per_block, row_stride, n_blocks, block_stride, index, n_index, out, acts, &pd);
+}
 
 extern "C" int sigmaenv_mlp32_backward_workspace(const sigmaenv_mlp32* m, int64_t rows, uint64_t* n_floats) {
   if (!m || !n_floats || rows < 0 || rows > INT32_MAX) return SIGMAENV_EINVAL;
@@ -304,10 +332,11 @@ extern "C" int sigmaenv_mlp32_backward_workspace(const sigmaenv_mlp32* m, int64_
 
 static int mlp32_backward_impl(sigmaenv_t* h, sigmaenv_mlp32* m, const char* what_c, const float* in, int32_t rows_per_block, int64_t row_stride, int32_t n_blocks,
                                int64_t block_stride, const int32_t* index, int32_t n_index, const float* acts, const float* dout, float* workspace, float* const* grad_w,
-                               float* const* grad_b) {
+                               float* const* grad_b, const Mlp32Pad* pad = nullptr) {
   if (!h) return SIGMAENV_EINVAL;
   const std::string what(what_c);
   if (!m) { h->err = what + ": null network handle"; return SIGMAENV_EINVAL; }
+  if (pad && !index) { h->err = what + ": padded rows are built for the indexed backward"; return SIGMAENV_EINVAL; }
   const int n = m->w.n_layers;
   if (!grad_w || !grad_b) { h->err = what + ": null gradient pointer array"; return SIGMAENV_EINVAL; }
   for (int l = 0; l < n; ++l)
@@ -320,7 +349,7 @@ static int mlp32_backward_impl(sigmaenv_t* h, sigmaenv_mlp32* m, const char* wha
   int64_t rows = 0;
   if (index || n_index)
     if (const int rc = mlp32_grad_index(h, what_c, n_blocks, block_stride, index, n_index, &ix)) return rc;
-  if (const int rc = mlp32_grad_rows(h, m, what_c, in, rows_per_block, row_stride, ix.index ? n_index : n_blocks, block_stride, &rw, &rows)) return rc;
+  if (const int rc = mlp32_grad_rows(h, m, what_c, in, rows_per_block, row_stride, ix.index ? n_index : n_blocks, block_stride, &rw, &rows, pad)) return rc;
   if (rows > 0 && (!acts || !dout || !workspace || ((uintptr_t)acts & 15) || ((uintptr_t)dout & 3) || ((uintptr_t)workspace & 15))) {
     h->err = what + ": null acts / dout / workspace, or acts / workspace not 16-byte aligned";
     return SIGMAENV_EINVAL;
@@ -347,9 +376,10 @@ static int mlp32_backward_impl(sigmaenv_t* h, sigmaenv_mlp32* m, const char* wha
       p.a = l == 0 ? in : acts + (size_t)(l - 1) * (size_t)R * MLP32_H;
       p.pw = pw; p.pb = pb; p.F = F; p.K = K; p.R = R; p.len = grad::range_len(rows);
       const dim3 grid((unsigned)(((F + GRAD_BLK - 1) / GRAD_BLK) * ((K + GRAD_BLK - 1) / GRAD_BLK)), (unsigned)ranges);
-      if (l == 0 && ix.index) hipLaunchKernelGGL((grad::sigmaenv_mlp32_dw_kernel<true, true>), grid, dim3(256), 0, h->stream, p, rw, ix);
-      else if (l == 0) hipLaunchKernelGGL(grad::sigmaenv_mlp32_dw_kernel<true>, grid, dim3(256), 0, h->stream, p, rw, Mlp32Index{});
-      else hipLaunchKernelGGL(grad::sigmaenv_mlp32_dw_kernel<false>, grid, dim3(256), 0, h->stream, p, Mlp32Rows{}, Mlp32Index{});
+      if (l == 0 && pad) hipLaunchKernelGGL((grad::sigmaenv_mlp32_dw_kernel<true, true, true>), grid, dim3(256), 0, h->stream, p, rw, ix, *pad);
+      else if (l == 0 && ix.index) hipLaunchKernelGGL((grad::sigmaenv_mlp32_dw_kernel<true, true>), grid, dim3(256), 0, h->stream, p, rw, ix, Mlp32Pad{});
+      else if (l == 0) hipLaunchKernelGGL(grad::sigmaenv_mlp32_dw_kernel<true>, grid, dim3(256), 0, h->stream, p, rw, Mlp32Index{}, Mlp32Pad{});
+      else hipLaunchKernelGGL(grad::sigmaenv_mlp32_dw_kernel<false>, grid, dim3(256), 0, h->stream, p, Mlp32Rows{}, Mlp32Index{}, Mlp32Pad{});
       HIPCHK(h, hipGetLastError());
     }
     hipLaunchKernelGGL(grad::sigmaenv_mlp32_dw_sum_kernel, dim3((unsigned)((F * K + F + 255) / 256)), dim3(256), 0, h->stream, pw, pb, ranges, F * K, F, grad_w[l], grad_b[l]);
@@ -368,4 +398,12 @@ extern "C" int sigmaenv_mlp32_backward_indexed(sigmaenv_t* h, sigmaenv_mlp32* m,
   // (an empty minibatch is the rows = 0 case of sigmaenv_mlp32_backward: the gradients are written as zeros)
   if (!index && n_index == 0) return mlp32_backward_impl(h, m, "mlp32_backward_indexed", in, rows_per_block, row_stride, 0, block_stride, nullptr, 0, acts, dout, workspace, grad_w, grad_b);
   return mlp32_backward_impl(h, m, "mlp32_backward_indexed", in, rows_per_block, row_stride, n_blocks, block_stride, index, n_index, acts, dout, workspace, grad_w, grad_b);
+}
+// the same on padded rows (sigmaenv_mlp32_forward_save_indexed_pad's): dW_0's columns of the padding are zeros
+extern "C" int sigmaenv_mlp32_backward_indexed_pad(sigmaenv_t* h, sigmaenv_mlp32* m, const float* in, int32_t rows_per_block, int64_t row_stride, int32_t n_blocks,
+                                                   int64_t block_stride, const int32_t* index, int32_t n_index, int32_t seg_src, int32_t seg_dst, const float* acts,
+                                                   const float* dout, float* workspace, float* const* grad_w, float* const* grad_b) {
+  if (!index && n_index == 0) return mlp32_backward_impl(h, m, "mlp32_backward_indexed_pad", in, rows_per_block, row_stride, 0, block_stride, nullptr, 0, acts, dout, workspace, grad_w, grad_b);
+  const Mlp32Pad pd{seg_src, seg_dst};
+  return mlp32_backward_impl(h, m, "mlp32_backward_indexed_pad", in, rows_per_block, row_stride, n_blocks, block_stride, index, n_index, acts, dout, workspace, grad_w, grad_b, &pd);
 }

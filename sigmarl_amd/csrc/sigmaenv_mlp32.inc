@@ -68,6 +68,18 @@ __device__ __forceinline__ long long mlp32_indexed_row_offset(int row, const Mlp
   const int f = ix.index[t];
   return (unsigned)f < (unsigned)ix.n_blocks ? (long long)f * rw.block_stride + (long long)b * rw.row_stride : -1ll;
 }
+// Padded rows (sigmaenv_mlp32_forward_rows_pad / sigmaenv_mlp32_forward_save_indexed_pad / sigmaenv_mlp32_backward_indexed_pad): the network's input row is in_dim / dst
+// segments of width dst, the row in memory the same number of segments of width src <= dst: network column k = a * dst + j reads the row's float a * src + j for
+// j < src and is zero for j >= src -- the base critic's next rows (per agent the D floats of the record's next observation, then 2 K zeros), staged without a padded
+// copy in HBM.  A segment boundary may fall inside a 16-byte granule, so the padded instantiations stage column by column (the loop of an input width that is no
+// multiple of 4); what is staged is what a dense call stages from the padded copy, so the results are its bits.
+struct Mlp32Pad {
+  int src, dst;
+};
+__device__ __forceinline__ float mlp32_pad_load(const float* __restrict__ row, int k, const Mlp32Pad& pd) {
+  const int a = k / pd.dst, j = k - a * pd.dst;
+  return j < pd.src ? row[a * pd.src + j] : 0.0f;
+}
 // Four (eight) floats at a 4-byte-aligned address p from 16-byte-ALIGNED loads: the granule that holds p[0] and the following one (two), each only when it holds
 // one of the wanted floats -- so no load touches a granule without a valid float, and an aligned granule never crosses a page --, the wanted floats selected by
 // s = the offset of p in its granule.  A row's lanes read consecutive granules: the requests coalesce as those of the aligned path do (3 loads per 8 floats, not 2).
@@ -154,9 +166,10 @@ __device__ __forceinline__ void mlp32_tile_k256(const float4* __restrict__ wa, c
 // INDEXED (sigmaenv_mlp32_forward_save_indexed): a fourth instantiation, <true, true, true>, whose rows are blocks picked by `ix` (Mlp32Index).  The 64 row offsets of the
 // tile are formed once, by the first 64 lanes, into the LDS words the output layer's partial sums use much later; stage() reads them from there.  The other three never
 // read `ix` and keep their figures (profiles/ppo_kernel_resources.txt).
-template <bool ROWS, bool SAVE = false, bool INDEXED = false>
+// PAD (Mlp32Pad): <true, false, false, true> and <true, true, true, true>, the padded forms of the record rows and of the indexed saving forward; the others never read `pd`.
+template <bool ROWS, bool SAVE = false, bool INDEXED = false, bool PAD = false>
 __global__ void __launch_bounds__(256, 2) sigmaenv_mlp32_kernel(Mlp32Weights mw, const float* __restrict__ in, int R, int in_dim, float* __restrict__ out, Mlp32Rows rw,
-                                                                float* __restrict__ acts, Mlp32Index ix MLP32_TS_ARG) {
+                                                                float* __restrict__ acts, Mlp32Index ix, Mlp32Pad pd MLP32_TS_ARG) {
   sigma_poison_lds();
   MLP32_TS(0);
 #ifdef SIGMAENV_PROFILE
@@ -198,7 +211,20 @@ __global__ void __launch_bounds__(256, 2) sigmaenv_mlp32_kernel(Mlp32Weights mw,
   }
   // input tile, columns [c0, c0 + cw) of layer 0 (cw a multiple of 8, at most MLP32_KC; columns >= in_dim are zeros) at LDS columns [0, cw)
   auto stage = [&](const int c0, const int cw) {
-    if ((in_dim & 3) == 0) {  // four columns per lane and load (rows are 16-byte aligned: include/sigmaenv.h)
+    if constexpr (PAD) {
+      for (int e = tid; e < cw * MLP32_ROWS; e += blockDim.x) {            // (coalesced along k within a segment)
+        const int n = e / cw, kl = e - n * cw, k = c0 + kl;
+        const int row = row0 + n;
+        float v = 0.0f;
+        if constexpr (INDEXED) {
+          const long long off = row_off[n];
+          if (off >= 0 && k < in_dim) v = mlp32_pad_load(in + off, k, pd);
+        } else if (row < R && k < in_dim) {
+          v = mlp32_pad_load(mlp32_row_ptr<true>(in, row, in_dim, rw), k, pd);
+        }
+        x[mlp32_act_idx(kl, n)] = v;
+      }
+    } else if ((in_dim & 3) == 0) {  // four columns per lane and load (rows are 16-byte aligned: include/sigmaenv.h)
       const int Q = cw >> 2;
       for (int e = tid; e < Q * MLP32_ROWS; e += blockDim.x) {
         const int n = e / Q, kl = (e - n * Q) << 2, k = c0 + kl;
@@ -501,6 +527,43 @@ extern "C" int sigmaenv_mlp32_forward_rows(sigmaenv_t* h, sigmaenv_mlp32* m, con
   rw.aligned = ((uintptr_t)in & 15) == 0 && (row_stride & 3) == 0 && (block_stride & 3) == 0;
   return mlp32_forward_impl(h, m, in, rows_per_block * n_blocks, out, nullptr, nullptr, &rw);
 }
+// sigmaenv_mlp32_forward_rows on padded rows (Mlp32Pad): the row in memory holds in_dim / seg_dst segments of seg_src floats.  Both modes; no distribution head.
+extern "C" int sigmaenv_mlp32_forward_rows_pad(sigmaenv_t* h, sigmaenv_mlp32* m, const float* in, int32_t rows_per_block, int64_t row_stride, int32_t n_blocks, int64_t block_stride,
+                                               int32_t seg_src, int32_t seg_dst, float* out) {
+  if (!h || !m || !in || !out || rows_per_block < 0 || n_blocks < 0) return SIGMAENV_EINVAL;
+  if ((int64_t)rows_per_block * n_blocks > INT32_MAX) { h->err = "mlp32_forward_rows_pad: more than 2^31 - 1 rows"; return SIGMAENV_EINVAL; }
+  if (seg_src < 1 || seg_dst < seg_src || m->in_dim % seg_dst) { h->err = "mlp32_forward_rows_pad: 1 <= seg_src <= seg_dst, and seg_dst divides the network's input width"; return SIGMAENV_EINVAL; }
+  if (rows_per_block == 0 || n_blocks == 0) return SIGMAENV_OK;
+  if (row_stride < (int64_t)(m->in_dim / seg_dst) * seg_src || ((uintptr_t)in & 3) || (n_blocks > 1 && block_stride < 0)) {
+    h->err = "mlp32_forward_rows_pad: row_stride below the source row's width, a negative block_stride or an input that is not 4-byte aligned";
+    return SIGMAENV_EINVAL;
+  }
+  Mlp32Rows rw{};
+  rw.rpb = rows_per_block; rw.row_stride = row_stride; rw.block_stride = block_stride; rw.aligned = 0;
+  const Mlp32Pad pd{seg_src, seg_dst};
+  const int rows = rows_per_block * n_blocks;
+  const dim3 grid((rows + MLP32_ROWS - 1) / MLP32_ROWS);
+  HIPCHK(h, hipSetDevice(h->device));
+  const int slot = timer_begin(h, SIGMAENV_KERNEL_MLP32);
+  if (m->mode == SIGMAENV_MLP32_SPLIT) {
+    if (m->smem_s > 64 * 1024) HIPCHK(h, hipFuncSetAttribute(reinterpret_cast<const void*>(sigmaenv_mlp32s_kernel<true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)m->smem_s));
+#ifdef SIGMAENV_PROFILE
+    hipLaunchKernelGGL((sigmaenv_mlp32s_kernel<true, true>), grid, dim3(256), m->smem_s, h->stream, m->ws, in, rows, m->in_dim, out, Mlp32sHead{}, rw, pd, (unsigned long long*)nullptr, 0);
+#else
+    hipLaunchKernelGGL((sigmaenv_mlp32s_kernel<true, true>), grid, dim3(256), m->smem_s, h->stream, m->ws, in, rows, m->in_dim, out, Mlp32sHead{}, rw, pd);
+#endif
+  } else {
+    if (m->smem > 64 * 1024) HIPCHK(h, hipFuncSetAttribute(reinterpret_cast<const void*>(sigmaenv_mlp32_kernel<true, false, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)m->smem));
+#ifdef SIGMAENV_PROFILE
+    hipLaunchKernelGGL((sigmaenv_mlp32_kernel<true, false, false, true>), grid, dim3(256), m->smem, h->stream, m->w, in, rows, m->in_dim, out, rw, (float*)nullptr, Mlp32Index{}, pd, (unsigned long long*)nullptr, 0);
+#else
+    hipLaunchKernelGGL((sigmaenv_mlp32_kernel<true, false, false, true>), grid, dim3(256), m->smem, h->stream, m->w, in, rows, m->in_dim, out, rw, (float*)nullptr, Mlp32Index{}, pd);
+#endif
+  }
+  HIPCHK(h, hipGetLastError());
+  timer_end(h, SIGMAENV_KERNEL_MLP32, slot);
+  return SIGMAENV_OK;
+}
 // head: the actor's distribution head, run as the epilogue of the split-mode kernel (*head_done = true) -- the exact mode leaves it to the caller's head launch
 // rw: the rows' addresses (sigmaenv_mlp32_forward_rows); nullptr: dense
 static int mlp32_forward_impl(sigmaenv_t* h, sigmaenv_mlp32* m, const float* in, int32_t rows, float* out, const Mlp32sHead* head, bool* head_done, const Mlp32Rows* rw) {
@@ -538,11 +601,11 @@ static int mlp32_forward_impl(sigmaenv_t* h, sigmaenv_mlp32* m, const float* in,
       HIPCHK(h, hipFuncSetAttribute(kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem_l));
     }
     const int stagger_l = getenv("SIGMAENV_MLP32_STAGGER") ? atoi(getenv("SIGMAENV_MLP32_STAGGER")) : 0;
-    if (rw) hipLaunchKernelGGL(sigmaenv_mlp32s_kernel<true>, dim3((rows + MLP32_ROWS - 1) / MLP32_ROWS), dim3(256), smem_l, h->stream, m->ws, in, (int)rows, m->in_dim, out, hd_, *rw, m->ts, stagger_l);
-    else hipLaunchKernelGGL(sigmaenv_mlp32s_kernel<false>, dim3((rows + MLP32_ROWS - 1) / MLP32_ROWS), dim3(256), smem_l, h->stream, m->ws, in, (int)rows, m->in_dim, out, hd_, Mlp32Rows{}, m->ts, stagger_l);
+    if (rw) hipLaunchKernelGGL(sigmaenv_mlp32s_kernel<true>, dim3((rows + MLP32_ROWS - 1) / MLP32_ROWS), dim3(256), smem_l, h->stream, m->ws, in, (int)rows, m->in_dim, out, hd_, *rw, Mlp32Pad{}, m->ts, stagger_l);
+    else hipLaunchKernelGGL(sigmaenv_mlp32s_kernel<false>, dim3((rows + MLP32_ROWS - 1) / MLP32_ROWS), dim3(256), smem_l, h->stream, m->ws, in, (int)rows, m->in_dim, out, hd_, Mlp32Rows{}, Mlp32Pad{}, m->ts, stagger_l);
 #else
-    if (rw) hipLaunchKernelGGL(sigmaenv_mlp32s_kernel<true>, dim3((rows + MLP32_ROWS - 1) / MLP32_ROWS), dim3(256), m->smem_s, h->stream, m->ws, in, (int)rows, m->in_dim, out, hd_, *rw);
-    else hipLaunchKernelGGL(sigmaenv_mlp32s_kernel<false>, dim3((rows + MLP32_ROWS - 1) / MLP32_ROWS), dim3(256), m->smem_s, h->stream, m->ws, in, (int)rows, m->in_dim, out, hd_, Mlp32Rows{});
+    if (rw) hipLaunchKernelGGL(sigmaenv_mlp32s_kernel<true>, dim3((rows + MLP32_ROWS - 1) / MLP32_ROWS), dim3(256), m->smem_s, h->stream, m->ws, in, (int)rows, m->in_dim, out, hd_, *rw, Mlp32Pad{});
+    else hipLaunchKernelGGL(sigmaenv_mlp32s_kernel<false>, dim3((rows + MLP32_ROWS - 1) / MLP32_ROWS), dim3(256), m->smem_s, h->stream, m->ws, in, (int)rows, m->in_dim, out, hd_, Mlp32Rows{}, Mlp32Pad{});
 #endif
     HIPCHK(h, hipGetLastError());
     timer_end(h, SIGMAENV_KERNEL_MLP32, slot);
@@ -567,11 +630,11 @@ static int mlp32_forward_impl(sigmaenv_t* h, sigmaenv_mlp32* m, const float* in,
     HIPCHK(h, hipFuncSetAttribute(kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem_l));
   }
   const int stagger_l = getenv("SIGMAENV_MLP32_STAGGER") ? atoi(getenv("SIGMAENV_MLP32_STAGGER")) : 0;
-  if (rw) hipLaunchKernelGGL(sigmaenv_mlp32_kernel<true>, dim3((rows + MLP32_ROWS - 1) / MLP32_ROWS), dim3(256), smem_l, h->stream, m->w, in, (int)rows, m->in_dim, out, *rw, (float*)nullptr, Mlp32Index{}, m->ts, stagger_l);
-  else hipLaunchKernelGGL(sigmaenv_mlp32_kernel<false>, dim3((rows + MLP32_ROWS - 1) / MLP32_ROWS), dim3(256), smem_l, h->stream, m->w, in, (int)rows, m->in_dim, out, Mlp32Rows{}, (float*)nullptr, Mlp32Index{}, m->ts, stagger_l);
+  if (rw) hipLaunchKernelGGL(sigmaenv_mlp32_kernel<true>, dim3((rows + MLP32_ROWS - 1) / MLP32_ROWS), dim3(256), smem_l, h->stream, m->w, in, (int)rows, m->in_dim, out, *rw, (float*)nullptr, Mlp32Index{}, Mlp32Pad{}, m->ts, stagger_l);
+  else hipLaunchKernelGGL(sigmaenv_mlp32_kernel<false>, dim3((rows + MLP32_ROWS - 1) / MLP32_ROWS), dim3(256), smem_l, h->stream, m->w, in, (int)rows, m->in_dim, out, Mlp32Rows{}, (float*)nullptr, Mlp32Index{}, Mlp32Pad{}, m->ts, stagger_l);
 #else
-  if (rw) hipLaunchKernelGGL(sigmaenv_mlp32_kernel<true>, dim3((rows + MLP32_ROWS - 1) / MLP32_ROWS), dim3(256), m->smem, h->stream, m->w, in, (int)rows, m->in_dim, out, *rw, (float*)nullptr, Mlp32Index{});
-  else hipLaunchKernelGGL(sigmaenv_mlp32_kernel<false>, dim3((rows + MLP32_ROWS - 1) / MLP32_ROWS), dim3(256), m->smem, h->stream, m->w, in, (int)rows, m->in_dim, out, Mlp32Rows{}, (float*)nullptr, Mlp32Index{});
+  if (rw) hipLaunchKernelGGL(sigmaenv_mlp32_kernel<true>, dim3((rows + MLP32_ROWS - 1) / MLP32_ROWS), dim3(256), m->smem, h->stream, m->w, in, (int)rows, m->in_dim, out, *rw, (float*)nullptr, Mlp32Index{}, Mlp32Pad{});
+  else hipLaunchKernelGGL(sigmaenv_mlp32_kernel<false>, dim3((rows + MLP32_ROWS - 1) / MLP32_ROWS), dim3(256), m->smem, h->stream, m->w, in, (int)rows, m->in_dim, out, Mlp32Rows{}, (float*)nullptr, Mlp32Index{}, Mlp32Pad{});
 #endif
   HIPCHK(h, hipGetLastError());
   timer_end(h, SIGMAENV_KERNEL_MLP32, slot);

@@ -95,9 +95,10 @@ struct Mlp32sHead {
 };
 // ROWS: as sigmaenv_mlp32_kernel -- false: `in` is dense [R][in_dim], 16-byte aligned (rw is not read); true: the rows of a record (sigmaenv_mlp32_forward_rows).
 // Only the input-tile staging differs; the dense instantiation compiles to what the kernel was before the strided one existed (216 VGPRs, no scratch).
-template <bool ROWS>
+// PAD (Mlp32Pad, sigmaenv_mlp32.inc): <true, true>, the padded form of the record rows, staged column by column; the other two never read `pd`.
+template <bool ROWS, bool PAD = false>
 __global__ void __launch_bounds__(256, 2) sigmaenv_mlp32s_kernel(Mlp32sWeights mw, const float* __restrict__ in, int R, int in_dim, float* __restrict__ out, Mlp32sHead hd,
-                                                                 Mlp32Rows rw MLP32_TS_ARG) {
+                                                                 Mlp32Rows rw, Mlp32Pad pd MLP32_TS_ARG) {
   sigma_poison_lds();
   MLP32_TS(0);
 #ifdef SIGMAENV_PROFILE
@@ -124,7 +125,7 @@ __global__ void __launch_bounds__(256, 2) sigmaenv_mlp32s_kernel(Mlp32sWeights m
   for (int l = 0; l + 1 < mw.n_layers; ++l) bl[l * MLP32_H + tid] = MLP32S_SEL(b, l)[tid];
   if (tid < 32) bl[(mw.n_layers - 1) * MLP32_H + tid] = MLP32S_SEL(b, mw.n_layers - 1)[tid];
   // ---- input tile: fp32 rows -> split fragments
-  if ((in_dim & 7) == 0) {
+  if (!PAD && (in_dim & 7) == 0) {
     const int Q0 = KB0 * 2;  // fragments (of 8 columns) per row
     for (int e = tid; e < Q0 * MLP32_ROWS; e += 256) {
       const int r = e / Q0, c8 = e - r * Q0, k = c8 << 3, row = row0 + r;
@@ -153,7 +154,11 @@ __global__ void __launch_bounds__(256, 2) sigmaenv_mlp32s_kernel(Mlp32sWeights m
     const int K0 = KB0 * 16;
     for (int e = tid; e < K0 * MLP32_ROWS; e += 256) {
       const int r = e / K0, k = e - r * K0, row = row0 + r;
-      const float v = (row < R && k < in_dim) ? mlp32s_sat(mlp32_row_ptr<ROWS>(in, row, in_dim, rw)[k] * MLP32S_SX0) : 0.0f;
+      float v = 0.0f;
+      if (row < R && k < in_dim) {
+        if constexpr (PAD) v = mlp32s_sat(mlp32_pad_load(mlp32_row_ptr<true>(in, row, in_dim, rw), k, pd) * MLP32S_SX0);
+        else v = mlp32s_sat(mlp32_row_ptr<ROWS>(in, row, in_dim, rw)[k] * MLP32S_SX0);
+      }
       _Float16 a16, b16;
       mlp32s_split(v, a16, b16);
       const size_t f = (size_t)(k >> 4) * 256 + ((k >> 3) & 1) * 64 + r;

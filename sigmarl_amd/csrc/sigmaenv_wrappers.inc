@@ -68,10 +68,12 @@ __global__ void __launch_bounds__(256) sigmaenv_priority_random_kernel(int B, in
 
 // turn k of prioritized action propagation: compact[b, :] = the base observation of agent i = ranks[b, k] (its SIGMAENV_BUF_OBS row, then 2 K columns with the
 // current actions of its observed neighbours: `actions` is zero for those that have not acted, as combined_action, helper_training.py:1219-1300);
-// row_map[b] = b N + i (-1 when ranks holds no agent index).  rec (optional, [B, N, K, 2]): the neighbour actions agent i saw.  One lane per (env, column).
+// row_map[b] = b N + i (-1 when ranks holds no agent index).  rec (optional, [B, N, K, 2]): the neighbour actions agent i saw.  base_rec (optional,
+// [B, N, D + 2 K]): the whole compact row at agent i's place -- the base observation a learner trains the actor on; one more store per gathered element, coalesced
+// over the row as the compact one is.  One lane per (env, column).
 __global__ void __launch_bounds__(256) sigmaenv_turn_gather_kernel(const float* __restrict__ obs, int D, const int32_t* __restrict__ nearing, int K, const float* __restrict__ actions,
                                                                    const int32_t* __restrict__ ranks, int k, int B, int N, float* __restrict__ compact, int32_t* __restrict__ row_map,
-                                                                   float* __restrict__ rec) {
+                                                                   float* __restrict__ rec, float* __restrict__ base_rec) {
   sigma_poison_lds();
   const int Dc = D + 2 * K;
   const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -92,6 +94,7 @@ __global__ void __launch_bounds__(256) sigmaenv_turn_gather_kernel(const float* 
       if (n >= 0 && n < N) v = actions[(b * N + n) * 2 + (q & 1)];
       if (rec) rec[(bi * K + j) * 2 + (q & 1)] = v;
     }
+    if (base_rec) base_rec[bi * Dc + c] = v;
   }
   compact[t] = v;
 }
@@ -214,10 +217,11 @@ extern "C" int sigmaenv_rollout_f32_ex(sigmaenv_t* h, sigmaenv_mlp32* m, const f
     HIPCHK(h, hipMemsetAsync(act, 0, BN * 2 * sizeof(float), h->stream));  // combined_action / combined_sample_log_prob start at zero
     if (logp) HIPCHK(h, hipMemsetAsync(logp, 0, BN * sizeof(float), h->stream));
     float* rec = opts->tentative_rec ? opts->tentative_rec + (size_t)t * BN * K * 2 : nullptr;
+    float* base_rec = opts->base_obs_rec ? opts->base_obs_rec + (size_t)t * BN * Dc : nullptr;
     const size_t n_gather = (size_t)B * Dc;
     for (int k = 0; k < N; ++k) {
       hipLaunchKernelGGL(wrap::sigmaenv_turn_gather_kernel, dim3((unsigned)((n_gather + 255) / 256)), dim3(256), 0, h->stream, h->buf.obs, D, h->buf.nearing, K, act, ranks, k, B, N,
-                         compact, row_map, rec);
+                         compact, row_map, rec, base_rec);
       HIPCHK(h, hipGetLastError());
       const int r = actor_rows_f32(h, m, compact, B, row_map, scratch, low, high, act, logp, nullptr, seed, ctr, deterministic);
       if (r) return r;

@@ -12,6 +12,11 @@ and the learner's side, ``_train_epoch`` / ``_train_on_batch`` (``sigmarl/mappo_
   ``Actor.apply`` / ``Critic.apply(index=)``   the networks on the frames of a minibatch, read from the records where they lie, with a ``grad_fn``
   ``ppo_head``                     ``sigmaenv_ppo_head``: torchrl's ``ClipPPOLoss`` as ``sigmarl/modules/optimization_module.py:44-66`` configures it, one fused launch
                                    from the networks' outputs and the records to the loss terms and both ``dout`` tensors
+  ``priority_ppo_head``            ``sigmaenv_ppo_head_1d``: the same loss for the priority module's 1-D score distribution and its own critic
+                                   (``sigmarl/modules/priority_module.py:93-126``), under a draw id of its own
+and, with ``Parameters.is_using_prioritized_marl`` and ``prioritization_method="marl"`` (``collect`` / ``update`` / ``train_iteration`` / ``train`` with
+``wrapper="prioritized"`` and ``priority=``): the base actor and critic on the recorded base observation (``Actor.rollout(base_obs=)``, the critic's next rows staged
+padded: ``Critic.rollout_values(pad=)``), the priority critic's own GAE, and the priority module's step behind every base optimiser step
   ``Adam``                         ``sigmaenv_optim_step``: ``clip_grad_norm_`` over all networks in one norm, ``torch.optim.Adam``'s step and the repack of every
                                    network's weight forms, three launches and no host wait (``:421-426``); ``resolve`` = the one wait, before the next rollout
   ``update``                       the epochs x minibatches loop: apply -> head -> backward -> ``Adam.step`` (the device route), or with a torch optimiser
@@ -34,7 +39,7 @@ import ctypes as C
 import torch
 
 from . import capi
-from .actor import Actor, Mlp32, check_record, load_source, source_pairs
+from .actor import Actor, Critic, Mlp32, PriorityNet, check_record, load_source, source_pairs
 
 TD_GAMMA = 0.9  # compute_td_error's discount as the trainer calls it (mappo_cavs.py:383, :454) -- not Parameters.gamma
 
@@ -81,15 +86,30 @@ def gae(env, slab: torch.Tensor, state_value: torch.Tensor, next_state_value: to
     return adv, vt, td
 
 
+BASE_OBS, PRIORITY = ("info", "base_observation"), ("info", "priority")  # the reference tensordict's keys of prioritized action propagation
+
+
 def collect(env, actor, critic, T: int, params=None, gamma: float | None = None, lmbda: float | None = None, td_gamma: float = TD_GAMMA, td_error: bool = True,
-            seed: int = 0, counter0: int = 0, returns: "EpisodeReturns | None" = None, **rollout_kw) -> dict:
+            seed: int = 0, counter0: int = 0, returns: "EpisodeReturns | None" = None, priority_critic=None, **rollout_kw) -> dict:
     """One learner-ready batch: ``T`` steps of the device rollout (``Actor.rollout``, ``rollout_kw`` = its wrapper / path / precision arguments), the critic on
     both sides of every step, GAE and the TD-error priorities -- enqueued on the env's stream, nothing copied in between.  ``gamma`` / ``lmbda`` come from
     ``params`` (a ``Parameters``; default: the env's) unless given.  Returns device tensors under the reference tensordict's keys:
     ``observation [T,B,N,D]``, ``action [T,B,N,2]``, ``sample_log_prob [T,B,N]``, ``("next", "observation") [T,B,N,D]``, ``("next", "reward") [T,B,N]``,
     ``("next", "done") [T,B]`` (the record's float flag) -- the three zero-copy views of the record, which is returned whole as ``"slab"`` --, ``state_value`` /
     ``("next", "state_value") [T,B]`` (one value per env: every agent's), ``advantage`` / ``value_target [T,B,N]``, ``td_error [T,B]``.  With ``returns`` (an ``EpisodeReturns`` of this env, which carries the
-    open episodes' sums from one call to the next) the batch gains ``("next", "episode_reward") [T,B,N]`` and ``"episode_stats"`` (``EpisodeReturns.update``)."""
+    open episodes' sums from one call to the next) the batch gains ``("next", "episode_reward") [T,B,N]`` and ``"episode_stats"`` (``EpisodeReturns.update``).
+
+    Prioritized action propagation (``wrapper="prioritized"`` with a ``critic`` on ``N (D + 2 K)`` inputs: the base critic reads the base observation, as the base
+    actor does -- ``get_observation_key``, ``sigmarl/helper_training.py:1145-1150``): the rollout also records ``("info", "base_observation") [T,B,N,D + 2 K]`` and
+    ``("info", "priority", "rank") [T,B,N]`` (int32); ``state_value`` is the critic on that record and ``("next", "state_value")`` the critic on the record's next
+    observations with every agent's 2 K placeholder columns zero (``Critic.rollout_values(pad=)``: the reference's ``("next", base_observation)`` is the env's own
+    output).  With ``priority=`` a ``PriorityNet`` the batch gains ``("info", "priority", "scores")`` / ``("info", "priority", "sample_log_prob")``, and with
+    ``priority_critic=`` (a ``Critic`` on the ``N D`` priority observation, which is ``env.obs``) its values on ``observation`` / the next observations as
+    ``("info", "priority", "state_value")`` / ``("next", "info", "priority", "state_value")`` and a SECOND ``sigmaenv_gae`` on them.  Which pair the losses read, as the
+    reference RUNS: its priority loss module never re-keys ``advantage`` / ``value_target`` (``sigmarl/modules/priority_module.py:102-113``: the two ``set_keys``
+    entries are commented out), so ``priority_module.GAE``, run after the base GAE (``sigmarl/mappo_cavs.py:370-378``), overwrites both keys and BOTH losses train on
+    the priority critic's pair.  So with a ``priority_critic`` ``batch["advantage"]`` / ``batch["value_target"]`` are the PRIORITY critic's pair and the base critic's
+    stay available as ``batch["base_advantage"]`` / ``batch["base_value_target"]``; ``td_error`` stays the base critic's (``compute_td_error`` reads its values)."""
     if returns is not None and not (isinstance(returns, EpisodeReturns) and returns.env is env):
         raise TypeError("collect(): returns must be a learn.EpisodeReturns of this env")
     p = params if params is not None else getattr(env, "parameters", None)
@@ -97,10 +117,15 @@ def collect(env, actor, critic, T: int, params=None, gamma: float | None = None,
         raise ValueError("collect(): gamma and lmbda, or a Parameters to take them from")
     gamma = float(gamma if gamma is not None else p.gamma)
     lmbda = float(lmbda if lmbda is not None else p.lmbda)
-    for k in ("slab", "log_prob", "actions", "obs_rec", "slab_ptr"):
+    for k in ("slab", "log_prob", "actions", "obs_rec", "slab_ptr", "base_obs", "scores", "score_log_prob", "ranks"):
         if k in rollout_kw:
             raise TypeError(f"collect() makes the {k} record itself")
     T, B, N, D = int(T), env.B, env.N, env.D
+    Dc = D + 2 * env.K
+    if rollout_kw.get("wrapper") == "prioritized" and (critic.in_dim == N * Dc != N * D or priority_critic is not None):
+        return _collect_prioritized(env, actor, critic, priority_critic, T, gamma, lmbda, td_gamma, td_error, seed, counter0, returns, rollout_kw)
+    if priority_critic is not None:
+        raise ValueError("collect(): priority_critic belongs to wrapper='prioritized'")
     W = N * (D + 1) + 1
     kw = dict(dtype=torch.float32, device=env.device)
     slab, obs = torch.empty((T, B, W), **kw), torch.empty((T, B, N, D), **kw)
@@ -113,6 +138,40 @@ def collect(env, actor, critic, T: int, params=None, gamma: float | None = None,
         ("next", "observation"): slab[:, :, : N * D].unflatten(2, (N, D)), ("next", "reward"): slab[:, :, N * D: N * D + N], ("next", "done"): slab[:, :, N * D + N],
         "state_value": sv, ("next", "state_value"): nv, "advantage": adv, "value_target": vt,
     }
+    if td is not None:
+        out["td_error"] = td
+    if returns is not None:
+        out[("next", "episode_reward")], out["episode_stats"] = returns.update(slab, T)
+    return out
+
+
+def _collect_prioritized(env, actor, critic, priority_critic, T, gamma, lmbda, td_gamma, td_error, seed, counter0, returns, rollout_kw) -> dict:
+    """``collect`` under prioritized action propagation (its docstring): the records of the wrapper, the base critic on base observations, the priority critic's pair"""
+    B, N, D, K = env.B, env.N, env.D, env.K
+    W, Dc = N * (D + 1) + 1, D + 2 * K
+    net = isinstance(rollout_kw.get("priority"), PriorityNet)
+    if priority_critic is not None and not (net and isinstance(priority_critic, Critic)):
+        raise TypeError("collect(): priority_critic is a Critic on the priority observation, next to priority= a PriorityNet")
+    kw = dict(dtype=torch.float32, device=env.device)
+    slab, obs, base = torch.empty((T, B, W), **kw), torch.empty((T, B, N, D), **kw), torch.empty((T, B, N, Dc), **kw)
+    act, logp = torch.empty((T, B, N, 2), **kw), torch.empty((T, B, N), **kw)
+    ranks = torch.empty((T, B, N), dtype=torch.int32, device=env.device)
+    rec = dict(scores=torch.empty((T, B, N), **kw), score_log_prob=torch.empty((T, B, N), **kw)) if net else {}
+    actor.rollout(env, T, slab=slab, log_prob=logp, actions=act, obs_rec=obs, base_obs=base, ranks=ranks, seed=seed, counter0=counter0, **rec, **rollout_kw)
+    sv, nv = critic.rollout_values(env, slab, base, T, pad=(D, Dc))
+    adv, vt, td = gae(env, slab, sv, nv, gamma, lmbda, td_error=bool(td_error), td_gamma=td_gamma)
+    out = {
+        "observation": obs, "action": act, "sample_log_prob": logp, "slab": slab, BASE_OBS: base, PRIORITY + ("rank",): ranks,
+        ("next", "observation"): slab[:, :, : N * D].unflatten(2, (N, D)), ("next", "reward"): slab[:, :, N * D: N * D + N], ("next", "done"): slab[:, :, N * D + N],
+        "state_value": sv, ("next", "state_value"): nv, "advantage": adv, "value_target": vt,
+    }
+    if net:
+        out[PRIORITY + ("scores",)], out[PRIORITY + ("sample_log_prob",)] = rec["scores"], rec["score_log_prob"]
+    if priority_critic is not None:
+        psv, pnv = priority_critic.rollout_values(env, slab, obs, T)
+        padv, pvt, _ = gae(env, slab, psv, pnv, gamma, lmbda, td_error=False)
+        out[PRIORITY + ("state_value",)], out[("next",) + PRIORITY + ("state_value",)] = psv, pnv
+        out["base_advantage"], out["base_value_target"], out["advantage"], out["value_target"] = adv, vt, padv, pvt
     if td is not None:
         out["td_error"] = td
     if returns is not None:
@@ -265,6 +324,75 @@ def ppo_head(env, out: torch.Tensor, value: torch.Tensor, batch: dict, index: to
     a.clip_epsilon, a.entropy_coeff, a.critic_coeff = float(clip_epsilon), float(entropy_coeff), float(critic_coeff)
     a.seed, a.counter = int(seed) & 0xFFFFFFFFFFFFFFFF, int(counter) & 0xFFFFFFFFFFFFFFFF
     loss, result = _PpoHeadFunction.apply(env, a, (index, *recs), out.reshape(M, N, 4).contiguous(), value.reshape(M).contiguous())
+    return loss, {k: result[i] for i, k in enumerate(capi.PPO_RESULT)}
+
+
+class _PriorityPpoHeadFunction(torch.autograd.Function):
+    """``priority_ppo_head``: ``sigmaenv_ppo_head_1d`` forwards; backwards the stored ``dout`` tensors times the incoming gradient of the loss."""
+
+    @staticmethod
+    def forward(ctx, env, args, keep, out, value):
+        dev = env.device
+        M, N = out.shape[0], out.shape[1]
+        kw = dict(dtype=torch.float32, device=dev)
+        dout_a, dout_c, result = torch.empty((M, N, 2), **kw), torch.empty((M,), **kw), torch.empty((8,), **kw)
+        ws = torch.empty((capi.PPO_SUMS * ((M * N + 255) // 256),), **kw)
+        out, value = out.detach(), value.detach()
+        args.out, args.value = out.data_ptr(), value.data_ptr()
+        args.dout_actor, args.dout_critic, args.result, args.workspace = dout_a.data_ptr(), dout_c.data_ptr(), result.data_ptr(), ws.data_ptr()
+        cur = torch.cuda.current_stream(dev)
+        with torch.cuda.device(dev):  # on the env's stream after what torch's current stream holds, which then waits for it (ppo_head's discipline)
+            env.stream.wait_stream(cur)
+            rc = env.lib.ppo_head_1d(env.h, C.byref(args))
+            if rc != 0:
+                raise RuntimeError(f"sigmaenv_ppo_head_1d failed with code {rc}: {env.lib.last_error(env.h).decode()}")
+            cur.wait_stream(env.stream)
+        for t in (out, value, dout_a, dout_c, result, ws, *keep):
+            t.record_stream(env.stream)
+        ctx.save_for_backward(dout_a, dout_c)
+        ctx.mark_non_differentiable(result)
+        return (result[0] + result[1]) + result[2], result
+
+    @staticmethod
+    def backward(ctx, g, _):
+        dout_a, dout_c = ctx.saved_tensors
+        return None, None, None, dout_a * g, dout_c * g
+
+
+def priority_ppo_head(env, out: torch.Tensor, value: torch.Tensor, batch: dict, index: torch.Tensor, *, clip_epsilon: float, entropy_coeff: float,
+                      critic_coeff: float = 1.0, seed: int, counter: int):
+    """The clip-PPO loss of the priority module on one minibatch of frames (``sigmaenv_ppo_head_1d``; every formula: ``include/sigmaenv.h``) -- the reference's second
+    ``ClipPPOLoss`` (``sigmarl/modules/priority_module.py:93-126``): ``out [M, N, 2]`` = ``PriorityNet.apply(index=)`` (loc, raw scale of the 1-D TanhNormal on
+    [-1, 1]), ``value [M]`` = the priority critic's ``apply(index=)``.  ``batch`` holds the records read in place at the frames ``index [M]`` (int32 CUDA):
+    ``("info", "priority", "scores")`` and ``("info", "priority", "sample_log_prob")`` -- the ``scores`` / ``score_log_prob [T, B, N]`` records of
+    ``Actor.rollout(wrapper="prioritized", priority=PriorityNet)`` -- and ``advantage`` / ``value_target [T, B, N]``.  WHICH advantages: as the reference runs, the
+    priority loss module reads the keys ``advantage`` / ``value_target`` that ``priority_module.GAE`` wrote last, i.e. the PRIORITY critic's pair; this function reads
+    ``batch["advantage"]`` / ``batch["value_target"]`` and leaves the choice to whoever fills them.  ``(seed, counter)``: the key of the entropy sample's draw; the
+    draw id is the priority head's own (``DRAW_PRIORITY_ENTROPY``), so the same ``(seed, counter)`` as the base head's shares no draw with it.  Returns
+    ``(loss, info)`` as ``ppo_head`` does.  Enqueued on the env's stream, nothing waits."""
+    N = env.N
+    for t, what in ((out, "out"), (value, "value")):
+        if not isinstance(t, torch.Tensor) or not (t.is_cuda and t.dtype == torch.float32 and t.device == env.device):
+            raise TypeError(f"priority_ppo_head: {what} must be a float32 CUDA tensor on {env.device}")
+    if not (isinstance(index, torch.Tensor) and index.is_cuda and index.dtype == torch.int32 and index.dim() == 1 and index.is_contiguous() and index.device == env.device):
+        raise TypeError(f"priority_ppo_head: index must be a contiguous int32 CUDA tensor [M] on {env.device}")
+    M = index.numel()
+    if M < 1 or out.numel() != M * N * 2 or value.numel() != M:
+        raise ValueError(f"priority_ppo_head: out {list(out.shape)} / value {list(value.shape)} are not [M, {N}, 2] / [M] of the {M} indexed frames (M >= 1)")
+    sc = batch[("info", "priority", "scores")]
+    if not isinstance(sc, torch.Tensor) or sc.dim() != 3:
+        raise TypeError("priority_ppo_head: batch[('info', 'priority', 'scores')] must be [T, B, N]")
+    T, B = sc.shape[0], sc.shape[1]
+    recs = (check_record(sc, (T, B, N), "scores"), check_record(batch[("info", "priority", "sample_log_prob")], (T, B, N), "score log-probabilities"),
+            check_record(batch["advantage"], (T, B, N), "advantage"), check_record(batch["value_target"], (T, B, N), "value_target"))
+    if not 0.0 < float(clip_epsilon) < 1.0:
+        raise ValueError(f"clip_epsilon = {clip_epsilon} is not in (0, 1)")
+    a = capi.PpoHead1dArgs()
+    a.n_index, a.n_frames, a.index = M, T * B, index.data_ptr()
+    a.scores, a.score_log_prob, a.advantage, a.value_target = (t.data_ptr() for t in recs)
+    a.clip_epsilon, a.entropy_coeff, a.critic_coeff = float(clip_epsilon), float(entropy_coeff), float(critic_coeff)
+    a.seed, a.counter = int(seed) & 0xFFFFFFFFFFFFFFFF, int(counter) & 0xFFFFFFFFFFFFFFFF
+    loss, result = _PriorityPpoHeadFunction.apply(env, a, (index, *recs), out.reshape(M, N, 2).contiguous(), value.reshape(M).contiguous())
     return loss, {k: result[i] for i, k in enumerate(capi.PPO_RESULT)}
 
 
@@ -570,9 +698,11 @@ class PrioritizedBuffer:
         if T * B != self.len or B != env.B:
             raise ValueError(f"PrioritizedBuffer.refresh: the batch has {T} x {B} frames, the buffer holds {self.len} of an env of {env.B}")
         check_record(obs, (T, B, N, D), "observation")
+        base = batch.get(BASE_OBS)  # (prioritized action propagation: the critic reads the base observation, and the next rows padded)
+        pad = None if base is None else (D, check_record(base, (T, B, N, base.shape[-1]), "base_observation").shape[-1])
         with torch.no_grad():  # (the sampled index is in range by construction; an entry outside is read as zeros and ignored by the refresh)
-            sv = critic.apply(env, obs, index=index, check_index=False)
-            nv = critic.apply(env, slab, index=index, check_index=False)
+            sv = critic.apply(env, obs if base is None else base, index=index, check_index=False, pad=pad)
+            nv = critic.apply(env, slab, index=index, check_index=False, pad=pad)
         td = torch.empty((M,), dtype=torch.float32, device=env.device)
         a = capi.PrbRefreshArgs()
         a.n_index, a.index, a.state_value, a.next_state_value, a.slab, a.td_out = M, index.data_ptr(), sv.data_ptr(), nv.data_ptr(), slab.data_ptr(), td.data_ptr()
@@ -604,7 +734,7 @@ class PrioritizedBuffer:
 
 def update(env, actor, critic, actor_module, critic_module, optim, batch: dict, params=None, *, num_epochs: int | None = None, minibatch_size: int | None = None,
            clip_epsilon: float | None = None, entropy_coeff: float | None = None, max_grad_norm: float | None = None, critic_coeff: float = 1.0, seed: int = 0,
-           counter0: int = 0, generator: torch.Generator | None = None, buffer: PrioritizedBuffer | None = None, td_gamma: float = TD_GAMMA) -> list:
+           counter0: int = 0, generator: torch.Generator | None = None, buffer: PrioritizedBuffer | None = None, td_gamma: float = TD_GAMMA, priority=None) -> list:
     """``_train_epoch`` / ``_train_on_batch`` (``sigmarl/mappo_cavs.py:389-426``) on the batch ``collect`` returned: ``num_epochs x (frames // minibatch_size)``
     steps of ``Actor.apply`` / ``Critic.apply(index=)`` -> ``ppo_head`` -> ``loss.backward()`` -> ``clip_grad_norm_`` over both modules' parameters ->
     ``optim.step()`` -> ``optim.zero_grad()`` -> ``actor.load`` / ``critic.load``; every epoch draws a new ``minibatches`` permutation and uses its full chunks.
@@ -620,7 +750,18 @@ def update(env, actor, critic, actor_module, critic_module, optim, batch: dict, 
     On the device route there is still no host wait inside the loop.  What that rests on: ``Adam.step`` enqueues its three launches on the env's stream and leaves the
     networks in the exact mode, whose weight form is valid for every weight, and ``apply`` runs the exact chain whatever mode is in force -- so the next minibatch's
     forward and ``refresh``'s two critic passes, enqueued on the same stream behind the step, read the new weights without anyone having read the range word;
-    ``resolve`` (the one wait) only decides whether the split form may be used again, which the loop never asks.  Without ``buffer`` nothing changes."""
+    ``resolve`` (the one wait) only decides whether the split form may be used again, which the loop never asks.  Without ``buffer`` nothing changes.
+
+    Prioritized action propagation (a batch of ``collect(wrapper="prioritized")``: it holds ``("info", "base_observation")``): the base ``actor.apply`` reads that
+    record with width ``D + 2 K`` and the base critic with width ``N (D + 2 K)``; with ``buffer``, ``refresh`` reads the critic's next rows padded.  ``priority =
+    (priority_net, priority_critic, priority_module, priority_critic_module, priority_optim)`` trains the priority module as the reference does behind every base
+    optimiser step (``compute_losses_and_optimize``, ``sigmarl/mappo_cavs.py:428-429``, ``sigmarl/modules/priority_module.py:188-224``), on the same ``index``:
+    ``priority_net.apply(index=)`` -> ``priority_critic.apply(index=)`` on the priority observation (``batch["observation"]``) -> ``priority_ppo_head`` with the same
+    ``clip_epsilon`` / ``entropy_coeff`` / ``(seed, counter0 + k)`` (its draw id is its own) -> ``backward`` -> its OWN clip norm and optimiser:
+    ``priority_optim.step(max_grad_norm)`` with a ``learn.Adam`` over both priority networks, else ``clip_grad_norm_`` over the two priority modules ->
+    ``priority_optim.step()`` -> ``zero_grad()`` -> ``load``; then ``refresh``.  Both losses read ``batch["advantage"]`` / ``["value_target"]`` (``collect``: the
+    priority critic's pair).  ``infos[k]["priority"]`` is the priority head's ``info``.  On the device route there is no host wait inside the loop; both optimisers
+    get one ``resolve()`` at the end."""
     p = params if params is not None else getattr(env, "parameters", None)
 
     def pick(v, name, attr=None):
@@ -644,13 +785,25 @@ def update(env, actor, critic, actor_module, critic_module, optim, batch: dict, 
     low, high = actor._keep[-2], actor._keep[-1]
     pars = list(actor_module.parameters()) + list(critic_module.parameters())
     device_route = isinstance(optim, Adam)
+    base = batch.get(BASE_OBS)
+    Dc = D if base is None else check_record(base, (T, B, N, base.shape[-1]), "base_observation").shape[-1]
+    pad = None if base is None else (D, Dc)
+    if priority is not None:
+        try:
+            pnet, pcritic, pmodule, pcritic_module, poptim = priority
+        except (TypeError, ValueError):
+            raise TypeError("update(): priority = (priority_net, priority_critic, priority_module, priority_critic_module, priority_optim)") from None
+        if base is None or PRIORITY + ("scores",) not in batch:
+            raise ValueError("update(): priority= needs a batch of collect(wrapper='prioritized', priority=PriorityNet, priority_critic=...)")
+        ppars = list(pmodule.parameters()) + list(pcritic_module.parameters())
+        pdevice = isinstance(poptim, Adam)
     infos, k = [], 0
     for _ in range(num_epochs):
         for index in ([None] * (frames // mb) if buffer is not None else minibatches(frames, mb, generator, env.device)[: frames // mb]):
             if buffer is not None:
                 index, weight = buffer.sample(mb, seed, counter0 + k)
-            out = actor.apply(env, rows=(obs, 0, N, D, frames, N * D), index=index, check_index=False)  # (a permutation's and a sample's entries are in range)
-            value = critic.apply(env, obs, index=index, check_index=False)
+            out = actor.apply(env, rows=(obs if base is None else base, 0, N, Dc, frames, N * Dc), index=index, check_index=False)  # (a permutation's and a sample's entries are in range)
+            value = critic.apply(env, obs if base is None else base, index=index, check_index=False, pad=pad)
             loss, info = ppo_head(env, out, value, batch, index, low=low, high=high, clip_epsilon=clip_epsilon, entropy_coeff=entropy_coeff, critic_coeff=critic_coeff,
                                   seed=seed, counter=counter0 + k)
             loss.backward()
@@ -662,12 +815,28 @@ def update(env, actor, critic, actor_module, critic_module, optim, batch: dict, 
                 optim.zero_grad()
                 actor.load(env, actor_module)
                 critic.load(env, critic_module)
+            if priority is not None:
+                pout = pnet.apply(env, rows=(obs, 0, N, D, frames, N * D), index=index, check_index=False)
+                pvalue = pcritic.apply(env, obs, index=index, check_index=False)
+                ploss, info["priority"] = priority_ppo_head(env, pout, pvalue, batch, index, clip_epsilon=clip_epsilon, entropy_coeff=entropy_coeff, critic_coeff=critic_coeff,
+                                                            seed=seed, counter=counter0 + k)
+                ploss.backward()
+                if pdevice:
+                    poptim.step(max_grad_norm)
+                else:
+                    torch.nn.utils.clip_grad_norm_(ppars, max_grad_norm)
+                    poptim.step()
+                    poptim.zero_grad()
+                    pnet.load(env, pmodule)
+                    pcritic.load(env, pcritic_module)
             if buffer is not None:
                 info["_weight"], info["td_error"] = weight, buffer.refresh(critic, batch, index, td_gamma)
             infos.append(info)
             k += 1
     if device_route and k:
         optim.resolve()
+    if priority is not None and pdevice and k:
+        poptim.resolve()
     return infos
 
 
@@ -703,7 +872,7 @@ def steps_per_iteration(params, frames: int, num_epochs: int | None = None, mini
 
 def train_iteration(env, actor, critic, actor_module, critic_module, optim, returns: EpisodeReturns, params=None, *, i_iter: int = 1, buffer: PrioritizedBuffer | None = None,
                     frames_per_batch: int | None = None, seed: int = 0, counter0: int = 0, generator: torch.Generator | None = None, td_gamma: float = TD_GAMMA,
-                    rollout_kw: dict | None = None, **update_kw):
+                    rollout_kw: dict | None = None, priority=None, **update_kw):
     """Iteration ``i_iter`` (1-based) of the reference's training loop (``sigmarl/mappo_cavs.py:126-150``) from its parts:
       1. ``collect`` with ``T = frames_per_batch // env.B`` steps (``frames_per_batch``: ``params``' unless given; not a multiple of ``env.B``: ``ValueError``) and
          ``returns``: the rollout, the critic's values, GAE, the TD-error priorities, the episode returns;
@@ -713,7 +882,14 @@ def train_iteration(env, actor, critic, actor_module, critic_module, optim, retu
       5. the learning rate of the NEXT iteration, ``lr_at(params, i_iter + 1)``, into ``optim`` (``set_lr``).
     The counters, stated once: with ``j = i_iter - 1`` the rollout's steps are keyed ``(seed, counter0 + j * T + t)`` and the update's steps ``(seed, counter0 + j *
     steps_per_iteration + k)`` -- within a draw id of ``sigmaenv_dist.h`` no ``(seed, counter)`` is used twice across iterations, and the rollout's draw ids, the
-    entropy sample's and the replay sampler's are different entries of that table, so the two counter ranges may overlap.  Returns ``(batch, infos, stats)``."""
+    entropy sample's and the replay sampler's are different entries of that table, so the two counter ranges may overlap.  Returns ``(batch, infos, stats)``.
+
+    ``priority = (priority_net, priority_critic, priority_module, priority_critic_module, priority_optim)`` (``Parameters.is_using_prioritized_marl`` with
+    ``prioritization_method="marl"``; ``rollout_kw`` then holds ``wrapper="prioritized"``): ``collect`` gets ``priority=priority_net`` and ``priority_critic=``, ``update``
+    the tuple.  The priority head's entropy draw of step ``k`` is keyed with the base head's ``(seed, counter)`` under ``DRAW_PRIORITY_ENTROPY``, a further entry of the
+    table: the statement above holds for it as it does for the others.  The learning rate of the next iteration goes into ``optim`` ALONE, as in the reference:
+    ``_update_learning_rate`` walks ``optimization_module.optim.param_groups`` and nothing else, so the priority optimiser trains at the ``lr`` it was built with
+    (``sigmarl/modules/priority_module.py:122``) in every iteration."""
     p = params if params is not None else getattr(env, "parameters", None)
     if p is None:
         raise ValueError("train_iteration(): a Parameters (frames_per_batch, the discounts, the schedule)")
@@ -727,12 +903,15 @@ def train_iteration(env, actor, critic, actor_module, critic_module, optim, retu
         raise ValueError("train_iteration(): Parameters.is_prb needs a PrioritizedBuffer (buffer=)")
     T = fpb // env.B
     steps = steps_per_iteration(p, fpb, update_kw.get("num_epochs"), update_kw.get("minibatch_size"))
-    batch = collect(env, actor, critic, T, params=p, td_gamma=td_gamma, td_error=True, seed=seed, counter0=counter0 + (k - 1) * T, returns=returns, **(rollout_kw or {}))
+    rkw = dict(rollout_kw or {})
+    if priority is not None:
+        rkw.update(priority=priority[0], priority_critic=priority[1])
+    batch = collect(env, actor, critic, T, params=p, td_gamma=td_gamma, td_error=True, seed=seed, counter0=counter0 + (k - 1) * T, returns=returns, **rkw)
     stats = batch["episode_stats"]
     if buffer is not None:
         buffer.extend(batch["td_error"])
     infos = update(env, actor, critic, actor_module, critic_module, optim, batch, params=p, seed=seed, counter0=counter0 + (k - 1) * steps, generator=generator,
-                   buffer=buffer, td_gamma=td_gamma, **update_kw)
+                   buffer=buffer, td_gamma=td_gamma, priority=priority, **update_kw)
     set_lr(optim, lr_at(p, k + 1))
     return batch, infos, stats
 
@@ -745,7 +924,8 @@ def train(env, actor, critic, actor_module, critic_module, optim, params=None, *
     ``episode_reward_mean_list``; ``params.episode_reward_mean_current = mean``; ``improved = mean > params.episode_reward_intermediate`` (compared after the
     rounding; never true for a NaN); if improved ``params.episode_reward_intermediate = mean``, else ``params.episode_reward_mean_current`` falls back to the best
     so far, as the reference's does.  Then ``on_iteration(i_iter, batch, infos, mean, improved)`` if given: the place where a caller saves models -- this loop writes
-    no files.  The optimiser starts from whatever ``lr`` it holds (``params.lr`` in the reference).  Returns ``episode_reward_mean_list``."""
+    no files.  The optimiser starts from whatever ``lr`` it holds (``params.lr`` in the reference).  Returns ``episode_reward_mean_list``.  ``iteration_kw`` may hold
+    ``rollout_kw=dict(wrapper="prioritized")`` and ``priority=(...)`` (``train_iteration``): the ``is_using_prioritized_marl`` / ``"marl"`` configuration end to end."""
     p = params if params is not None else getattr(env, "parameters", None)
     if p is None:
         raise ValueError("train(): a Parameters")
