@@ -327,12 +327,16 @@ __device__ inline void agent_scan_full(const DevMap& m, const sigmaenv_config_t&
 // ---------------------------------------------------------------------------------------------------------------------
 // B2, pruned: the same (min, first argmin) / collision results as the full scan, but only the polyline chunks that can matter
 // are evaluated.  Exactness argument (DESIGN.md "Pruned scan"): a run of SIGMAENV_CHUNK consecutive segments is skipped only
-// if the distance from the agent's centre to the run's bounding box exceeds T, where T bounds (with a 1e-4 m margin, >> fp32
+// if the distance from the agent's centre c to the run's bounding box exceeds T, where T bounds (with a 1e-4 m margin, >> fp32
 // error)
-//   * the distance of every query point to the segment that was closest last step (an upper bound of its minimum), and
+//   * for every query point q (the centre, and for a boundary the four corners the scan will use): u(q) + |q - c|, where u(q) is
+//     q's OWN distance to the segment s* that was closest last step.  The query's minimum is at most u(q), so a segment that can
+//     equal or beat it has a point within u(q) of q, hence within u(q) + |q - c| of the centre, and so has its run's box; and
 //   * the rectangle's circumradius (a segment farther than that cannot intersect an edge).
 // So every segment whose computed distance can equal or beat the running minimum, and every segment that can hit the
-// rectangle, is still evaluated with the very same arithmetic; ties still resolve to the lowest index.
+// rectangle, is still evaluated with the very same arithmetic; ties still resolve to the lowest index (a tied segment is as
+// near as the winner, so inside the bound as well).  The agent whose corner queries are last step's vertices needs no rule of
+// its own: its real query points enter like any other's.
 // ---------------------------------------------------------------------------------------------------------------------
 // exact radius of the corner-query points around the centre (used for agent 0, whose query points are last step's vertices)
 __device__ __forceinline__ float query_radius(const float* qv, float cgx, float cgy) {
@@ -410,31 +414,39 @@ __device__ __forceinline__ void mask_stage2(const DevMap& m, const Smem& s, Mask
   }
   const float px = s.st[sl * 8], py = s.st[sl * 8 + 1];
   mt.px = px; mt.py = py;
-  // pruning threshold T (see the exactness argument above): distance to last step's closest segment, plus (boundaries) twice the
-  // radius of the query points around the centre -- exact for the agent whose corners are stale -- and at least the circumradius
-  // when the rectangle is also tested for collision
+  // pruning threshold T (see the exactness argument above): the centre's distance dg to last step's closest segment; for a boundary also, per corner query
+  // point q_j, its own distance u_j to that segment plus its distance r_j from the centre; and at least the circumradius when the rectangle is also tested
+  // for collision
   const float MARGIN = 1e-4f;
   const float glx = mt.bx - mt.ax, gly = mt.by - mt.ay;
+  const float rl2 = __builtin_amdgcn_rcpf(glx * glx + gly * gly);
   // dg only has to be an UPPER bound of the distance to that segment: the distance to ANY point of the segment is one, so the projection parameter may come
   // from the approximate reciprocal and the root from the 1-ulp instruction (their rounding is far inside MARGIN) -- no IEEE division / square-root sequences
   float dg;
   {
     const float vx = px - mt.ax, vy = py - mt.ay;
-    const float tq = clampf((vx * glx + vy * gly) * __builtin_amdgcn_rcpf(glx * glx + gly * gly), 0.0f, 1.0f);  // (a zero-length segment: NaN -> 0)
+    const float tq = clampf((vx * glx + vy * gly) * rl2, 0.0f, 1.0f);  // (a zero-length segment: NaN -> 0)
     const float ex = (mt.ax + glx * tq) - px, ey = (mt.ay + gly * tq) - py;
     dg = __builtin_amdgcn_sqrtf(fmaf(ey, ey, ex * ex)) * 1.000001f + 1e-6f;
   }
   float T = dg;
   if (pl != 0) {
+    // the corner query points the scan will use: last step's vertices for the agent whose corners are stale, else the new ones
     const bool stale = stale_first && (sl % N == 0);  // (only evaluated for the step kernel: N is a kernel-uniform divisor there)
-    // the agent whose corner queries are last step's vertices: they lie within the circumradius of last step's position (s.thr, staged by phase A), i.e. within
-    // circumradius + |move| of the new centre -- a bound from one root instead of the exact maximum over the four corners (four roots)
-    float Rq = m.rect_radius;
-    if (stale) {
-      const float mx = px - s.thr[sl * 3], my = py - s.thr[sl * 3 + 1];
-      Rq = (m.rect_radius + __builtin_amdgcn_sqrtf(fmaf(my, my, mx * mx))) * 1.000001f + 1e-6f;
+    const float* qv = stale ? (s.vold + sl * 10) : (s.vnew + sl * 10);
+    // u_j + r_j, each an UPPER bound by the same argument as dg (any point of the segment; approximate reciprocal, 1-ulp roots, one inflation of the largest sum).
+    // (A NaN corner drops out of the maximum; it comes with a NaN centre, for which box_within keeps every box whatever T is.)
+    float w = 0.0f;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const float qx = qv[2 * j], qy = qv[2 * j + 1];
+      const float vx = qx - mt.ax, vy = qy - mt.ay;
+      const float tq = clampf((vx * glx + vy * gly) * rl2, 0.0f, 1.0f);
+      const float ex = (mt.ax + glx * tq) - qx, ey = (mt.ay + gly * tq) - qy;
+      const float rx = qx - px, ry = qy - py;
+      w = fmaxf(w, __builtin_amdgcn_sqrtf(fmaf(ey, ey, ex * ex)) + __builtin_amdgcn_sqrtf(fmaf(ry, ry, rx * rx)));
     }
-    T = fmaxf(T + 2.0f * Rq, COLLIDE ? m.rect_radius : 0.0f);
+    T = fmaxf(fmaxf(T, w * 1.000001f + 1e-6f), COLLIDE ? m.rect_radius : 0.0f);
   }
   T += MARGIN;
   mt.T2 = T * T;

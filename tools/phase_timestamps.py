@@ -27,13 +27,19 @@ def stamp_rows():
 # 20 single ones -- the stamps are then those of its last step, the accumulated words those of all its steps
 T = int(os.environ.get("T", 1))
 edge_steps = []  # per launch: (list entries, overflowed tile-steps) of every tile
+item_steps = []  # per single-step launch: the work-list items of every tile (one value per tile-step)
 prev = stamp_rows()[:, 8:10] >> np.uint64(32)
+prev_items = stamp_rows()[:, 8] & np.uint64(0xFFFFFFFF)
 for t in range(20):
     env.step_autoreset(acts, seed=1, counter=t, path_first=pf, path_count=pc)
     if T == 1:
-        cur = stamp_rows()[:, 8:10] >> np.uint64(32)
+        rows_t = stamp_rows()
+        cur = rows_t[:, 8:10] >> np.uint64(32)
         edge_steps.append((cur - prev).astype(np.int64))
         prev = cur
+        cur_items = rows_t[:, 8] & np.uint64(0xFFFFFFFF)
+        item_steps.append((cur_items - prev_items).astype(np.int64))
+        prev_items = cur_items
 n_steps = 20
 if T > 1:
     prev = stamp_rows()[:, 8:10] >> np.uint64(32)
@@ -57,6 +63,10 @@ print("tile total mean", (ts[:, 7] - ts[:, 0]).mean())
 if stats[:, 1].sum():  # accumulated over the launches above
     per = stats[:, 0] / np.maximum(stats[:, 1], 1)
     print("scan work list: items per tile-step mean %.1f p10 %.0f p50 %.0f p90 %.0f max %.0f; rounds per step %.2f" % (per.mean(), np.percentile(per, 10), np.percentile(per, 50), np.percentile(per, 90), per.max(), stats[:, 1].sum() / (float(n_steps) * len(stats))))
+if item_steps:  # T = 1: the distribution over tile-steps (above: over the tiles' means), and the S2 passes of 64 lanes it takes (the third one starts at 129 items)
+    it = np.concatenate(item_steps)
+    print("scan work list per tile-step: items mean %.1f p10 %.0f p50 %.0f p90 %.0f max %.0f; tile-steps with more than 128 items %d of %d (%.2f %%), with more than 64 %d (%.2f %%)" % (
+        it.mean(), np.percentile(it, 10), np.percentile(it, 50), np.percentile(it, 90), it.max(), (it > 128).sum(), len(it), 100.0 * (it > 128).mean(), (it > 64).sum(), 100.0 * (it > 64).mean()))
 if edge_steps and sum(int(e[:, 0].sum()) for e in edge_steps):
     ent = np.concatenate([e[:, 0] for e in edge_steps]) / float(T)  # T = 1: one value per tile-step; T > 1: per tile, the mean over the launch's steps
     print("edge list (%s): entries per tile-step mean %.1f p50 %.0f p99 %.0f max %.0f; overflowed tile-steps %d of %d" % (
