@@ -625,6 +625,74 @@ typedef struct sigmaenv_episode_args {
 } sigmaenv_episode_args_t;
 int sigmaenv_episode_return(sigmaenv_t* h, const sigmaenv_episode_args_t* a);
 
+/* ---- the evaluation of a policy (sigmaenv_eval.inc; the arithmetic: sigmaenv_eval.h) ----------------------------------------------------------
+ * What the reference reduces a testing rollout to (sigmarl/evaluation_base.py:184-217, _evaluate_model_i): four numbers per env -- the average speed
+ * velocities.norm(dim=-1).mean(dim=(-2, -1)) (:205-207), the agent-agent collision rate is_collision_with_agents.squeeze(-1).any(dim=-1).sum(dim=-1) / num_steps
+ * (:208-210), the agent-lanelet collision rate (:211-214) and the mean centre-line deviation distance_ref.squeeze(-1).mean(dim=(-2, -1)) (:215-217) -- accumulated
+ * frame by frame from the per-step output buffers, on the device.  A rollout record row holds none of the inputs, and the fused step + auto-reset launch has
+ * cleared the collision flags by the time a call returns: an evaluator is therefore either handed its frames (sigmaenv_eval_accumulate) or attached to the
+ * handle's rollouts (sigmaenv_eval_attach), which then run every step as sigmaenv_step -> sigmaenv_eval_accumulate -> sigmaenv_auto_reset.
+ *
+ * A frame of env b: SIGMAENV_BUF_STATE[b,i,5:7] = (vx, vy) (info["vel"]); SIGMAENV_BUF_DIST_REF[b,i] (info["distance_ref"]); SIGMAENV_BUF_COL_AGENTS[b,i,j];
+ * byte 0 of SIGMAENV_BUF_COL_FLAGS[b,i,.] (with_lanelets; bytes 1 .. 3 are never counted) -- as the buffers stand when the launch runs, no other source.
+ * Element contract: n_i = sqrtf(vx * vx + vy * vy), two products, one addition, one correctly rounded square root, each fp32, no contraction;
+ * aa = OR over i, j of col_agents[b,i,j]; al = OR over i of col_flags[b,i,0].
+ * Reduction contract: the frame's sums of (double)n_i and of (double)dist_ref_i over the agents in fp64 in a butterfly over G = the smallest power of two >= N
+ * lanes -- lane i holds agent i's term, lanes N .. G-1 hold +0.0, v += v[lane ^ m] for m = G/2, .., 1 --; per env sum_speed = sum_speed + frame_sum and sum_dref
+ * likewise, ONE fp64 addition per frame in frame order; n_aa += aa, n_al += al, frames += 1 in uint32.  No atomics: a function of the inputs and (N, B, frames)
+ * alone, whatever the scheduling or the launch shape.
+ * sigmaenv_eval_finish: metrics f32 [B, 4], with F = frames:  [0] = (float)(sum_speed / (double)(F * N));  [1] = (float)n_aa / (float)F;  [2] = (float)n_al / (float)F;
+ * [3] = (float)(sum_dref / (double)(F * N)).  F * N < 2^24 always holds (below), so both rates are one fp32 division of two exactly represented integers: bit for bit
+ * the count / num_steps of :208-214.  F = 0: NaN in all four.  counts (optional) u32 [B, 3] = n_aa, n_al, frames.  The accumulators are left as they are.
+ *
+ * sigmaenv_eval_create: an evaluator of THIS handle (its B and N); args->trace_frames > 0 also allocates a device trace f32 [trace_frames, B, N, 8] with the rows
+ *   x, y, vx, vy, dist_ref, n_i, col_agents-any-j (0/1), col_lanelet (0/1) -- the out_td entries :191-199 reads -- of the first trace_frames frames after a reset;
+ *   later frames are accumulated but not traced.  args->debug_frames0 is a test hook and zero otherwise: the frame count every reset starts from (sums and counts
+ *   start from zero all the same).  Allocates: do not call inside a stream capture.
+ * sigmaenv_eval_reset: zero accumulators (and trace), enqueued on the handle's stream.  sigmaenv_eval_create ends with one.
+ * sigmaenv_eval_accumulate: ONE launch, one frame for every env.  src NULL: the handle's buffers; otherwise each non-null pointer of src replaces the handle's buffer
+ *   of that name, in the handle's own layout ([B,N,8] f32, [B,N] f32, [B,N,N] u8, [B,N,4] u8), 4-byte aligned.  Takes no position on WHICH moments are frames.
+ * sigmaenv_eval_finish: ONE launch.  Nothing above waits on the host.
+ * sigmaenv_eval_attach(h, ev) / (h, NULL): while an evaluator is attached, every step of sigmaenv_rollout, sigmaenv_rollout_f32 and sigmaenv_rollout_f32_ex (every
+ *   wrapper, and the CBF chain: the step then takes the chain's own action, the QP's safe action where the chain uses one) runs as sigmaenv_step ->
+ *   sigmaenv_eval_accumulate -> sigmaenv_auto_reset with the record row block, the (seed, counter0 + t) keys and the path range of the fused launch it replaces: end
+ *   state, slab, log-probabilities, action record and observation record are the fused rollout's, bit for bit (sigmaenv_step_autoreset promises it).  The frame of
+ *   step t is the step's outcome BEFORE the re-placements of testing mode (road_traffic.py:1435-1447) and reset_collisions clear it.  With nothing attached the
+ *   rollouts are unchanged.  Direct calls of sigmaenv_step_autoreset, sigmaenv_step_autoreset_many and sigmaenv_step_autoreset_n are NOT affected by an attachment.
+ * sigmaenv_eval_get: the one call that waits (it synchronises the handle's stream): copies an item to HOST memory, for inspection -- SIGMAENV_EVAL_SUM_SPEED /
+ *   _SUM_DREF f64 [B]; _N_AA / _N_AL / _FRAMES u32 [B]; _TRACE f32 [trace_frames, B, N, 8]; _FRAMES_HOST one u64, the frames since the last reset as the host counts
+ *   them (no wait).
+ * sigmaenv_eval_destroy: waits for the handle's stream, detaches, frees.  An evaluator whose handle was destroyed first can only be destroyed.
+ * Refused with SIGMAENV_EINVAL and sigmaenv_last_error set, before any launch: a null handle (no message), a null evaluator, an evaluator of another handle, an
+ * override that is not 4-byte aligned, a frame with (frames + 1) * N >= 2^24 (an attached rollout: (frames + n_steps) * N, before its first launch). */
+typedef struct sigmaenv_eval sigmaenv_eval_t;
+typedef struct sigmaenv_eval_args {
+  int32_t trace_frames;            /* 0: no trace */
+  int32_t debug_frames0;           /* test hook, zero otherwise: the frame count a reset starts from */
+  int32_t reserved[6];             /* zero */
+} sigmaenv_eval_args_t;
+typedef struct sigmaenv_eval_src {
+  const float* state;              /* optional device f32 [B, N, 8] */
+  const float* dist_ref;           /* optional device f32 [B, N] */
+  const uint8_t* col_agents;       /* optional device u8 [B, N, N] */
+  const uint8_t* col_flags;        /* optional device u8 [B, N, 4] */
+  int32_t reserved[4];             /* zero */
+} sigmaenv_eval_src_t;
+#define SIGMAENV_EVAL_SUM_SPEED 0
+#define SIGMAENV_EVAL_SUM_DREF 1
+#define SIGMAENV_EVAL_N_AA 2
+#define SIGMAENV_EVAL_N_AL 3
+#define SIGMAENV_EVAL_FRAMES 4
+#define SIGMAENV_EVAL_TRACE 5
+#define SIGMAENV_EVAL_FRAMES_HOST 6
+int sigmaenv_eval_create(sigmaenv_t* h, const sigmaenv_eval_args_t* args, sigmaenv_eval_t** out);
+void sigmaenv_eval_destroy(sigmaenv_eval_t* ev);
+int sigmaenv_eval_reset(sigmaenv_t* h, sigmaenv_eval_t* ev);
+int sigmaenv_eval_accumulate(sigmaenv_t* h, sigmaenv_eval_t* ev, const sigmaenv_eval_src_t* src);
+int sigmaenv_eval_finish(sigmaenv_t* h, sigmaenv_eval_t* ev, float* metrics, uint32_t* counts);
+int sigmaenv_eval_attach(sigmaenv_t* h, sigmaenv_eval_t* ev);
+int sigmaenv_eval_get(sigmaenv_t* h, sigmaenv_eval_t* ev, int32_t what, void* host_out);
+
 /* ---- the clip-PPO loss head of a minibatch update (sigmaenv_ppo.inc) ---------------------------------------------------------------------
  * sigmaenv_ppo_head: torchrl's ClipPPOLoss as sigmarl/modules/optimization_module.py:44-66 configures it (clip_epsilon, entropy_coeff = entropy_eps,
  * normalize_advantage = False, the default smooth-L1 critic loss, samples_mc_entropy = 1) for one minibatch of frames (sigmarl/mappo_cavs.py:389-407, _train_epoch /

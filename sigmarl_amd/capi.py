@@ -117,6 +117,25 @@ EPR_LANES, EPR_MAX_FRAMES = 256, 1 << 24  # sigmaenv_episode.h
 EPISODE_RESULT = ("episode_reward_mean", "episode_reward_sum", "episodes_done")  # result[0 .. 2]
 
 
+class EvalArgs(C.Structure):
+    """``sigmaenv_eval_args_t`` (sigmaenv_eval_create): the trace's capacity in frames; ``debug_frames0`` is a test hook (the frame count a reset starts from)."""
+
+    _fields_ = [("trace_frames", C.c_int32), ("debug_frames0", C.c_int32), ("reserved", C.c_int32 * 6)]
+
+
+class EvalSrc(C.Structure):
+    """``sigmaenv_eval_src_t`` (sigmaenv_eval_accumulate): optional device pointers that replace the handle's buffers of the same name, in the handle's layouts."""
+
+    _fields_ = [("state", C.c_void_p), ("dist_ref", C.c_void_p), ("col_agents", C.c_void_p), ("col_flags", C.c_void_p), ("reserved", C.c_int32 * 4)]
+
+
+EVAL_SUM_SPEED, EVAL_SUM_DREF, EVAL_N_AA, EVAL_N_AL, EVAL_FRAMES, EVAL_TRACE, EVAL_FRAMES_HOST = range(7)  # SIGMAENV_EVAL_*: what sigmaenv_eval_get copies
+EVL_MAX_TERMS, EVL_TRACE_COLS = 1 << 24, 8  # sigmaenv_eval.h
+EVAL_METRICS = ("average_speed", "collision_rate_with_agents", "collision_rate_with_lanelets", "distance_ref_average")  # metrics[:, 0 .. 3]: evaluation_base.py:205-217
+EVAL_COUNTS = ("n_collision_frames_with_agents", "n_collision_frames_with_lanelets", "frames")  # counts[:, 0 .. 2]
+EVAL_TRACE_FIELDS = ("x", "y", "vx", "vy", "distance_ref", "speed", "is_collision_with_agents", "is_collision_with_lanelets")  # a trace row
+
+
 class PpoHeadArgs(C.Structure):
     """``sigmaenv_ppo_head_args_t`` (sigmaenv_ppo_head): a minibatch's network outputs, the learner's records, the ``dout`` tensors and the loss terms."""
 
@@ -333,6 +352,13 @@ _PRODUCT_ONLY = {
     "gae": (C.c_int, [C.c_void_p, C.POINTER(GaeArgs)]),
     "episode_return": (C.c_int, [C.c_void_p, C.POINTER(EpisodeArgs)]),
     "launch_shape": (C.c_int, [C.c_void_p, C.POINTER(LaunchShape)]),
+    "eval_create": (C.c_int, [C.c_void_p, C.POINTER(EvalArgs), C.POINTER(C.c_void_p)]),
+    "eval_destroy": (None, [C.c_void_p]),
+    "eval_reset": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "eval_accumulate": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(EvalSrc)]),
+    "eval_finish": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "eval_attach": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "eval_get": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
 }
 
 

@@ -1768,6 +1768,7 @@ __global__ void __launch_bounds__(512) sigmaenv_auto_reset_kernel(sigmaenv_confi
 // =====================================================================================================================
 // host side: the C-ABI
 // =====================================================================================================================
+struct sigmaenv_eval;  // sigmaenv_eval.inc
 struct sigmaenv {
   sigmaenv_config_t cfg;
   int device = 0;
@@ -1822,6 +1823,8 @@ struct sigmaenv {
   bool cbf_groups_valid = false;
   void* wrap_ws = nullptr;        // workspace of the rollout wrappers (sigmaenv_wrappers.inc), grown on demand
   size_t wrap_ws_bytes = 0;
+  sigmaenv_eval* eval_attached = nullptr;  // sigmaenv_eval_attach: the rollouts step as step -> accumulate -> auto_reset while set (sigmaenv_eval.inc)
+  std::vector<sigmaenv_eval*> evals;       // the evaluators created on this handle (they outlive it only as orphans: sigmaenv_destroy)
   std::string err;
 };
 
@@ -1893,10 +1896,13 @@ extern "C" int sigmaenv_obs_dim_full(int32_t n_agents, int32_t n_nearing, int32_
 
 extern "C" const char* sigmaenv_last_error(const sigmaenv_t* h) { return h ? h->err.c_str() : "null handle"; }
 
+static void eval_orphan(sigmaenv* h);  // sigmaenv_eval.inc: the handle's evaluators lose their owner
+
 extern "C" void sigmaenv_destroy(sigmaenv_t* h) {
   if (!h) return;
   (void)hipSetDevice(h->device);
   (void)hipStreamSynchronize(h->stream);
+  eval_orphan(h);
   for (void* p : h->allocs) (void)hipFree(p);
   for (auto& tm : h->timers)
     for (auto& ev : tm.pool) { (void)hipEventDestroy(ev.first); (void)hipEventDestroy(ev.second); }
@@ -2499,7 +2505,13 @@ extern "C" int sigmaenv_cbf_qp(sigmaenv_t* h, const float* actions, float* actio
 // rew_method asks for one (the margin rewards, or the QP into h->cbf_safe), then the fused step l on the action the rule selects -- the grouped update ALWAYS
 // replaces the action by the safe one (cbf_qp.py:2211-2222), the centralized one only with is_apply_cbf_action.  A handle without sigmaenv_cbf_attach steps without
 // a CBF launch: sigmaenv_rollout* tolerate it; sigmaenv_step_autoreset_n refuses such a handle before it gets here.
-static int launch_cbf_then_step(sigmaenv* h, StepLaunch l) {
+//
+// for_rollout (sigmaenv_rollout*: rollout_loop) with an evaluator attached (sigmaenv_eval_attach): the fused launch is taken apart into sigmaenv_step ->
+// sigmaenv_eval_accumulate -> sigmaenv_auto_reset -- the same action, record target and (seed, counter) -- so that the evaluator sees the step's outcome before the
+// re-placements clear it; the header promises the same end state and record as the fused launch, bit for bit.  Without an attachment, and for every other caller,
+// nothing changes.
+static int eval_accumulate_impl(sigmaenv* h, sigmaenv_eval* ev, const sigmaenv_eval_src_t* src);  // sigmaenv_eval.inc
+static int launch_cbf_then_step(sigmaenv* h, StepLaunch l, bool for_rollout = false) {
   if (!h || !l.actions) return SIGMAENV_EINVAL;
   if ((h->cfg.rew_flags & SIGMAENV_REW_CBF) && h->cbf_seg4) {
     const int rc = sigmaenv_cbf_rewards(h, l.actions, nullptr);
@@ -2508,6 +2520,13 @@ static int launch_cbf_then_step(sigmaenv* h, StepLaunch l) {
     const int rc = sigmaenv_cbf_qp(h, l.actions, (float*)h->cbf_safe, nullptr, nullptr);
     if (rc) return rc;
     if (h->cbf_cfg.is_apply_cbf_action || h->cbf_cfg.is_grouping) l.actions = (const float*)h->cbf_safe;
+  }
+  if (for_rollout && h->eval_attached) {
+    int rc = launch_step(h, {l.actions, l.slab, 0, 0, 0, 0});  // sigmaenv_step
+    if (rc) return rc;
+    rc = eval_accumulate_impl(h, h->eval_attached, nullptr);
+    if (rc) return rc;
+    return l.path_count != 0 ? sigmaenv_auto_reset(h, l.seed, l.counter, l.path_first, l.path_count) : SIGMAENV_OK;
   }
   return launch_step(h, l);
 }
@@ -2684,6 +2703,8 @@ extern "C" int sigmaenv_trig_selftest(sigmaenv_t* h, int32_t kind, int32_t n, co
 #include "sigmaenv_learn.inc"
 #include "sigmaenv_episode.h"
 #include "sigmaenv_episode.inc"
+#include "sigmaenv_eval.h"
+#include "sigmaenv_eval.inc"
 #include "sigmaenv_ppo.inc"
 #include "sigmaenv_prb.h"
 #include "sigmaenv_prb.inc"

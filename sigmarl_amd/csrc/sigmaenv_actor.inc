@@ -255,6 +255,7 @@ extern "C" int sigmaenv_actor_forward(sigmaenv_t* h, sigmaenv_actor* a, const fl
 // slab_base (optional) device f32 [T, B, W]: row block t receives the record of step t; logp_base (optional) device f32 [T, B, N].
 // the loop shared by sigmaenv_rollout (bf16 actor) and sigmaenv_rollout_f32 (the reference's fp32 actor): policy(t) enqueues the actor forward
 // of step t writing the actions (and log-probabilities) to the given pointers
+static int eval_check_frames(sigmaenv* h, const sigmaenv_eval* ev, uint64_t more, const char* what);  // sigmaenv_eval.inc
 template <class Policy>
 static int rollout_loop(sigmaenv_t* h, Policy policy, int32_t n_steps, float* actions_buf, float* slab_base, float* logp_base, float* actions_rec, uint64_t seed,
                         uint64_t counter0, int32_t path_first, int32_t path_count) {
@@ -262,6 +263,10 @@ static int rollout_loop(sigmaenv_t* h, Policy policy, int32_t n_steps, float* ac
   if (path_count != 0 && !paths_ok(h, path_first, path_count)) { h->err = "rollout: path range outside the table (or no scenario lists set)"; return SIGMAENV_EINVAL; }
   const size_t W = (size_t)h->N * (h->D + 1) + 1, BN = (size_t)h->B * h->N;
   const size_t slab_stride = h->rollout_slab_stride ? h->rollout_slab_stride : (size_t)h->B * W;
+  if (h->eval_attached) {  // an attached evaluator takes one frame per step: refused here, before the first launch, if it could not take them all
+    const int rc = eval_check_frames(h, h->eval_attached, (uint64_t)n_steps, "rollout (evaluator attached)");
+    if (rc) return rc;
+  }
   for (int t = 0; t < n_steps; ++t) {
     float* act = actions_rec ? actions_rec + (size_t)t * BN * 2 : actions_buf;
     int rc = policy(t, act, logp_base ? logp_base + (size_t)t * BN : nullptr);
@@ -272,7 +277,7 @@ static int rollout_loop(sigmaenv_t* h, Policy policy, int32_t n_steps, float* ac
                                h->stream));
     }
     // step t records into row block t of slab_base, or -- without one -- wherever the handle records (sigmaenv_set_slab); the handle's target is only read
-    rc = launch_cbf_then_step(h, {act, slab_base ? slab_base + (size_t)t * slab_stride : h->buf.slab, seed, counter0 + (uint64_t)t, path_first, path_count});
+    rc = launch_cbf_then_step(h, {act, slab_base ? slab_base + (size_t)t * slab_stride : h->buf.slab, seed, counter0 + (uint64_t)t, path_first, path_count}, true);
     if (rc) return rc;
   }
   return SIGMAENV_OK;

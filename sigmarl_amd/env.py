@@ -442,10 +442,11 @@ class SigmaEnv:
         self.reset(np.repeat(np.arange(B, dtype=np.int32), N), np.tile(np.arange(N, dtype=np.int32), B), ids.reshape(-1, 4), state8.reshape(-1, 8), True)
         self.observe()
 
-    def reset_random(self, seed: int = 0):
-        """Initial reset of every env through the device-side sampler (marks all envs done first)."""
+    def reset_random(self, seed: int = 0, counter: int | None = None):
+        """Initial reset of every env through the device-side sampler (marks all envs done first).  ``counter``: the counter of the draws (default: the env's
+        running reset counter, which then advances -- a second call places the agents elsewhere; a caller that names it gets the same placement again)."""
         self._views[capi.BUF_DONE].fill_(1)
-        self.auto_reset(seed=seed)
+        self.auto_reset(seed=seed, counter=counter)
 
 
 from .cbf import split_cbf_margins  # noqa: E402
