@@ -1553,13 +1553,19 @@ __global__ void __launch_bounds__(256) sigmaenv_start_table_kernel(sigmaenv_conf
 // (world_state_rt_sim.py:189-213, world_state_rt.py:422-529)
 // fin = false (a step of the in-kernel step loop that is not the launch's last one): only what the next step reads from LDS and the path row, which no
 // step writes back, are stored -- the last step of the launch writes every other HBM tensor of the agent, and phases S and C of the next step rewrite the
-// distances to the reference path and the boundaries (dref, dleft, dright, dbound) in LDS before anything reads them.
+// distances to the reference path and the boundaries (dref, dleft, dright, dbound) in LDS before anything reads them.  Those twelve floats are the row's tail
+// (START_HOT .. START_ROW, sigmaenv_device.h): fin = false does not load them.  One function for every caller -- the wavefront and the workgroup kernels, the
+// full-env restart (one lane per agent) and the per-agent requests (the winner lane).
 __device__ __forceinline__ void place_from_start_table(const DevMap& m, const DevBufs& g, const Smem& s, const Tile& t, int sl, int path, int pt,
                                                        float speed, int path_first, bool full_env, int scenario_id = 0, bool fin = true) {
   const float4* row4 = reinterpret_cast<const float4*>(m.start_table + ((size_t)path * m.P + pt) * START_ROW);
-  float r[START_ROW];
+  float r[START_ROW];  // (fin = false loads the row's head only: the tail's floats are read under `if (fin)` alone)
 #pragma unroll
-  for (int k = 0; k < START_ROW / 4; ++k) { float4 q = row4[k]; r[4 * k] = q.x; r[4 * k + 1] = q.y; r[4 * k + 2] = q.z; r[4 * k + 3] = q.w; }
+  for (int k = 0; k < START_HOT / 4; ++k) { float4 q = row4[k]; r[4 * k] = q.x; r[4 * k + 1] = q.y; r[4 * k + 2] = q.z; r[4 * k + 3] = q.w; }
+  if (fin) {
+#pragma unroll
+    for (int k = START_HOT / 4; k < START_ROW / 4; ++k) { float4 q = row4[k]; r[4 * k] = q.x; r[4 * k + 1] = q.y; r[4 * k + 2] = q.z; r[4 * k + 3] = q.w; }
+  }
   const size_t gi = t.a0 + sl;
   const float st[8] = {r[START_X], r[START_X + 1], r[START_X + 2], speed, 0.0f, speed * r[START_COSV], speed * r[START_COSV + 1], 0.0f};
   if (fin) {
@@ -1675,44 +1681,59 @@ __device__ __forceinline__ void auto_reset_tile(const sigmaenv_config_t& c, cons
     float cx = 0.f, cy = 0.f;
     if (pre.have && e == wave) { cpath = pre.path; cpt = pre.pt; cx = pre.x; cy = pre.y; }
     else if (has_c) reset_candidate(m, rd, b, ca, ctr, cpath, cpt, cx, cy);
-    bool cok = has_c;  // still feasible w.r.t. every agent accepted so far
-    int my_path = 0, my_pt = 3;  // lane i keeps agent i's accepted start (registers only: the common case touches LDS once, after the loop)
+    TS2(7);
+    // The accept loop, in registers.  Bit l of cokm: lane l's try is still feasible w.r.t. every agent accepted so far -- a wavefront-uniform word (scalar
+    // registers), and agent i's tries are the TR consecutive bits from i * TR (lane order = try order), so "first feasible" is a shift, a mask and a
+    // find-first-set.  An iteration of the common case is that, two broadcasts (the winner's x, y), the distance test on every lane and one ballot; lane i notes
+    // its agent's winner LANE (one select) and fetches path / point from it after the loop.  Nothing is stored to LDS: place_from_start_table writes the
+    // accepted position -- the same centre-line point, from the start table -- with the rest of the row.
+    unsigned long long cokm = __ballot(has_c);
+    const unsigned long long tr_mask = ~0ull >> (64 - TR);
+    int my_wl = -1;              // lane i: the lane whose precomputed try agent i accepted; -1: agent i took the rare branch, its start is in the four below
+    int my_path = 0, my_pt = 3;
+    float my_x = 0.f, my_y = 0.f;
     for (int i = 0; i < N; ++i) {
-      unsigned long long feas = __ballot(cok && ca == i);
-      int path, pt;
+      const unsigned long long feas = (cokm >> (i * TR)) & tr_mask;
       float px, py;
       if (feas) {  // first feasible among the precomputed tries (they are tries 0..TR-1 in lane order)
-        const int wl = __builtin_amdgcn_readfirstlane(__ffsll((long long)feas) - 1);
-        path = __builtin_amdgcn_readlane(cpath, wl); pt = __builtin_amdgcn_readlane(cpt, wl);
+        const int wl = i * TR + __ffsll((long long)feas) - 1;
         px = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(cx), wl)); py = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(cy), wl));
+        if (lane == i) my_wl = wl;
       } else {     // rare: tries TR..63 of this agent, all lanes at once; none feasible -> the last try (as the bounded loop would)
         int p2, q2;
         float x2, y2;
         reset_candidate(m, rd, b, i, lane, p2, q2, x2, y2);
-        bool ok = lane >= TR;
-        wave_sync();  // the accepted positions of agents 0..i-1 (written below by lane 0)
-        for (int j = 0; j < i; ++j) {
-          float dx = x2 - s.st[(e * N + j) * 8], dy = y2 - s.st[(e * N + j) * 8 + 1];
+        unsigned long long f2 = TR < 64 ? ~0ull << TR : 0ull;  // the tries still feasible, as a wavefront-uniform word (tries 0..TR-1 are known not to be)
+        // the accepted positions of agents 0..i-1, from the lanes' registers: lane j's winner lane holds it as its candidate, unless agent j came through here
+        const float wx = __shfl(cx, my_wl), wy = __shfl(cy, my_wl);
+        const float ax = my_wl >= 0 ? wx : my_x, ay = my_wl >= 0 ? wy : my_y;
+        for (int j = 0; j < i && f2; ++j) {  // (a try only ever loses its bit: once none is left the answer is "none feasible", whatever the agents after j)
+          const float axj = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(ax), j)), ayj = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(ay), j));
+          float dx = x2 - axj, dy = y2 - ayj;
           float d2 = dx * dx + dy * dy;
-          if (!(d2 >= min_d_sq)) ok = false;
+          f2 &= __ballot(d2 >= min_d_sq);
         }
-        unsigned long long f2 = __ballot(ok);
         const int wl = __builtin_amdgcn_readfirstlane(f2 ? (__ffsll((long long)f2) - 1) : (AUTO_RESET_MAX_TRIES - 1));
-        path = __builtin_amdgcn_readlane(p2, wl); pt = __builtin_amdgcn_readlane(q2, wl);
+        const int path = __builtin_amdgcn_readlane(p2, wl), pt = __builtin_amdgcn_readlane(q2, wl);
         px = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(x2), wl)); py = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(y2), wl));
+        if (lane == i) { my_path = path; my_pt = pt; my_x = px; my_y = py; }
       }
-      if (lane == i) { my_path = path; my_pt = pt; }
-      if (lane == 0) { s.st[(e * N + i) * 8] = px; s.st[(e * N + i) * 8 + 1] = py; }
-      // later agents must keep the minimum distance to this one (world_state_rt_sim.py:296-309)
+      // later agents must keep the minimum distance to this one (world_state_rt_sim.py:296-309): lanes up to agent i's keep their bit
       float dx = cx - px, dy = cy - py;
       float d2 = dx * dx + dy * dy;
-      if (ca > i && !(d2 >= min_d_sq)) cok = false;
+      cokm &= __ballot(d2 >= min_d_sq) | (~0ull >> (64 - (i + 1) * TR));
+    }
+    TS2(8);
+    {
+      const int wpath = __shfl(cpath, my_wl), wpt = __shfl(cpt, my_wl);  // (every lane takes part: a cross-lane read needs its source lane active)
+      if (my_wl >= 0) { my_path = wpath; my_pt = wpt; }
     }
     if (lane < N) {  // finalise the accepted starts, one lane per agent (world_state_rt_sim.py:189-213)
       const int i = lane, sl = e * N + i;
       float u = rng_uniform(rng_u32(seed, counter, (uint32_t)(c.env_index_base + b), (uint32_t)i, DRAW_RESET_SPEED));
       place_from_start_table(m, g, s, t, sl, my_path, my_pt, u * c.max_speed, rd.path_first, true, sid, fin);
     }
+    TS2(9);
   }
   __threadfence_block();
   Grp<WAVE>::sync();

@@ -110,13 +110,17 @@ inline CfgDerived derive_config(const sigmaenv_config_t& c) {
 #define START_COSV 3     /* cr_cos(0 + yaw), cr_sin(0 + yaw): velocity direction (world_state_rt_sim.py:203-207) */
 #define START_VERT 5     /* 10 floats */
 #define START_CS 15      /* cos / sin of the yaw as rect_vertices produces them */
-#define START_DREF 17
-#define START_DLEFT 18   /* 5 */
-#define START_DRIGHT 23  /* 5 */
-#define START_DBOUND 28
-#define START_SHORT 29   /* 2 * NS */
+#define START_SHORT 17   /* 2 * NS */
 #define START_CP (START_SHORT + 2 * NS)             /* 3 ints */
-#define START_ROW ((START_CP + 3 + 3) & ~3)         /* whole float4s */
+/* the row's head [0, START_HOT) is what the next step of a T-step launch reads from LDS: a mid-launch reset (place_from_start_table, fin = false) loads these
+   float4s only.  The tail holds the distances to the reference path and the boundaries, which only a complete reset copies (phases S and C of the next step
+   rewrite them in LDS before anything reads them): whole float4s of their own. */
+#define START_HOT ((START_CP + 3 + 3) & ~3)
+#define START_DREF START_HOT
+#define START_DLEFT (START_DREF + 1)    /* 5 */
+#define START_DRIGHT (START_DLEFT + 5)  /* 5 */
+#define START_DBOUND (START_DRIGHT + 5)
+#define START_ROW ((START_DBOUND + 1 + 3) & ~3)     /* whole float4s */
 
 struct DevBufs {
   float *state, *prev_pos, *vertices, *short_term, *dist_ref, *dist_left, *dist_right, *dist_bound, *dist_agents;
