@@ -536,7 +536,19 @@ int sigmaenv_rollout_f32(sigmaenv_t* h, sigmaenv_mlp32_t* m, const float* low, c
  *   neighbour actions each agent saw at its turn; base_obs_rec f32 [n_steps, B, N, obs_dim + 2 K] = the compact row every agent was evaluated on in its
  *   turn (its SIGMAENV_BUF_OBS row, then the 2 K neighbour-action columns: info()["base_observation"], helper_training.py:1305-1312), written by the turn's gather;
  *   every agent has one turn per step, so every row is written exactly once per step -- unless ranks_given names no agent for it, which leaves the row as it
- *   was; a rank entry outside [0, N) is never an address.  Communication noise (is_communication_noise, :1240-1254) is not built.
+ *   was; a rank entry outside [0, N) is never an address.
+ *   Communication noise (is_communication_noise, :1271-1287): comm_noise_std = (s_v, s_d) != 0, or comm_noise_std_env = a device f32 [B, 2] of per-env pairs,
+ *   turns it on (all zero: off).  The agent acting in turn k then sees column q of its 2 K neighbour-action columns as fl32(v + fl32(std_q * z)), z a standard
+ *   normal drawn per (env, acting agent, step, column) -- key (seed, counter0 + t, env_index_base + b, i), draws DRAW_COMM_NOISE + 2 q, + 2 q + 1, cosine branch
+ *   (csrc/sigmaenv_dist.h) -- whether or not the action sample is deterministic.  The std goes by the column's POSITION as in the reference, which adds
+ *   cat([s_v randn(2), s_d randn(2)]) to [a(n0).speed, a(n0).steer, a(n1).speed, a(n1).steer]: std = [s_v, s_v, s_d, s_d].  That 4-vector fits 2 K = 4 columns only,
+ *   so n_nearing != 2 is SIGMAENV_EINVAL (raises in the reference as well).  Every column gets its draw, whatever it holds: the zero of a neighbour that has not
+ *   acted, the column of a neighbour index that is no agent.  The noisy row is what the actor is evaluated on and what tentative_rec / base_obs_rec hold; the
+ *   actions themselves stay clean (combined_action): the step and the later turns read clean values.  A pair of zeros in comm_noise_std_env gives values that
+ *   compare equal to the noise-free rollout's.  Noise with another wrapper, a negative or non-finite comm_noise_std: SIGMAENV_EINVAL.
+ *   sigmaenv_comm_noise_stds(level, stds4): the four per-column stds of `level` as the reference forms them -- the double products
+ *   SIGMAENV_AGENT_MAX_SPEED * level and SIGMAENV_AGENT_MAX_STEERING * level rounded to fp32, by position; (stds4[0], stds4[2]) is comm_noise_std.  A library from
+ *   before this entry point reads the two fields as reserved words and runs WITHOUT noise: a binding must refuse noise when the symbol is missing.
  * A first call per handle allocates a workspace (grown when a later call needs more): do not make that first call inside a stream capture. */
 #define SIGMAENV_WRAP_PLAIN 0
 #define SIGMAENV_WRAP_OPPONENT 1
@@ -553,12 +565,16 @@ typedef struct sigmaenv_rollout_opts {
   int32_t* rank_rec;                 /* optional device i32 [n_steps, B, N] */
   float* score_rec;                  /* optional device f32 [n_steps, B, N] */
   float* score_logp_rec;             /* optional device f32 [n_steps, B, N] */
-  int32_t reserved[4];               /* zero */
+  float comm_noise_std[2];           /* communication noise: (s_v, s_d), the stds of columns 0, 1 and of columns 2, 3; zero: none */
+  const float* comm_noise_std_env;   /* optional device f32 [B, 2]: a pair per env, in place of comm_noise_std */
   float* base_obs_rec;               /* optional device f32 [n_steps, B, N, obs_dim + 2 K] (SIGMAENV_WRAP_PRIORITIZED) */
 } sigmaenv_rollout_opts_t;
 int sigmaenv_rollout_f32_ex(sigmaenv_t* h, sigmaenv_mlp32_t* m, const float* low, const float* high, float* scratch, int32_t n_steps, float* actions_buf,
                             float* slab_base, float* logp_base, float* actions_rec, uint64_t seed, uint64_t counter0, int32_t path_first, int32_t path_count,
                             int32_t deterministic, const sigmaenv_rollout_opts_t* opts);
+#define SIGMAENV_AGENT_MAX_SPEED 1.0                              /* AGENTS["max_speed"], sigmarl/constants.py:637-640 */
+#define SIGMAENV_AGENT_MAX_STEERING (31 * 3.141592653589793 / 180) /* AGENTS["max_steering"] = 31 * math.pi / 180 */
+int sigmaenv_comm_noise_stds(double level, float* stds4);
 
 /* ---- from a rollout's records to a learner's batch -------------------------------------------------------------------------------------
  * sigmaenv_gae: what the trainer computes right after collector.rollout() -- _compute_gae (sigmarl/mappo_cavs.py:357-386: torchrl GAE(gamma, lmbda,

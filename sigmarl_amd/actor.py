@@ -733,7 +733,8 @@ class Actor:
                 actions: torch.Tensor | None = None, seed: int = 0, counter0: int = 0, path_first: int | None = None, path_count: int | None = None,
                 deterministic: bool = False, precision: str | None = None, slab_ptr: int | None = None, wrapper: str | None = None,
                 priority=None, tentative: torch.Tensor | None = None, ranks: torch.Tensor | None = None, scores: torch.Tensor | None = None,
-                score_log_prob: torch.Tensor | None = None, obs_rec: torch.Tensor | None = None, base_obs: torch.Tensor | None = None):
+                score_log_prob: torch.Tensor | None = None, obs_rec: torch.Tensor | None = None, base_obs: torch.Tensor | None = None,
+                communication_noise=None):
         """``n_steps`` x (policy -> fused step + record + resets) enqueued back to back; optional records ``slab [T,B,W]``,
         ``log_prob [T,B,N]``, ``actions [T,B,N,2]`` (CUDA float32, contiguous).  ``slab_ptr``: the record target as a raw device address instead of ``slab`` (an env
         shard's first row inside a ``[T, B_total, W]`` buffer of the whole batch, with ``env.set_rollout_slab_stride(B_total * W)``).  ``precision`` (default: the actor's): "fp32" = the reference's
@@ -747,16 +748,25 @@ class Actor:
         its turn -- its ``env.obs`` row, then the 2 K neighbour-action columns it saw (the reference's ``base_observation``) --, written by the turn's gather, every
         row once per step.  Step semantics: include/sigmaenv.h, sigmaenv_rollout_f32_ex.
 
+        ``communication_noise`` (``"prioritized"`` only, 2 observed neighbours; ``params.communication_noise`` gives it for a ``Parameters``): the reference's
+        ``communication_noise_level`` -- a float, or a float32 CUDA tensor ``[B]`` of per-env levels (one rollout over a sweep of levels,
+        ``evaluate.noise_sweep``; a float64 tensor is taken too: its envs compute what the float of the same value computes).  Every agent then
+        sees the 2 K propagated-action columns of its turn plus a normal draw of std ``[s_v, s_v, s_d, s_d]``,
+        ``s_v = max_speed * level``, ``s_d = max_steering * level`` (by the column's position, as the reference adds them: helper_training.py:1271-1287), drawn per
+        (env, agent, step) from the rollout's key, also when ``deterministic``.  ``tentative`` and ``base_obs`` record the noisy values the actor was evaluated on;
+        ``actions`` and the step stay clean.  Level 0.0 is the rollout without the argument.  The stds are formed on the host as the reference forms them (the
+        double product, rounded to float32); the levels of a tensor are the caller's and are not checked (a NaN level gives NaN rows).
+
         ``obs_rec [T,B,N,D]`` (any precision, any wrapper): the root observations -- row t = ``env.obs`` as the final actor forward of step t read it, i.e. the
         ``observation`` of the collector's tensordict (the record row of step t - 1 holds it only where nothing was re-placed).  ``None``: the handle's setting is
         left as it is (off unless ``env.set_rollout_obs_record`` set it, as an env shard that records into the whole batch's buffer does)."""
-        check_rollout_wrapper(getattr(env, "parameters", None), wrapper)
+        check_rollout_wrapper(getattr(env, "parameters", None), wrapper, communication_noise)
         if obs_rec is not None:
             check_record(obs_rec, (int(n_steps), env.B, env.N, env.D), "obs_rec")
             env.set_rollout_obs_record(obs_rec)
             try:
                 return self.rollout(env, n_steps, slab, log_prob, actions, seed, counter0, path_first, path_count, deterministic, precision, slab_ptr, wrapper, priority,
-                                    tentative, ranks, scores, score_log_prob, base_obs=base_obs)
+                                    tentative, ranks, scores, score_log_prob, base_obs=base_obs, communication_noise=communication_noise)
             finally:
                 env.set_rollout_obs_record(None)  # (the copies are enqueued: the setting is only read while the loop enqueues)
         if path_first is None:
@@ -767,7 +777,7 @@ class Actor:
         if wrapper is not None:
             if (precision or self.precision) != "fp32":
                 raise ValueError("the rollout wrappers run the fp32 actor (precision='fp32')")
-            opts = self._wrapper_opts(env, int(n_steps), wrapper, priority, tentative, ranks, scores, score_log_prob, base_obs)
+            opts = self._wrapper_opts(env, int(n_steps), wrapper, priority, tentative, ranks, scores, score_log_prob, base_obs, communication_noise)
             lo, hi = self._keep[-2], self._keep[-1]
             rc = env.lib.rollout_f32_ex(env.h, self._mlp32.handle(env.lib, env), lo.ctypes.data_as(C.c_void_p), hi.ctypes.data_as(C.c_void_p), p(self._scratch_out4(env)),
                                          int(n_steps), p(scratch), p_slab, p(log_prob), p(actions), int(seed), int(counter0), int(path_first), int(path_count),
@@ -777,6 +787,8 @@ class Actor:
             return
         if base_obs is not None:
             raise ValueError("base_obs belongs to wrapper='prioritized'")
+        if communication_noise is not None:
+            raise ValueError("communication_noise belongs to wrapper='prioritized'")
         if (precision or self.precision) == "fp32":
             lo, hi = self._keep[-2], self._keep[-1]
             rc = env.lib.rollout_f32(env.h, self._mlp32.handle(env.lib, env), lo.ctypes.data_as(C.c_void_p), hi.ctypes.data_as(C.c_void_p), p(self._scratch_out4(env)), int(n_steps),
@@ -790,7 +802,34 @@ class Actor:
         if rc != 0:
             raise RuntimeError(f"sigmaenv_rollout failed with code {rc}: {env.lib.last_error(env.h).decode()}")
 
-    def _wrapper_opts(self, env: SigmaEnv, T: int, wrapper: str, priority, tentative, ranks, scores, score_log_prob, base_obs=None) -> capi.RolloutOpts:
+    def _noise_opts(self, env: SigmaEnv, opts: capi.RolloutOpts, noise) -> None:
+        """``communication_noise`` into ``opts``: the pair ``(s_v, s_d)`` of a float level, or the ``[B, 2]`` pairs of a ``[B]`` tensor of levels."""
+        if not hasattr(env.lib, "comm_noise_stds"):  # (a build from before the fields reads them as reserved words and would run without noise)
+            raise RuntimeError("communication_noise: this build of the library does not add communication noise")
+        if env.K != 2:
+            raise NotImplementedError(f"communication_noise with {env.K} observed neighbours: the reference's 4 noise stds fit 2 K = 4 columns only "
+                                      "(raises in the reference as well)")
+        max_speed, max_steering = capi.AGENTS["max_speed"], capi.AGENTS["max_steering"]
+        if isinstance(noise, torch.Tensor):
+            if not (noise.is_cuda and noise.dtype in (torch.float32, torch.float64) and noise.device == env.device and tuple(noise.shape) == (env.B,)):
+                raise TypeError(f"communication_noise must be a float or a float32 (or float64) CUDA tensor [{env.B}] on {env.device}")
+            with torch.cuda.device(env.device):
+                env.stream.wait_stream(torch.cuda.current_stream(env.device))
+                with torch.cuda.stream(env.stream):
+                    level = noise.to(torch.float64)
+                    stds = torch.stack((level * max_speed, level * max_steering), dim=-1).to(torch.float32).contiguous()
+            noise.record_stream(env.stream)
+            opts.comm_noise_std_env = stds.data_ptr()
+            self._noise_stds = stds  # (kept alive until the next call: the launches read it asynchronously)
+            return
+        if isinstance(noise, bool) or not isinstance(noise, (int, float, np.floating, np.integer)):
+            raise TypeError(f"communication_noise must be a float or a float32 (or float64) CUDA tensor [{env.B}] on {env.device}")
+        level = float(noise)
+        if not (np.isfinite(level) and level >= 0.0):
+            raise ValueError(f"communication_noise must be finite and >= 0, not {level}")
+        opts.comm_noise_std[0], opts.comm_noise_std[1] = float(np.float32(max_speed * level)), float(np.float32(max_steering * level))
+
+    def _wrapper_opts(self, env: SigmaEnv, T: int, wrapper: str, priority, tentative, ranks, scores, score_log_prob, base_obs=None, communication_noise=None) -> capi.RolloutOpts:
         opts = capi.RolloutOpts()
         opts.wrapper = {"plain": capi.WRAP_PLAIN, "opponent": capi.WRAP_OPPONENT, "prioritized": capi.WRAP_PRIORITIZED}[wrapper]
 
@@ -805,7 +844,11 @@ class Actor:
         if wrapper != "prioritized":
             if priority is not None or ranks is not None or scores is not None or score_log_prob is not None or base_obs is not None:
                 raise ValueError("priority / ranks / scores / score_log_prob / base_obs belong to wrapper='prioritized'")
+            if communication_noise is not None:
+                raise ValueError("communication_noise belongs to wrapper='prioritized'")
             return opts
+        if communication_noise is not None:
+            self._noise_opts(env, opts, communication_noise)
         if base_obs is not None and not hasattr(env.lib, "ppo_head_1d"):  # (SIGMAENV_LIB_OLD_ABI: a build from before the record reads a shorter struct)
             raise RuntimeError("base_obs: this build of the library does not write the base-observation record")
         opts.base_obs_rec = rec(base_obs, (T, env.B, env.N, env.D + 2 * env.K), torch.float32, "base_obs")

@@ -90,7 +90,7 @@ class RolloutOpts(C.Structure):
     _fields_ = [
         ("wrapper", C.c_int32), ("priority_source", C.c_int32), ("priority_net", C.c_void_p), ("ranks_given", C.c_void_p),
         ("tentative_rec", C.c_void_p), ("rank_rec", C.c_void_p), ("score_rec", C.c_void_p), ("score_logp_rec", C.c_void_p),
-        ("reserved", C.c_int32 * 4), ("base_obs_rec", C.c_void_p),
+        ("comm_noise_std", C.c_float * 2), ("comm_noise_std_env", C.c_void_p), ("base_obs_rec", C.c_void_p),
     ]
 
 
@@ -346,6 +346,7 @@ _PRODUCT_ONLY = {
                           C.c_int32, C.c_int32]),
     "rollout_f32_ex": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64,
                                  C.c_uint64, C.c_int32, C.c_int32, C.c_int32, C.POINTER(RolloutOpts)]),
+    "comm_noise_stds": (C.c_int, [C.c_double, C.c_void_p]),
     "priority_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_int32]),
     "priority_rank": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "priority_random": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p]),

@@ -3,7 +3,8 @@
 // sigmarl/modules/decision_making_module.py:50-82 and priority_module.py:34-66 build them; torchrl is third-party and absent: restated from its published
 // behaviour).  The kernels of sigmaenv.hip, sigmaenv_actor.inc, sigmaenv_wrappers.inc, sigmaenv_ppo.inc and sigmaenv_prb.inc run these functions on the device; a host
 // program runs them on the host (tests/test_dist_check.py holds the generator, the uniforms and the bounded draw bit for bit to tests/policy_head_check.py, the
-// normals and the head to its float64 reference within its criterion, and the table to every Python mirror).
+// normals and the head to its float64 reference within its criterion, and the table to every Python mirror; tests/test_comm_noise_check.py holds the communication noise
+// at the end of this file to tests/comm_noise_check.py).
 //
 // Plain C++: no HIP include and no other file of the library.  The library compiles it as __host__ __device__ __forceinline__; a host program defines SIGMA_HD as
 // `static inline` first and includes this header alone.  Every operator below is ONE IEEE fp32 operation in the order written (-ffp-contract=off).  logf / expf /
@@ -45,11 +46,14 @@ SIGMA_HD uint32_t rng_u32(uint64_t seed, uint64_t counter, uint32_t env, uint32_
 #define DRAW_ENTROPY 7300u       /* u1, + 1: u2 of the PPO entropy sample                                        ppo_head            (env = frame, agent) */
 #define DRAW_PRIORITY_ENTROPY 7350u /* u1, + 1: u2 of the priority PPO entropy sample (cosine branch)           ppo_head_1d         (env = frame, agent) */
 #define DRAW_REPLAY 7400u        /* the replay sampler's uniform                                                 prb sample          (env = slot m, 0) */
+#define COMM_NOISE_MAX_COLUMNS 8u /* 2 K action columns of a base observation at the largest K the library accepts (SIGMAENV_MAX_NEARING = 4) */
+#define DRAW_COMM_NOISE 7500u    /* + 2 q: u1, + 2 q + 1: u2 of the normal (cosine branch) on action column q of a turn      turn_gather         (env, agent = the acting one) */
 #define DRAW_OBS_NOISE 9000u     /* + k: element k of an observation row; open-ended, so the highest             obs_noise           (env, agent) */
 static_assert(DRAW_RESET_TRY + 2u * AUTO_RESET_MAX_TRIES <= DRAW_RESET_SPEED && DRAW_RESET_SPEED < DRAW_AGENT_TRY, "full-env reset tries run into the next stream");
 static_assert(DRAW_AGENT_TRY + 2u * AUTO_RESET_MAX_TRIES <= DRAW_AGENT_SPEED && DRAW_AGENT_SPEED < DRAW_SCENARIO, "single-agent reset tries run into the next stream");
 static_assert(DRAW_SCENARIO < DRAW_ACTOR && DRAW_ACTOR + 1u < DRAW_PRIORITY && DRAW_PRIORITY + 1u < DRAW_SHUFFLE && DRAW_SHUFFLE < DRAW_ENTROPY &&
-              DRAW_ENTROPY + 1u < DRAW_PRIORITY_ENTROPY && DRAW_PRIORITY_ENTROPY + 1u < DRAW_REPLAY && DRAW_REPLAY < DRAW_OBS_NOISE, "the streams overlap, or the open-ended noise range is not the highest");
+              DRAW_ENTROPY + 1u < DRAW_PRIORITY_ENTROPY && DRAW_PRIORITY_ENTROPY + 1u < DRAW_REPLAY && DRAW_REPLAY < DRAW_COMM_NOISE && DRAW_COMM_NOISE + 2u * COMM_NOISE_MAX_COLUMNS <= DRAW_OBS_NOISE,
+              "the streams overlap, or the open-ended noise range is not the highest");
 
 // ---- a word -> a number ------------------------------------------------------------------------------------------------------------------------------------------------
 // U[0, 1): (k >> 8) * 2^-24, exact in fp32; never 1
@@ -100,5 +104,22 @@ SIGMA_HD float tn_affine(float low, float y, float h) { return low + (y + 1.0f) 
 // q = (x - loc) / scale (a sample's own x: q = z);  without the - log h of the affine map
 SIGMA_HD float tn_log_density(float q, float log_scale, float x) {
   return -0.5f * q * q - log_scale - TN_LOG_SQRT_2PI - 2.0f * (TN_LOG2 - x - tn_softplus(-2.0f * x));
+}
+
+// ---- communication noise on the propagated actions (prioritized_ap_policy, sigmarl/helper_training.py:1271-1287) ------------------------------------------------------
+// The acting agent sees column q of its 2 K neighbour-action columns as v + std z: the fp32 product rounded, then the fp32 sum rounded -- two operations whatever
+// the compiler's contraction setting is (torch multiplies the draws by the std, then adds the tensor).  z: rng_normal_cos of DRAW_COMM_NOISE + 2 q under the key
+// (seed, counter, env, the acting agent).
+// The std goes by the column's POSITION, not by its quantity: the reference adds cat([s_v randn(2), s_d randn(2)]) to [a(n0).speed, a(n0).steer, a(n1).speed,
+// a(n1).steer], so columns 0 and 1 take the speed's std and columns 2 and 3 the steering's.  (The 4-vector fits 2 K = 4 columns only: K = 2.)
+SIGMA_HD float comm_noise_std(int q, float s_v, float s_d) { return q < 2 ? s_v : s_d; }
+SIGMA_HD float comm_noise_seen(float v, float std, float z) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+  const float p = std * z;
+#else
+  volatile float p = std * z;  /* (no pragma that every host compiler honours: the product is forced through memory) */
+#endif
+  return v + p;
 }
 #endif  // SIGMAENV_DIST_H

@@ -71,9 +71,25 @@ __global__ void __launch_bounds__(256) sigmaenv_priority_random_kernel(int B, in
 // row_map[b] = b N + i (-1 when ranks holds no agent index).  rec (optional, [B, N, K, 2]): the neighbour actions agent i saw.  base_rec (optional,
 // [B, N, D + 2 K]): the whole compact row at agent i's place -- the base observation a learner trains the actor on; one more store per gathered element, coalesced
 // over the row as the compact one is.  One lane per (env, column).
-__global__ void __launch_bounds__(256) sigmaenv_turn_gather_kernel(const float* __restrict__ obs, int D, const int32_t* __restrict__ nearing, int K, const float* __restrict__ actions,
-                                                                   const int32_t* __restrict__ ranks, int k, int B, int N, float* __restrict__ compact, int32_t* __restrict__ row_map,
-                                                                   float* __restrict__ rec, float* __restrict__ base_rec) {
+//
+// The body is one template; sigmaenv_turn_gather_kernel is its noise-free instantiation under the signature it always had, sigmaenv_turn_gather_noise_kernel the noisy one.
+// NOISE (is_communication_noise, helper_training.py:1271-1287; K = 2): every one of the 2 K columns -- the zero of an undecided neighbour and the column of a
+// neighbour index that is no agent included -- is seen as comm_noise_seen(v, std of its position, z) (sigmaenv_dist.h), z drawn per (env, acting agent, step,
+// column).  compact, rec and base_rec take the noisy value: the actor is evaluated on it and the learner trains on it.  `actions` is only read, so the step and the
+// later turns' gathers get the clean actions (combined_action).  The stds: std_env[b] = (s_v, s_d) of env b when given, else the launch's pair.
+struct TurnNoise {
+  float s_v, s_d;
+  const float* std_env;  // optional [B, 2]
+  uint64_t seed, counter;
+  int env_base;
+};
+
+static_assert(COMM_NOISE_MAX_COLUMNS == 2u * SIGMAENV_MAX_NEARING, "the draw ids reserved for communication noise are those of 2 K columns at the largest K");
+
+template <bool NOISE>
+__device__ __forceinline__ void turn_gather(const float* __restrict__ obs, int D, const int32_t* __restrict__ nearing, int K, const float* __restrict__ actions,
+                                            const int32_t* __restrict__ ranks, int k, int B, int N, float* __restrict__ compact, int32_t* __restrict__ row_map,
+                                            float* __restrict__ rec, float* __restrict__ base_rec, const TurnNoise& nz) {
   sigma_poison_lds();
   const int Dc = D + 2 * K;
   const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -92,11 +108,33 @@ __global__ void __launch_bounds__(256) sigmaenv_turn_gather_kernel(const float* 
       const int q = c - D, j = q >> 1;
       const int n = nearing[bi * K + j];
       if (n >= 0 && n < N) v = actions[(b * N + n) * 2 + (q & 1)];
+      if (NOISE) {
+        float s_v = nz.s_v, s_d = nz.s_d;
+        if (nz.std_env) {
+          const float2 s = reinterpret_cast<const float2*>(nz.std_env)[b];
+          s_v = s.x;
+          s_d = s.y;
+        }
+        const float z = rng_normal_cos(nz.seed, nz.counter, (uint32_t)(nz.env_base + (int)b), (uint32_t)i, DRAW_COMM_NOISE + 2u * (uint32_t)q);
+        v = comm_noise_seen(v, comm_noise_std(q, s_v, s_d), z);
+      }
       if (rec) rec[(bi * K + j) * 2 + (q & 1)] = v;
     }
     if (base_rec) base_rec[bi * Dc + c] = v;
   }
   compact[t] = v;
+}
+
+__global__ void __launch_bounds__(256) sigmaenv_turn_gather_kernel(const float* __restrict__ obs, int D, const int32_t* __restrict__ nearing, int K, const float* __restrict__ actions,
+                                                                   const int32_t* __restrict__ ranks, int k, int B, int N, float* __restrict__ compact, int32_t* __restrict__ row_map,
+                                                                   float* __restrict__ rec, float* __restrict__ base_rec) {
+  turn_gather<false>(obs, D, nearing, K, actions, ranks, k, B, N, compact, row_map, rec, base_rec, TurnNoise{});
+}
+
+__global__ void __launch_bounds__(256) sigmaenv_turn_gather_noise_kernel(const float* __restrict__ obs, int D, const int32_t* __restrict__ nearing, int K, const float* __restrict__ actions,
+                                                                         const int32_t* __restrict__ ranks, int k, int B, int N, float* __restrict__ compact, int32_t* __restrict__ row_map,
+                                                                         float* __restrict__ rec, float* __restrict__ base_rec, TurnNoise nz) {
+  turn_gather<true>(obs, D, nearing, K, actions, ranks, k, B, N, compact, row_map, rec, base_rec, nz);
 }
 
 }  // namespace wrap
@@ -149,6 +187,24 @@ extern "C" int sigmaenv_rollout_f32_ex(sigmaenv_t* h, sigmaenv_mlp32* m, const f
                                        float* slab_base, float* logp_base, float* actions_rec, uint64_t seed, uint64_t counter0, int32_t path_first, int32_t path_count,
                                        int32_t deterministic, const sigmaenv_rollout_opts_t* opts) {
   const int wrapper = opts ? opts->wrapper : SIGMAENV_WRAP_PLAIN;
+  // communication noise: all zero (what a caller from before the fields existed passes as reserved[4]) means off
+  const bool noise = opts && (opts->comm_noise_std[0] != 0.0f || opts->comm_noise_std[1] != 0.0f || opts->comm_noise_std_env);
+  if (noise) {
+    if (!h) return SIGMAENV_EINVAL;
+    if (wrapper != SIGMAENV_WRAP_PRIORITIZED) {
+      h->err = "rollout_f32_ex: communication noise acts on the propagated actions of SIGMAENV_WRAP_PRIORITIZED only";
+      return SIGMAENV_EINVAL;
+    }
+    if (h->cfg.n_nearing != 2) {
+      h->err = "rollout_f32_ex: communication noise needs n_nearing == 2 (its 4 stds fit 2 K = 4 columns only: raises in the reference as well)";
+      return SIGMAENV_EINVAL;
+    }
+    for (int d = 0; d < 2; ++d)
+      if (!(opts->comm_noise_std[d] >= 0.0f) || isinf(opts->comm_noise_std[d])) {
+        h->err = "rollout_f32_ex: comm_noise_std must be finite and >= 0";
+        return SIGMAENV_EINVAL;
+      }
+  }
   if (wrapper == SIGMAENV_WRAP_PLAIN)
     return sigmaenv_rollout_f32(h, m, low, high, scratch, n_steps, actions_buf, slab_base, logp_base, actions_rec, seed, counter0, path_first, path_count, deterministic);
   if (!h || !m || !low || !high || !scratch || !actions_buf || n_steps < 1 || m->out_dim != 4) return SIGMAENV_EINVAL;
@@ -219,13 +275,28 @@ extern "C" int sigmaenv_rollout_f32_ex(sigmaenv_t* h, sigmaenv_mlp32* m, const f
     float* rec = opts->tentative_rec ? opts->tentative_rec + (size_t)t * BN * K * 2 : nullptr;
     float* base_rec = opts->base_obs_rec ? opts->base_obs_rec + (size_t)t * BN * Dc : nullptr;
     const size_t n_gather = (size_t)B * Dc;
+    const wrap::TurnNoise nz = {noise ? opts->comm_noise_std[0] : 0.0f, noise ? opts->comm_noise_std[1] : 0.0f, noise ? opts->comm_noise_std_env : nullptr, seed, ctr,
+                                h->cfg.env_index_base};
     for (int k = 0; k < N; ++k) {
-      hipLaunchKernelGGL(wrap::sigmaenv_turn_gather_kernel, dim3((unsigned)((n_gather + 255) / 256)), dim3(256), 0, h->stream, h->buf.obs, D, h->buf.nearing, K, act, ranks, k, B, N,
-                         compact, row_map, rec, base_rec);
+      if (noise)
+        hipLaunchKernelGGL(wrap::sigmaenv_turn_gather_noise_kernel, dim3((unsigned)((n_gather + 255) / 256)), dim3(256), 0, h->stream, h->buf.obs, D, h->buf.nearing, K, act, ranks, k,
+                           B, N, compact, row_map, rec, base_rec, nz);
+      else
+        hipLaunchKernelGGL(wrap::sigmaenv_turn_gather_kernel, dim3((unsigned)((n_gather + 255) / 256)), dim3(256), 0, h->stream, h->buf.obs, D, h->buf.nearing, K, act, ranks, k, B, N,
+                           compact, row_map, rec, base_rec);
       HIPCHK(h, hipGetLastError());
       const int r = actor_rows_f32(h, m, compact, B, row_map, scratch, low, high, act, logp, nullptr, seed, ctr, deterministic);
       if (r) return r;
     }
     return SIGMAENV_OK;
   }, n_steps, actions_buf, slab_base, logp_base, actions_rec, seed, counter0, path_first, path_count);
+}
+
+// the per-column stds of communication noise at `level` as the reference forms them (helper_training.py:1274-1284): the double products AGENTS["max_speed"] * level
+// and AGENTS["max_steering"] * level, each rounded to fp32 where it multiplies the fp32 draws, laid out by position (comm_noise_std)
+extern "C" int sigmaenv_comm_noise_stds(double level, float* stds4) {
+  if (!stds4 || !(level >= 0.0) || isinf(level)) return SIGMAENV_EINVAL;
+  const float s_v = (float)(SIGMAENV_AGENT_MAX_SPEED * level), s_d = (float)(SIGMAENV_AGENT_MAX_STEERING * level);
+  for (int q = 0; q < 4; ++q) stds4[q] = comm_noise_std(q, s_v, s_d);
+  return SIGMAENV_OK;
 }

@@ -5,7 +5,8 @@ and many parallel envs, ``_get_simulation_outputs`` (:271-282) makes ONE ``env.r
 (:184-217) reduces five ``info`` entries of its output to four numbers per env, and ``compute_performance_metrics`` / ``_log`` (:670-760) summarise them.
 
 Here ``Evaluator`` owns the per-env accumulators on the device (``sigmaenv_eval_*``, include/sigmaenv.h; the arithmetic: csrc/sigmaenv_eval.h), ``evaluate`` is the
-rollout with the evaluator attached, and ``summarize`` / ``composite_score`` are the summary as host torch on ``[B]`` vectors.
+rollout with the evaluator attached, ``noise_sweep`` is that rollout over a sweep of communication-noise levels, and ``summarize`` / ``composite_score`` are the
+summary as host torch on ``[B]`` vectors.
 
 The frame window of ``evaluate`` -- which moments are counted -- restates torchrl's rollout from its published behaviour (torchrl is third-party and absent, as for
 GAE and ``RewardSum``): ``out_td["agents", "info", .]`` holds the ROOT entries of the ``T`` stacked tensordicts, and the root entries are the info after the reset,
@@ -170,7 +171,8 @@ def evaluate(env, actor, params=None, n_steps: int | None = None, seed: int = 0,
     ``env.reset_random(seed)`` -- its draws keyed by the counter ``counter0 + T - 1``, the first one the rollout's steps ``counter0 .. counter0 + T - 2`` do not use, so
     that the result is a function of the arguments alone --, ``Evaluator.reset()``, ``accumulate()`` of the state after the initial reset, ``actor.rollout`` of ``T - 1`` steps with the evaluator
     attached, ``finish()`` -- the window the module docstring derives.  The reference sets no exploration type for this rollout; ``deterministic=True`` is the default
-    here and is passed through to ``Actor.rollout``, as is ``rollout_kw`` (``wrapper=``, ``priority=``, ``precision=`` ..).  Returns ``finish()``'s dict, plus ``trace``
+    here and is passed through to ``Actor.rollout``, as is ``rollout_kw`` (``wrapper=``, ``priority=``, ``precision=``, ``communication_noise=`` ..; the noise is drawn
+    although the actions are deterministic, as in the reference's evaluation rollout, helper_training.py:230-243).  Returns ``finish()``'s dict, plus ``trace``
     (host ``[T, B, N, 8]``) when asked for."""
     params = params if params is not None else env.parameters
     T = int(n_steps) if n_steps else int(params.max_steps) - 1
@@ -192,6 +194,35 @@ def evaluate(env, actor, params=None, n_steps: int | None = None, seed: int = 0,
         return out
     finally:
         ev.close()
+
+
+def noise_sweep(env, actor, levels, params=None, **evaluate_kw) -> list:
+    """The reference's robustness study of prioritized action propagation -- the communication-noise level swept at evaluation -- as ONE evaluation rollout: the
+    envs are split into ``len(levels)`` contiguous groups of ``B / len(levels)`` (``ValueError`` when that does not divide), group ``g`` runs at ``levels[g]``
+    (``Actor.rollout(communication_noise=)`` with the per-env levels, formed in float64 so that a group computes what the scalar level computes), and
+    ``evaluate``'s per-env results come back grouped: a list of dicts, one per level in order, each with ``level``, ``envs = (first, end)``, ``metrics [B / L, 4]``,
+    ``counts``, the four named columns and ``frames`` -- each ready for ``summarize``.  ``evaluate_kw``: ``evaluate``'s arguments, with ``wrapper="prioritized"`` and
+    ``priority=`` among them.  An env's draws are keyed by its index in the whole batch, so group ``g`` equals the evaluation of a handle of those envs alone
+    (``env_index_base`` = its first env) at the scalar level."""
+    levels = [float(v) for v in levels]
+    n = len(levels)
+    if n < 1 or int(env.B) % n:
+        raise ValueError(f"noise_sweep: the {int(env.B)} envs do not split into {n} groups of equal size, one per level")
+    if "communication_noise" in evaluate_kw:
+        raise TypeError("noise_sweep: the levels are the communication noise")
+    if "trace" in evaluate_kw:
+        raise TypeError("noise_sweep: the trace is per evaluation, not per level: evaluate(trace=True, communication_noise=...)")
+    g = int(env.B) // n
+    per_env = torch.tensor(levels, dtype=torch.float64).repeat_interleave(g).to(env.device)
+    out = evaluate(env, actor, params, communication_noise=per_env, **evaluate_kw)
+    groups = []
+    for k, level in enumerate(levels):
+        r = {"level": level, "envs": (k * g, (k + 1) * g), "metrics": out["metrics"][k * g:(k + 1) * g], "counts": out["counts"][k * g:(k + 1) * g],
+             "count_names": out["count_names"], "frames": out["frames"]}
+        for c, name in enumerate(capi.EVAL_METRICS):
+            r[name] = r["metrics"][:, c]
+        groups.append(r)
+    return groups
 
 
 # ---- the summary (host torch) ---------------------------------------------------------------------------------------------------------------------

@@ -118,13 +118,30 @@ def rollout_wrapper(p: Parameters) -> str | None:
     return None
 
 
-def check_rollout_wrapper(p: Parameters | None, wrapper: str | None) -> None:
-    """Raise for a wrapper / configuration pair the device rollout does not build: communication noise on the propagated actions
-    (``is_communication_noise``, helper_training.py:1240-1254) is not built for ``"prioritized"`` -- refused, never ignored."""
+def communication_noise(p: Parameters):
+    """The ``communication_noise=`` of ``Actor.rollout`` for ``p``: ``p.communication_noise_level`` when ``p.is_communication_noise``, else ``None``."""
+    return p.communication_noise_level if getattr(p, "is_communication_noise", False) else None
+
+
+def check_rollout_wrapper(p: Parameters | None, wrapper: str | None, communication_noise=None) -> None:
+    """Raise for a wrapper / configuration / noise triple the device rollout does not run.  ``communication_noise``: the noise the call will run on the
+    propagated actions (``Actor.rollout(communication_noise=)``; ``None``: none).  Parameters that ask for noise (``is_communication_noise``,
+    helper_training.py:1271-1287) with ``"prioritized"`` and a call that passes none: ``NotImplementedError`` -- the call would ignore what the parameters ask
+    for; refused, never ignored.  Noise passed with ``"prioritized"`` needs 2 observed neighbours (the reference's 4 stds fit 2 K = 4 columns only and its
+    addition raises otherwise): ``NotImplementedError`` for any other K known from ``p``; with any other wrapper: ``ValueError``."""
     if wrapper not in (None, "plain", "opponent", "prioritized"):
         raise ValueError(f"wrapper must be None, 'plain', 'opponent' or 'prioritized', not {wrapper!r}")
-    if wrapper == "prioritized" and p is not None and getattr(p, "is_communication_noise", False):
-        raise NotImplementedError("is_communication_noise (noise on the propagated actions, helper_training.py:1240-1254) is not built in the prioritized device rollout")
+    if communication_noise is not None:
+        if wrapper != "prioritized":
+            raise ValueError(f"communication_noise acts on the propagated actions of wrapper='prioritized', not of {wrapper!r}")
+        if p is not None:
+            k = min(int(p.n_nearing_agents_observed), int(p.n_agents) - 1)
+            if k != 2:
+                raise NotImplementedError(f"communication_noise with {k} observed neighbours: the reference's 4 noise stds fit 2 K = 4 columns only "
+                                          "(raises in the reference as well)")
+    elif wrapper == "prioritized" and p is not None and getattr(p, "is_communication_noise", False):
+        raise NotImplementedError("the parameters ask for is_communication_noise (noise on the propagated actions, helper_training.py:1271-1287) and this call "
+                                  "would ignore it: pass communication_noise=params.communication_noise(p)")
 
 
 def check_supported(p: Parameters) -> None:

@@ -1,6 +1,6 @@
 #!/usr/bin/env python
 """ms per step of the fp32 device rollout with each policy wrapper of the collector (sigmaenv_rollout_f32_ex): plain, opponent modelling, prioritized action
-propagation (priority network, random ranks), in chunks of T steps at N agents x B envs (default 32 x (16 x 4096)).  A report, not a pass criterion.
+propagation (priority network, random ranks, random ranks with communication noise next to their noise-free line), in chunks of T steps at N agents x B envs (default 32 x (16 x 4096)).  A report, not a pass criterion.
 Prints one JSON line."""
 import json
 import os
@@ -50,5 +50,8 @@ actor = Actor(make_mlp(env.D + 2 * env.K), low=[-1.0, -0.6], high=[1.0, 0.6])
 pn = PriorityNet(make_priority_mlp(env.D))
 out["ms_per_step"]["prioritized_net"] = time_rollout(actor, env, wrapper="prioritized", priority=pn)
 out["ms_per_step"]["prioritized_random"] = time_rollout(actor, env, wrapper="prioritized", priority="random")
+if hasattr(env.lib, "comm_noise_stds"):  # (an older build of the library as the A/B baseline has no noise)
+    out["ms_per_step"]["prioritized_random_noise"] = time_rollout(actor, env, wrapper="prioritized", priority="random", communication_noise=0.1)
+    out["ms_per_step"]["prioritized_random_again"] = time_rollout(actor, env, wrapper="prioritized", priority="random")  # the noise-free line once more: the run's own spread
 env.close()
 print(json.dumps(out))
