@@ -685,7 +685,8 @@ typedef struct sigmaenv_eval sigmaenv_eval_t;
 typedef struct sigmaenv_eval_args {
   int32_t trace_frames;            /* 0: no trace */
   int32_t debug_frames0;           /* test hook, zero otherwise: the frame count a reset starts from */
-  int32_t reserved[6];             /* zero */
+  int32_t study;                   /* 1: a study evaluator (below); 0 (what a zeroed reserved word was): the four metrics alone */
+  int32_t reserved[5];             /* zero */
 } sigmaenv_eval_args_t;
 typedef struct sigmaenv_eval_src {
   const float* state;              /* optional device f32 [B, N, 8] */
@@ -701,6 +702,10 @@ typedef struct sigmaenv_eval_src {
 #define SIGMAENV_EVAL_FRAMES 4
 #define SIGMAENV_EVAL_TRACE 5
 #define SIGMAENV_EVAL_FRAMES_HOST 6
+#define SIGMAENV_EVAL_STUDY_SUMS 7    /* f64 [7, B]: event, a^2, j^2, |dv|, |ds|, |av|, |as| */
+#define SIGMAENV_EVAL_STUDY_N_ACT 8   /* u32 [B] */
+#define SIGMAENV_EVAL_STUDY_CARRY 9   /* f32 [B, N, 2]: v_prev, a_prev */
+#define SIGMAENV_EVAL_STUDY_TIMER0 10 /* i32 [B, 2]: the snapshot of num_task_tries, task_success_times */
 int sigmaenv_eval_create(sigmaenv_t* h, const sigmaenv_eval_args_t* args, sigmaenv_eval_t** out);
 void sigmaenv_eval_destroy(sigmaenv_eval_t* ev);
 int sigmaenv_eval_reset(sigmaenv_t* h, sigmaenv_eval_t* ev);
@@ -708,6 +713,43 @@ int sigmaenv_eval_accumulate(sigmaenv_t* h, sigmaenv_eval_t* ev, const sigmaenv_
 int sigmaenv_eval_finish(sigmaenv_t* h, sigmaenv_eval_t* ev, float* metrics, uint32_t* counts);
 int sigmaenv_eval_attach(sigmaenv_t* h, sigmaenv_eval_t* ev);
 int sigmaenv_eval_get(sigmaenv_t* h, sigmaenv_eval_t* ev, int32_t what, void* host_out);
+
+/* ---- the study of a CBF-filtered policy: six more metrics per env (sigmaenv_eval_args_t.study = 1; the arithmetic: sigmaenv_eval.h, second half) ------------
+ * What sigmarl/evaluation_itsc26.py reduces a testing rollout to: compute_total_reward (:926-992), compute_cbf_activation_percentage (:995-1035) and the task
+ * counters num_task_tries / task_success_times (:883-898, metric_task_success_rate :1450-1458).  The reference runs one env per process; here every env of the
+ * batch is such a run.  An evaluator created with study = 0 is what it was: nothing below applies to it, and its kernel is unchanged.
+ *
+ * A study evaluator takes, with EVERY frame (sigmaenv_eval_accumulate, an attached rollout's step, sigmaenv_eval_accumulate_study), besides the four inputs above:
+ * (av, as) = SIGMAENV_BUF_ACTION[b,i,:], the applied action; (nv, ns) = the nominal action: SIGMAENV_BUF_CBF_NOMINAL[b,i,:] when the handle's chain runs the
+ * CBF-QP (SIGMAENV_REW_CBF_QP without SIGMAENV_REW_CBF, and sigmaenv_cbf_attach: the very condition under which a rollout step launches sigmaenv_cbf_qp; with both
+ * flags set the chain runs the margin rewards and no QP), otherwise the applied action of the frame itself.  This is a fact of the HANDLE; a caller who reads the
+ * nominal action from its own configuration instead (sigmarl_amd/scenario.py does, from its Parameters) can disagree with it, e.g. before sigmaenv_cbf_attach; rows 1 (rew_reach_goal), 7 (rew_collide_other_agents), 8 (rew_collide_lane) of SIGMAENV_BUF_REWARD_INFO; and a carry f32 [B,N,2] = (v_prev, a_prev).
+ * Element contract, every operator one fp32 IEEE operation, no contraction:  e = (r1 + r7) + r8;  a = (av - v_prev) / fl32(0.1);  j = (a - a_prev) / fl32(0.1)  (0.1 is
+ * the reference's constant, not Parameters.dt);  then v_prev = av, a_prev = a;  terms q q with q = |a| / 3.0f, q q with q = |j| / 20.0f, |av - nv|, |as - ns|, |av|, |as|;
+ * activated = |av - nv| > fl32(1e-9) || |as - ns| > fl32(1e-9).  An INITIAL frame (study_src->initial = 1: the state after the reset) takes av = as = nv = ns = e = 0
+ * whatever the buffers hold, a = j = 0, leaves the carry zero, and retakes the snapshot of the task counters from columns 1, 2 of the timer it is given.  A
+ * re-placement of testing mode does not touch the carry.  Reduction contract: the seven sums over the agents in the butterfly above, ONE fp64 addition per frame
+ * into seven accumulators; n_act += the activated agents of the frame (the popcount of the group's ballot), uint32.  No atomics.
+ * sigmaenv_eval_study_finish: ONE launch.  metrics f32 [B,6], M = F N, m_x = (float)(sum_x / (double)M):  [1] event = (float)sum_e;  [2] comfort = (-0.2f m_a2) + (-0.2f m_j2);
+ *   [0] total = event + comfort;  [3] degree = 100.0f (0.5f (m_dv / (m_av + 1e-9f) + m_ds / (m_as + 1e-9f)));  [4] rate = (float)((double)(100 n_act) / (double)M);
+ *   [5] success rate = (float)(100.0 success / tries), NaN when tries <= 0, with tries / success = SIGMAENV_BUF_TIMER[b,1] / [b,2] AS THEY STAND WHEN THE LAUNCH RUNS
+ *   minus the snapshot.  counts (optional) u32 [B,4] = n_act, tries, success, frames.  The accumulators are left as they are; sigmaenv_eval_finish still gives the four.
+ * sigmaenv_eval_reset on a study evaluator also zeroes sums, count and carry and takes the snapshot from SIGMAENV_BUF_TIMER, on the stream (one more small launch).
+ * sigmaenv_eval_accumulate_study: sigmaenv_eval_accumulate with study_src (NULL: no override, not initial): each non-null pointer replaces the handle's buffer of
+ *   that name in its layout (applied, nominal f32 [B,N,2]; reward_info f32 [12,B,N], rows 1, 7, 8 read; timer i32 [B,4], read by an initial frame only), 4-byte
+ *   aligned.  Without a nominal override and without the QP in the chain, the nominal action is the frame's applied action, an override included.
+ * sigmaenv_eval_get: _STUDY_SUMS f64 [7,B] (event, a^2, j^2, |dv|, |ds|, |av|, |as|), _STUDY_N_ACT u32 [B], _STUDY_CARRY f32 [B,N,2], _STUDY_TIMER0 i32 [B,2].
+ * Refused with SIGMAENV_EINVAL before any launch, besides the refusals above: the three study calls / items on an evaluator created without study; initial not 0 / 1. */
+typedef struct sigmaenv_eval_study_src {
+  const float* applied;            /* optional device f32 [B, N, 2] */
+  const float* nominal;            /* optional device f32 [B, N, 2] */
+  const float* reward_info;        /* optional device f32 [12, B, N] */
+  const int32_t* timer;            /* optional device i32 [B, 4] */
+  int32_t initial;                 /* 1: the frame after the reset */
+  int32_t reserved[3];             /* zero */
+} sigmaenv_eval_study_src_t;
+int sigmaenv_eval_accumulate_study(sigmaenv_t* h, sigmaenv_eval_t* ev, const sigmaenv_eval_src_t* src, const sigmaenv_eval_study_src_t* study_src);
+int sigmaenv_eval_study_finish(sigmaenv_t* h, sigmaenv_eval_t* ev, float* metrics, uint32_t* counts);
 
 /* ---- the clip-PPO loss head of a minibatch update (sigmaenv_ppo.inc) ---------------------------------------------------------------------
  * sigmaenv_ppo_head: torchrl's ClipPPOLoss as sigmarl/modules/optimization_module.py:44-66 configures it (clip_epsilon, entropy_coeff = entropy_eps,

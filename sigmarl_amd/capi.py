@@ -118,9 +118,10 @@ EPISODE_RESULT = ("episode_reward_mean", "episode_reward_sum", "episodes_done") 
 
 
 class EvalArgs(C.Structure):
-    """``sigmaenv_eval_args_t`` (sigmaenv_eval_create): the trace's capacity in frames; ``debug_frames0`` is a test hook (the frame count a reset starts from)."""
+    """``sigmaenv_eval_args_t`` (sigmaenv_eval_create): the trace's capacity in frames; ``debug_frames0`` is a test hook (the frame count a reset starts from);
+    ``study`` = 1 makes a study evaluator (the word was reserved and zero)."""
 
-    _fields_ = [("trace_frames", C.c_int32), ("debug_frames0", C.c_int32), ("reserved", C.c_int32 * 6)]
+    _fields_ = [("trace_frames", C.c_int32), ("debug_frames0", C.c_int32), ("study", C.c_int32), ("reserved", C.c_int32 * 5)]
 
 
 class EvalSrc(C.Structure):
@@ -129,10 +130,33 @@ class EvalSrc(C.Structure):
     _fields_ = [("state", C.c_void_p), ("dist_ref", C.c_void_p), ("col_agents", C.c_void_p), ("col_flags", C.c_void_p), ("reserved", C.c_int32 * 4)]
 
 
+class EvalStudySrc(C.Structure):
+    """``sigmaenv_eval_study_src_t`` (sigmaenv_eval_accumulate_study): optional device pointers in place of the applied action, the nominal action, the reward info
+    and the timer, and the flag of the frame after the reset."""
+
+    _fields_ = [("applied", C.c_void_p), ("nominal", C.c_void_p), ("reward_info", C.c_void_p), ("timer", C.c_void_p), ("initial", C.c_int32), ("reserved", C.c_int32 * 3)]
+
+
 EVAL_SUM_SPEED, EVAL_SUM_DREF, EVAL_N_AA, EVAL_N_AL, EVAL_FRAMES, EVAL_TRACE, EVAL_FRAMES_HOST = range(7)  # SIGMAENV_EVAL_*: what sigmaenv_eval_get copies
 EVL_MAX_TERMS, EVL_TRACE_COLS = 1 << 24, 8  # sigmaenv_eval.h
 EVAL_METRICS = ("average_speed", "collision_rate_with_agents", "collision_rate_with_lanelets", "distance_ref_average")  # metrics[:, 0 .. 3]: evaluation_base.py:205-217
 EVAL_COUNTS = ("n_collision_frames_with_agents", "n_collision_frames_with_lanelets", "frames")  # counts[:, 0 .. 2]
+EVAL_STUDY_SUMS, EVAL_STUDY_N_ACT, EVAL_STUDY_CARRY, EVAL_STUDY_TIMER0 = range(7, 11)  # SIGMAENV_EVAL_STUDY_*
+EVAL_STUDY_METRICS = ("total_reward", "event_reward", "comfort_reward", "cbf_activation_degree", "cbf_activation_rate", "task_success_rate")  # evaluation_itsc26.py:926-1035, :1450-1458
+EVAL_STUDY_COUNTS = ("n_activated", "num_task_tries", "task_success_times", "frames")  # study counts[:, 0 .. 3]
+EVAL_STUDY_SUM_NAMES = ("sum_event", "sum_a2", "sum_j2", "sum_dv", "sum_ds", "sum_av", "sum_as")  # the rows of EVAL_STUDY_SUMS (EVL_S_*)
+EVL_REW_ROWS = (1, 7, 8)  # rew_reach_goal, rew_collide_other_agents, rew_collide_lane in REWARD_INFO_FIELDS
+
+
+def nominal_from_cbf(parameters) -> bool:
+    """``evl_nominal_from_cbf`` (csrc/sigmaenv_eval.h) asked of a ``Parameters``: does ``BUF_CBF_NOMINAL`` hold the nominal action -- a CBF controller in the loop
+    (training or testing) that solves the QP (cbf_qp.py:1315-1379) -- or does the applied action stand for it (road_traffic.py:1522-1540)?  This is what the reference's ``info()`` does, and what ``scenario._build_views`` mirrors.
+    The library asks the same rule of a HANDLE -- a QP reward method with the CBF tables attached, i.e. what its rollout chain launches -- and the two can disagree:
+    ``rew_method="cbf"`` with ``is_solve_qp`` and ``cbf_attach()`` but neither ``is_using_cbf_*`` gives the nominal buffer there and the applied action here; a
+    handle whose ``cbf_attach()`` was never called, the opposite.  The evaluator follows the handle, because the chain wrote the buffers it reads."""
+    return bool((parameters.is_using_cbf_training or parameters.is_using_cbf_testing) and parameters.is_solve_qp)
+
+
 EVAL_TRACE_FIELDS = ("x", "y", "vx", "vy", "distance_ref", "speed", "is_collision_with_agents", "is_collision_with_lanelets")  # a trace row
 
 
@@ -360,6 +384,8 @@ _PRODUCT_ONLY = {
     "eval_finish": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "eval_attach": (C.c_int, [C.c_void_p, C.c_void_p]),
     "eval_get": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
+    "eval_accumulate_study": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(EvalSrc), C.POINTER(EvalStudySrc)]),
+    "eval_study_finish": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
 

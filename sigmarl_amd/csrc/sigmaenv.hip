@@ -2531,13 +2531,14 @@ extern "C" int sigmaenv_cbf_qp(sigmaenv_t* h, const float* actions, float* actio
 // sigmaenv_eval_accumulate -> sigmaenv_auto_reset -- the same action, record target and (seed, counter) -- so that the evaluator sees the step's outcome before the
 // re-placements clear it; the header promises the same end state and record as the fused launch, bit for bit.  Without an attachment, and for every other caller,
 // nothing changes.
-static int eval_accumulate_impl(sigmaenv* h, sigmaenv_eval* ev, const sigmaenv_eval_src_t* src);  // sigmaenv_eval.inc
+static int eval_accumulate_impl(sigmaenv* h, sigmaenv_eval* ev, const sigmaenv_eval_src_t* src, const sigmaenv_eval_study_src_t* ssrc);  // sigmaenv_eval.inc
+static bool eval_nominal_from_cbf(const sigmaenv* h);  // sigmaenv_eval.inc: does the chain run the CBF-QP (and SIGMAENV_BUF_CBF_NOMINAL hold the nominal action)?
 static int launch_cbf_then_step(sigmaenv* h, StepLaunch l, bool for_rollout = false) {
   if (!h || !l.actions) return SIGMAENV_EINVAL;
   if ((h->cfg.rew_flags & SIGMAENV_REW_CBF) && h->cbf_seg4) {
     const int rc = sigmaenv_cbf_rewards(h, l.actions, nullptr);
     if (rc) return rc;
-  } else if ((h->cfg.rew_flags & SIGMAENV_REW_CBF_QP) && h->cbf_seg4) {
+  } else if (eval_nominal_from_cbf(h)) {
     const int rc = sigmaenv_cbf_qp(h, l.actions, (float*)h->cbf_safe, nullptr, nullptr);
     if (rc) return rc;
     if (h->cbf_cfg.is_apply_cbf_action || h->cbf_cfg.is_grouping) l.actions = (const float*)h->cbf_safe;
@@ -2545,7 +2546,7 @@ static int launch_cbf_then_step(sigmaenv* h, StepLaunch l, bool for_rollout = fa
   if (for_rollout && h->eval_attached) {
     int rc = launch_step(h, {l.actions, l.slab, 0, 0, 0, 0});  // sigmaenv_step
     if (rc) return rc;
-    rc = eval_accumulate_impl(h, h->eval_attached, nullptr);
+    rc = eval_accumulate_impl(h, h->eval_attached, nullptr, nullptr);  // (a study evaluator takes a study frame: sigmaenv_eval_accumulate_study with no override)
     if (rc) return rc;
     return l.path_count != 0 ? sigmaenv_auto_reset(h, l.seed, l.counter, l.path_first, l.path_count) : SIGMAENV_OK;
   }

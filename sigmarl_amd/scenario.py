@@ -359,7 +359,7 @@ class ScenarioRoadTraffic(BaseScenario):
         # with a CBF controller in the loop (training or testing) world_state.nominal_action_* is what CBFQP left behind
         # (cbf_qp.py:1315-1379); without one info() mirrors the applied action (road_traffic.py:1522-1540)
         pp = self.parameters
-        qp = bool((pp.is_using_cbf_training or pp.is_using_cbf_testing) and pp.is_solve_qp)
+        qp = capi.nominal_from_cbf(pp)
         self.world_state = SimpleNamespace(
             distances=distances, collisions=collisions, ref_paths_agent_related=ref_paths, vertices=e.buffer(capi.BUF_VERTICES), world=self._world,
             nominal_action_vel=(nom if qp else act)[..., 0], nominal_action_steer=(nom if qp else act)[..., 1],

@@ -5,6 +5,12 @@
   accumulate   ``sigmaenv_eval_accumulate`` alone, per launch
   torch        the same frame reduced with torch on the env's buffer views: the norm of (vx, vy) summed, dist_ref summed, the two ``any`` flags, added into [B]
                accumulators (fp32 sums: what the obvious host loop would write)
+  attached_study    ``attached`` with a study evaluator (``Evaluator(env, study=True)``): the same three launches, the accumulate one being the study instantiation
+  accumulate_study  ``sigmaenv_eval_accumulate_study`` alone, per launch
+  torch_study       what the study launch replaces: per frame, the copies of the applied and nominal action and the three event-reward rows into stacked tensors
+                    ``[STEPS, ..]``, and -- once per STEPS frames, its cost spread over them -- the reference's ``compute_total_reward`` and
+                    ``compute_cbf_activation_percentage`` (evaluation_itsc26.py:926-1035) in fp32 torch on the stacked tensors, reduced per env
+``ROUTES`` (comma-separated) picks routes; the study routes are left out on a build of the library from before them (an A/B baseline through ``SIGMAENV_LIB``).
 One process; one untimed pass of every route, then REPS (default 7) repetitions with the routes alternating; every figure is the host's wall clock around STEPS
 (default 256) steps / CALLS (default 2048) launches that end in a device synchronise, divided by their number.  Best, median and spread (max - min) per route.
 A report: no test asserts a time.  Writes profiles/eval_timing.txt (or the path given)."""
@@ -45,6 +51,11 @@ def main():
     torch.manual_seed(0)
     actor = Actor(make_mlp(env.D), low=LOW, high=HIGH)
     ev = Evaluator(env)
+    has_study = hasattr(env.lib, "eval_accumulate_study")
+    sev = Evaluator(env, study=True) if has_study else None
+    applied, nominal, rinfo = (env.buffer(w) for w in (capi.BUF_ACTION, capi.BUF_CBF_NOMINAL, capi.BUF_REWARD_INFO))
+    stack = {k: torch.zeros((STEPS, B, N) + tail, device="cuda") for k, tail in (("applied", (2,)), ("nominal", (2,)), ("event", (3,)))}
+    study_out = {}
     state, dist_ref, col_agents, col_flags = (env.buffer(w) for w in (capi.BUF_STATE, capi.BUF_DIST_REF, capi.BUF_COL_AGENTS, capi.BUF_COL_FLAGS))
     acc = {k: torch.zeros(B, device="cuda") for k in ("speed", "dref", "aa", "al")}
     counter = {"k": 0}
@@ -71,7 +82,40 @@ def main():
             acc["aa"] += col_agents.flatten(1).any(dim=-1)
             acc["al"] += col_flags[..., 0].any(dim=-1)
 
+    def attached_study():
+        sev.reset()
+        with sev.attached():
+            actor.rollout(env, STEPS, seed=1, counter0=counter["k"], deterministic=True)
+        counter["k"] += STEPS
+
+    def accumulate_study():
+        sev.reset()
+        for _ in range(CALLS):
+            sev.accumulate()
+
+    def torch_study():
+        rows = list(capi.EVL_REW_ROWS)
+        for t in range(STEPS):
+            stack["applied"][t].copy_(applied)
+            stack["nominal"][t].copy_(nominal)
+            stack["event"][t].copy_(rinfo[rows].permute(1, 2, 0))
+        v, nv = stack["applied"][..., 0], stack["nominal"][..., 0]  # [T, B, N]
+        d, nd = stack["applied"][..., 1], stack["nominal"][..., 1]
+        event = stack["event"].sum(dim=-1).sum(dim=(0, 2))
+        zero = torch.zeros_like(v[:1])
+        a = torch.cat([zero, (v[1:] - v[:-1]) / 0.1], dim=0)
+        jerk = torch.cat([zero, (a[1:] - a[:-1]) / 0.1], dim=0)
+        comfort = -0.2 * (a.abs() / 3.0).pow(2).mean(dim=(0, 2)) + -0.2 * (jerk.abs() / 20.0).pow(2).mean(dim=(0, 2))
+        d_vel, d_steer = v - nv, d - nd
+        degree = 0.5 * (d_vel.abs().mean(dim=(0, 2)) / (v.abs().mean(dim=(0, 2)) + 1e-9) + d_steer.abs().mean(dim=(0, 2)) / (d.abs().mean(dim=(0, 2)) + 1e-9))
+        rate = ((d_vel.abs() > 1e-9) | (d_steer.abs() > 1e-9)).float().mean(dim=(0, 2))
+        study_out["torch"] = (event + comfort, 100 * degree, 100 * rate)
+
     routes = {"fused": (fused, STEPS, "step"), "attached": (attached, STEPS, "step"), "accumulate": (accumulate, CALLS, "launch"), "torch": (torch_frame, CALLS, "frame")}
+    if has_study:
+        routes.update({"attached_study": (attached_study, STEPS, "step"), "accumulate_study": (accumulate_study, CALLS, "launch"), "torch_study": (torch_study, STEPS, "frame")})
+    if os.environ.get("ROUTES"):
+        routes = {k: routes[k] for k in os.environ["ROUTES"].split(",") if k in routes}
     for fn, _, _ in routes.values():  # untimed: allocations, code loading
         fn()
     torch.cuda.synchronize()
@@ -84,19 +128,26 @@ def main():
              f"wall clock around {STEPS} rollout steps / {CALLS} launches ending in a device synchronise, microseconds per unit", ""]
     for k, (_, n, unit) in routes.items():
         v = us[k]
-        lines.append(f"{k:<11} us/{unit:<7} best {min(v):9.2f}  median {statistics.median(v):9.2f}  spread {max(v) - min(v):8.2f}   all " + " ".join(f"{x:.2f}" for x in v))
-    cost = best["attached"] - best["fused"]
-    lines += ["", f"attachment over the fused step: {cost:+.2f} us/step ({100.0 * cost / best['fused']:+.1f} % of the fused step's {best['fused']:.2f} us; best of {REPS}); "
-                  f"the fused route is measured in this run, on this build, and is the code path of a rollout without an evaluator",
-              f"accumulate launch against the torch expression on the same buffers: {best['accumulate']:.2f} us vs {best['torch']:.2f} us per frame: "
-              + ("the launch is %.1fx faster" % (best["torch"] / best["accumulate"]) if best["accumulate"] < best["torch"] else "the launch does NOT beat torch here")]
+        lines.append(f"{k:<16} us/{unit:<7} best {min(v):9.2f}  median {statistics.median(v):9.2f}  spread {max(v) - min(v):8.2f}   all " + " ".join(f"{x:.2f}" for x in v))
+    if {"attached_study", "attached", "accumulate_study", "accumulate", "torch_study"} <= set(best):
+        lines += ["", f"study instantiation over the plain one: {best['accumulate_study'] - best['accumulate']:+.2f} us per launch ({best['accumulate_study']:.2f} vs {best['accumulate']:.2f}), "
+                      f"{best['attached_study'] - best['attached']:+.2f} us per attached step ({best['attached_study']:.2f} vs {best['attached']:.2f}); best of {REPS}",
+                  f"study launch against what it replaces (per-step copies + the reference's two functions in torch on the stacked tensors): {best['accumulate_study']:.2f} us vs "
+                  f"{best['torch_study']:.2f} us per frame"]
+    if {"attached", "fused", "accumulate", "torch"} <= set(best):
+        cost = best["attached"] - best["fused"]
+        lines += ["", f"attachment over the fused step: {cost:+.2f} us/step ({100.0 * cost / best['fused']:+.1f} % of the fused step's {best['fused']:.2f} us; best of {REPS}); "
+                      f"the fused route is measured in this run, on this build, and is the code path of a rollout without an evaluator",
+                  f"accumulate launch against the torch expression on the same buffers: {best['accumulate']:.2f} us vs {best['torch']:.2f} us per frame: "
+                  + ("the launch is %.1fx faster" % (best["torch"] / best["accumulate"]) if best["accumulate"] < best["torch"] else "the launch does NOT beat torch here")]
     text = "\n".join(lines) + "\n"
     print(text)
     os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
     with open(path, "w") as f:
         f.write(text)
-    for x in (ev, actor, env):
-        x.close()
+    for x in (sev, ev, actor, env):
+        if x is not None:
+            x.close()
 
 
 if __name__ == "__main__":
