@@ -241,70 +241,15 @@ static int mlp32_grad_load(sigmaenv_t* h, sigmaenv_mlp32* m, const float* const*
   return SIGMAENV_OK;
 }
 
-static int mlp32_grad_rows(sigmaenv_t* h, const sigmaenv_mlp32* m, const char* what, const float* in, int32_t rows_per_block, int64_t row_stride, int32_t n_blocks,
-                           int64_t block_stride, Mlp32Rows* rw, int64_t* rows, const Mlp32Pad* pad = nullptr) {
-  if (rows_per_block < 0 || n_blocks < 0 || (int64_t)rows_per_block * n_blocks > INT32_MAX) { h->err = std::string(what) + ": negative counts or more than 2^31 - 1 rows"; return SIGMAENV_EINVAL; }
-  *rows = (int64_t)rows_per_block * n_blocks;
-  if (pad && (pad->src < 1 || pad->dst < pad->src || m->in_dim % pad->dst)) { h->err = std::string(what) + ": 1 <= seg_src <= seg_dst, and seg_dst divides the network's input width"; return SIGMAENV_EINVAL; }
-  if (*rows == 0) return SIGMAENV_OK;
-  const int64_t width = pad ? (int64_t)(m->in_dim / pad->dst) * pad->src : m->in_dim;  // the row in memory
-  if (!in || ((uintptr_t)in & 3) || row_stride < width || (n_blocks > 1 && block_stride < 0)) {
-    h->err = std::string(what) + ": a null input or one that is not 4-byte aligned, row_stride below the network's input width or a negative block_stride";
-    return SIGMAENV_EINVAL;
-  }
-  rw->rpb = rows_per_block;
-  rw->row_stride = row_stride;
-  rw->block_stride = block_stride;
-  rw->aligned = !pad && ((uintptr_t)in & 15) == 0 && (row_stride & 3) == 0 && (block_stride & 3) == 0;
-  return SIGMAENV_OK;
-}
-
-// the indexed entry points' own arguments: the minibatch takes the place of the record's blocks in the row count; *ix is what the kernels get
-static int mlp32_grad_index(sigmaenv_t* h, const char* what, int32_t n_blocks, int64_t block_stride, const int32_t* index, int32_t n_index, Mlp32Index* ix) {
-  if (n_blocks < 0 || n_index < 0 || block_stride < 0) { h->err = std::string(what) + ": negative n_blocks, index length or block_stride"; return SIGMAENV_EINVAL; }
-  if (n_index > 0 && (!index || ((uintptr_t)index & 3))) { h->err = std::string(what) + ": a null index or one that is not 4-byte aligned"; return SIGMAENV_EINVAL; }
-  ix->index = index;
-  ix->n_blocks = n_blocks;
-  return SIGMAENV_OK;
-}
-
 // index == nullptr: the rows' blocks are the record's blocks 0 .. n_blocks - 1 (sigmaenv_mlp32_forward_save); else the n_index blocks index[.] of its n_blocks
 static int mlp32_forward_save_impl(sigmaenv_t* h, sigmaenv_mlp32* m, const char* what, const float* in, int32_t rows_per_block, int64_t row_stride, int32_t n_blocks,
                                    int64_t block_stride, const int32_t* index, int32_t n_index, float* out, float* acts, const Mlp32Pad* pad = nullptr) {
   if (!h) return SIGMAENV_EINVAL;
   if (!m) { h->err = std::string(what) + ": null network handle"; return SIGMAENV_EINVAL; }
-  if (pad && !index) { h->err = std::string(what) + ": padded rows are built for the indexed forward"; return SIGMAENV_EINVAL; }
-  Mlp32Rows rw{};
-  Mlp32Index ix{};
-  int64_t rows = 0;
-  if (index || n_index)
-    if (const int rc = mlp32_grad_index(h, what, n_blocks, block_stride, index, n_index, &ix)) return rc;
-  if (const int rc = mlp32_grad_rows(h, m, what, in, rows_per_block, row_stride, ix.index ? n_index : n_blocks, block_stride, &rw, &rows, pad)) return rc;
-  if (rows == 0) return SIGMAENV_OK;
-  if (!out || !acts || ((uintptr_t)out & 3) || ((uintptr_t)acts & 15)) { h->err = std::string(what) + ": null out / acts, or acts not 16-byte aligned"; return SIGMAENV_EINVAL; }
-  HIPCHK(h, hipSetDevice(h->device));
-  const void* kfn = pad ? reinterpret_cast<const void*>(sigmaenv_mlp32_kernel<true, true, true, true>)
-                        : ix.index ? reinterpret_cast<const void*>(sigmaenv_mlp32_kernel<true, true, true>) : reinterpret_cast<const void*>(sigmaenv_mlp32_kernel<true, true>);
-  HIPCHK(h, hipFuncSetAttribute(kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)m->smem));
-  const dim3 grid((unsigned)((rows + MLP32_ROWS - 1) / MLP32_ROWS));
-  if (pad) {
-#ifdef SIGMAENV_PROFILE
-    hipLaunchKernelGGL((sigmaenv_mlp32_kernel<true, true, true, true>), grid, dim3(256), m->smem, h->stream, m->w, in, (int)rows, m->in_dim, out, rw, acts, ix, *pad, (unsigned long long*)nullptr, 0);
-#else
-    hipLaunchKernelGGL((sigmaenv_mlp32_kernel<true, true, true, true>), grid, dim3(256), m->smem, h->stream, m->w, in, (int)rows, m->in_dim, out, rw, acts, ix, *pad);
-#endif
-    HIPCHK(h, hipGetLastError());
-    return SIGMAENV_OK;
-  }
-#ifdef SIGMAENV_PROFILE
-  if (ix.index) hipLaunchKernelGGL((sigmaenv_mlp32_kernel<true, true, true>), grid, dim3(256), m->smem, h->stream, m->w, in, (int)rows, m->in_dim, out, rw, acts, ix, Mlp32Pad{}, (unsigned long long*)nullptr, 0);
-  else hipLaunchKernelGGL((sigmaenv_mlp32_kernel<true, true>), grid, dim3(256), m->smem, h->stream, m->w, in, (int)rows, m->in_dim, out, rw, acts, ix, Mlp32Pad{}, (unsigned long long*)nullptr, 0);
-#else
-  if (ix.index) hipLaunchKernelGGL((sigmaenv_mlp32_kernel<true, true, true>), grid, dim3(256), m->smem, h->stream, m->w, in, (int)rows, m->in_dim, out, rw, acts, ix, Mlp32Pad{});
-  else hipLaunchKernelGGL((sigmaenv_mlp32_kernel<true, true>), grid, dim3(256), m->smem, h->stream, m->w, in, (int)rows, m->in_dim, out, rw, acts, ix, Mlp32Pad{});
-#endif
-  HIPCHK(h, hipGetLastError());
-  return SIGMAENV_OK;
+  Mlp32View v;
+  if (const int rc = mlp32_view(h, m, what, in, rows_per_block, row_stride, n_blocks, block_stride, index, n_index, pad, &v)) return rc;
+  if (v.rows > 0 && (!out || !acts || ((uintptr_t)out & 3) || ((uintptr_t)acts & 15))) { h->err = std::string(what) + ": null out / acts, or acts not 16-byte aligned"; return SIGMAENV_EINVAL; }
+  return mlp32_launch(h, m, v, out, acts, nullptr, nullptr);  // (no rows: OK, nothing is launched)
 }
 
 extern "C" int sigmaenv_mlp32_forward_save(sigmaenv_t* h, sigmaenv_mlp32* m, const float* in, int32_t rows_per_block, int64_t row_stride, int32_t n_blocks, int64_t block_stride,
@@ -336,7 +281,6 @@ static int mlp32_backward_impl(sigmaenv_t* h, sigmaenv_mlp32* m, const char* wha
   if (!h) return SIGMAENV_EINVAL;
   const std::string what(what_c);
   if (!m) { h->err = what + ": null network handle"; return SIGMAENV_EINVAL; }
-  if (pad && !index) { h->err = what + ": padded rows are built for the indexed backward"; return SIGMAENV_EINVAL; }
   const int n = m->w.n_layers;
   if (!grad_w || !grad_b) { h->err = what + ": null gradient pointer array"; return SIGMAENV_EINVAL; }
   for (int l = 0; l < n; ++l)
@@ -344,12 +288,10 @@ static int mlp32_backward_impl(sigmaenv_t* h, sigmaenv_mlp32* m, const char* wha
       h->err = what + ": layer " + std::to_string(l) + ": a null gradient tensor or one that is not 4-byte aligned";
       return SIGMAENV_EINVAL;
     }
-  Mlp32Rows rw{};
-  Mlp32Index ix{};
-  int64_t rows = 0;
-  if (index || n_index)
-    if (const int rc = mlp32_grad_index(h, what_c, n_blocks, block_stride, index, n_index, &ix)) return rc;
-  if (const int rc = mlp32_grad_rows(h, m, what_c, in, rows_per_block, row_stride, ix.index ? n_index : n_blocks, block_stride, &rw, &rows, pad)) return rc;
+  Mlp32View v;
+  if (const int rc = mlp32_view(h, m, what_c, in, rows_per_block, row_stride, n_blocks, block_stride, index, n_index, pad, &v)) return rc;
+  if (v.padded && !v.indexed) { h->err = what + ": padded rows are built for the indexed backward"; return SIGMAENV_EINVAL; }  // (no such dW instantiation)
+  const int64_t rows = v.rows;
   if (rows > 0 && (!acts || !dout || !workspace || ((uintptr_t)acts & 15) || ((uintptr_t)dout & 3) || ((uintptr_t)workspace & 15))) {
     h->err = what + ": null acts / dout / workspace, or acts / workspace not 16-byte aligned";
     return SIGMAENV_EINVAL;
@@ -373,12 +315,13 @@ static int mlp32_backward_impl(sigmaenv_t* h, sigmaenv_mlp32* m, const char* wha
       grad::DwLayer p{};
       p.g = l == n - 1 ? dout : delta + (size_t)l * (size_t)R * MLP32_H;
       p.gs = l == n - 1 ? F : MLP32_H;
-      p.a = l == 0 ? in : acts + (size_t)(l - 1) * (size_t)R * MLP32_H;
+      p.a = l == 0 ? v.in : acts + (size_t)(l - 1) * (size_t)R * MLP32_H;
       p.pw = pw; p.pb = pb; p.F = F; p.K = K; p.R = R; p.len = grad::range_len(rows);
       const dim3 grid((unsigned)(((F + GRAD_BLK - 1) / GRAD_BLK) * ((K + GRAD_BLK - 1) / GRAD_BLK)), (unsigned)ranges);
-      if (l == 0 && pad) hipLaunchKernelGGL((grad::sigmaenv_mlp32_dw_kernel<true, true, true>), grid, dim3(256), 0, h->stream, p, rw, ix, *pad);
-      else if (l == 0 && ix.index) hipLaunchKernelGGL((grad::sigmaenv_mlp32_dw_kernel<true, true>), grid, dim3(256), 0, h->stream, p, rw, ix, Mlp32Pad{});
-      else if (l == 0) hipLaunchKernelGGL(grad::sigmaenv_mlp32_dw_kernel<true>, grid, dim3(256), 0, h->stream, p, rw, Mlp32Index{}, Mlp32Pad{});
+      // (layer 0 reads the input rows where the view says they are; its three instantiations get the view's structs, zeros where not in force)
+      if (l == 0 && v.padded) hipLaunchKernelGGL((grad::sigmaenv_mlp32_dw_kernel<true, true, true>), grid, dim3(256), 0, h->stream, p, v.rw, v.ix, v.pd);
+      else if (l == 0 && v.indexed) hipLaunchKernelGGL((grad::sigmaenv_mlp32_dw_kernel<true, true>), grid, dim3(256), 0, h->stream, p, v.rw, v.ix, v.pd);
+      else if (l == 0) hipLaunchKernelGGL(grad::sigmaenv_mlp32_dw_kernel<true>, grid, dim3(256), 0, h->stream, p, v.rw, v.ix, v.pd);
       else hipLaunchKernelGGL(grad::sigmaenv_mlp32_dw_kernel<false>, grid, dim3(256), 0, h->stream, p, Mlp32Rows{}, Mlp32Index{}, Mlp32Pad{});
       HIPCHK(h, hipGetLastError());
     }

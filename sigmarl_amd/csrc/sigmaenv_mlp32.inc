@@ -80,6 +80,18 @@ __device__ __forceinline__ float mlp32_pad_load(const float* __restrict__ row, i
   const int a = k / pd.dst, j = k - a * pd.dst;
   return j < pd.src ? row[a * pd.src + j] : 0.0f;
 }
+// Host side: where the rows of one call are -- the three structs above as the kernels get them (zeros where not in force) and which of them are in force.  Every
+// row-taking entry point fills one from its raw arguments (mlp32_view, which holds all the checks); the forward's one launch site (mlp32_launch) and the backward's
+// choice of the dW kernel read it.  by_rows false: `in` is dense [rows][in_dim], 16-byte aligned (mlp32_forward_impl).
+struct Mlp32View {
+  const char* what;  // the entry point's name, the prefix of its messages
+  const float* in;
+  int rows;
+  Mlp32Rows rw;
+  Mlp32Index ix;
+  Mlp32Pad pd;
+  bool by_rows, indexed, padded;
+};
 // Four (eight) floats at a 4-byte-aligned address p from 16-byte-ALIGNED loads: the granule that holds p[0] and the following one (two), each only when it holds
 // one of the wanted floats -- so no load touches a granule without a valid float, and an aligned granule never crosses a page --, the wanted floats selected by
 // s = the offset of p in its granule.  A row's lanes read consecutive granules: the requests coalesce as those of the aligned path do (3 loads per 8 floats, not 2).
@@ -152,9 +164,11 @@ __device__ __forceinline__ void mlp32_tile_k256(const float4* __restrict__ wa, c
 // in: [R][in_dim] row-major fp32 (in_dim <= the padded K of layer 0); out: [R][F_last]
 #ifdef SIGMAENV_PROFILE
 #define MLP32_TS_ARG , unsigned long long* __restrict__ ts, int stagger
+#define MLP32_TS_PASS , m->ts, stagger  /* what mlp32_launch passes for MLP32_TS_ARG */
 #define MLP32_TS(k) do { if (ts && threadIdx.x == 0) ts[(size_t)blockIdx.x * 16 + (k)] = __builtin_readcyclecounter(); } while (0)
 #else
 #define MLP32_TS_ARG
+#define MLP32_TS_PASS
 #define MLP32_TS(k) do { } while (0)
 #endif
 // ROWS = false: `in` is dense [R][in_dim], 16-byte aligned (sigmaenv_mlp32_forward, the actor forwards, the rollouts; rw is not read); ROWS = true: the rows of a
@@ -167,6 +181,8 @@ __device__ __forceinline__ void mlp32_tile_k256(const float4* __restrict__ wa, c
 // tile are formed once, by the first 64 lanes, into the LDS words the output layer's partial sums use much later; stage() reads them from there.  The other three never
 // read `ix` and keep their figures (profiles/ppo_kernel_resources.txt).
 // PAD (Mlp32Pad): <true, false, false, true> and <true, true, true, true>, the padded forms of the record rows and of the indexed saving forward; the others never read `pd`.
+// These six and the three of sigmaenv_mlp32s_kernel are chosen and launched in ONE place, mlp32_launch below, from the call's Mlp32View: every launch passes the view's
+// rw / ix / pd and the caller's acts, which are zeros / null wherever an instantiation does not read them.
 template <bool ROWS, bool SAVE = false, bool INDEXED = false, bool PAD = false>
 __global__ void __launch_bounds__(256, 2) sigmaenv_mlp32_kernel(Mlp32Weights mw, const float* __restrict__ in, int R, int in_dim, float* __restrict__ out, Mlp32Rows rw,
                                                                 float* __restrict__ acts, Mlp32Index ix, Mlp32Pad pd MLP32_TS_ARG) {
@@ -506,139 +522,151 @@ extern "C" int sigmaenv_mlp32_set_mode(sigmaenv_mlp32* m, int32_t mode) {
 }
 extern "C" int sigmaenv_mlp32_get_mode(const sigmaenv_mlp32* m) { return m ? m->mode : SIGMAENV_EINVAL; }
 
-// out[rows, out_dim] := mlp(in[rows, in_dim]) in fp32 (device pointers), enqueued on the handle's stream
-static int mlp32_forward_impl(sigmaenv_t* h, sigmaenv_mlp32* m, const float* in, int32_t rows, float* out, const Mlp32sHead* head, bool* head_done, const Mlp32Rows* rw = nullptr);
-extern "C" int sigmaenv_mlp32_forward(sigmaenv_t* h, sigmaenv_mlp32* m, const float* in, int32_t rows, float* out) { return mlp32_forward_impl(h, m, in, rows, out, nullptr, nullptr); }
-// The network on rows that are not dense: row r = t * rows_per_block + b at in + t * block_stride + b * row_stride (floats), 4-byte alignment suffices; out is
-// dense.  The staging of the input tile is the only difference to sigmaenv_mlp32_forward (the *_rows_kernel instantiations): same bits per row in both modes.
-extern "C" int sigmaenv_mlp32_forward_rows(sigmaenv_t* h, sigmaenv_mlp32* m, const float* in, int32_t rows_per_block, int64_t row_stride, int32_t n_blocks, int64_t block_stride,
-                                           float* out) {
-  if (!h || !m || !in || !out || rows_per_block < 0 || n_blocks < 0) return SIGMAENV_EINVAL;
-  if ((int64_t)rows_per_block * n_blocks > INT32_MAX) { h->err = "mlp32_forward_rows: more than 2^31 - 1 rows"; return SIGMAENV_EINVAL; }
-  if (rows_per_block == 0 || n_blocks == 0) return SIGMAENV_OK;
-  if (row_stride < m->in_dim || ((uintptr_t)in & 3) || (n_blocks > 1 && block_stride < 0)) {
-    h->err = "mlp32_forward_rows: row_stride below the network's input width, a negative block_stride or an input that is not 4-byte aligned";
+// The rows of a record, from an entry point's raw arguments: row r = t * rows_per_block + b at in + t * block_stride + b * row_stride (floats), 4-byte alignment
+// suffices.  index / n_index (nullptr, 0: none): block t of the rows is block index[t] of the record's n_blocks, the minibatch takes the place of the record's blocks
+// in the row count.  pad (nullptr: none): the row in memory holds in_dim / dst segments of src floats.  Every refusal is made here, before any launch, with a message
+// that starts with `what`; no row is not an error, and then `in` is not looked at.
+static int mlp32_view(sigmaenv_t* h, const sigmaenv_mlp32* m, const char* what, const float* in, int32_t rows_per_block, int64_t row_stride, int32_t n_blocks, int64_t block_stride,
+                      const int32_t* index, int32_t n_index, const Mlp32Pad* pad, Mlp32View* v) {
+  *v = Mlp32View{};
+  v->what = what;
+  v->in = in;
+  v->by_rows = true;
+  if (index || n_index) {
+    if (n_blocks < 0 || n_index < 0 || block_stride < 0) { h->err = std::string(what) + ": negative n_blocks, index length or block_stride"; return SIGMAENV_EINVAL; }
+    if (n_index > 0 && (!index || ((uintptr_t)index & 3))) { h->err = std::string(what) + ": a null index or one that is not 4-byte aligned"; return SIGMAENV_EINVAL; }
+    v->indexed = true;  // (index is not null here)
+    v->ix.index = index;
+    v->ix.n_blocks = n_blocks;
+  }
+  const int32_t blocks = v->indexed ? n_index : n_blocks;
+  if (rows_per_block < 0 || blocks < 0 || (int64_t)rows_per_block * blocks > INT32_MAX) { h->err = std::string(what) + ": negative counts or more than 2^31 - 1 rows"; return SIGMAENV_EINVAL; }
+  if (pad) {
+    if (pad->src < 1 || pad->dst < pad->src || m->in_dim % pad->dst) { h->err = std::string(what) + ": 1 <= seg_src <= seg_dst, and seg_dst divides the network's input width"; return SIGMAENV_EINVAL; }
+    v->padded = true;
+    v->pd = *pad;
+  }
+  v->rows = rows_per_block * blocks;
+  if (v->rows == 0) return SIGMAENV_OK;
+  const int64_t width = pad ? (int64_t)(m->in_dim / pad->dst) * pad->src : m->in_dim;  // the row in memory
+  if (!in || ((uintptr_t)in & 3) || row_stride < width || (blocks > 1 && block_stride < 0)) {
+    h->err = std::string(what) + ": a null input or one that is not 4-byte aligned, row_stride below the row's width in memory or a negative block_stride";
     return SIGMAENV_EINVAL;
   }
-  Mlp32Rows rw;
-  rw.rpb = rows_per_block;
-  rw.row_stride = row_stride;
-  rw.block_stride = block_stride;
-  rw.aligned = ((uintptr_t)in & 15) == 0 && (row_stride & 3) == 0 && (block_stride & 3) == 0;
-  return mlp32_forward_impl(h, m, in, rows_per_block * n_blocks, out, nullptr, nullptr, &rw);
+  v->rw.rpb = rows_per_block;
+  v->rw.row_stride = row_stride;
+  v->rw.block_stride = block_stride;
+  // (16-byte loads as in the dense kernels; the padded instantiations stage column by column and do not read it)
+  v->rw.aligned = !pad && ((uintptr_t)in & 15) == 0 && (row_stride & 3) == 0 && (block_stride & 3) == 0;
+  return SIGMAENV_OK;
+}
+
+enum {  // the forward's instantiations: a row of the LDS table below each
+  MLP32_K_DENSE, MLP32_K_ROWS, MLP32_K_ROWS_PAD, MLP32_K_SAVE, MLP32_K_SAVE_INDEXED, MLP32_K_SAVE_INDEXED_PAD,  // sigmaenv_mlp32_kernel
+  MLP32_KS_DENSE, MLP32_KS_ROWS, MLP32_KS_ROWS_PAD,                                                             // sigmaenv_mlp32s_kernel
+  MLP32_N_KERNELS
+};
+// The dynamic-LDS limit is a per-kernel attribute -- PER DEVICE (ADVICE r5: a second GPU driven from the same process never got the opt-in beyond 64 KB): raised
+// when a call needs more than what was set for this kernel on this device before (not once per forward; models of different input widths coexist); atomics:
+// handles may be driven from several threads
+static int mlp32_lds_limit(sigmaenv_t* h, int kernel, const void* kfn, size_t smem) {
+  static std::atomic<size_t> s_lds_set[MLP32_N_KERNELS][64];
+  std::atomic<size_t>& lds_set = s_lds_set[kernel][h->device >= 0 && h->device < 64 ? h->device : 0];
+  if (smem > 64 * 1024 && smem > lds_set.load(std::memory_order_acquire)) {
+    HIPCHK(h, hipFuncSetAttribute(kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
+    size_t cur = lds_set.load(std::memory_order_relaxed);
+    while (cur < smem && !lds_set.compare_exchange_weak(cur, smem, std::memory_order_release)) {}
+  }
+  return SIGMAENV_OK;
+}
+
+// The network on the rows of `v`, enqueued on the handle's stream: out [rows, out_dim]; acts: the saving forward (sigmaenv_grad.inc), else nullptr.  The ONE place that
+// decides the arithmetic and the instantiation, raises its LDS limit and launches it.
+// head: the actor's distribution head, run as the epilogue of the non-padded split kernels (*head_done = true) -- every other kernel leaves it to the caller's head launch
+static int mlp32_launch(sigmaenv_t* h, sigmaenv_mlp32* m, const Mlp32View& v, float* out, float* acts, const Mlp32sHead* head, bool* head_done) {
+  if (head_done) *head_done = false;
+  if (v.rows == 0) return SIGMAENV_OK;
+  const bool save = acts != nullptr;
+  const bool split = !save && m->mode == SIGMAENV_MLP32_SPLIT;  // (the saving forward is the exact chain whatever mode the network runs in)
+  int k;  // a view that no instantiation serves: -1
+  if (save) k = !v.by_rows || (v.padded && !v.indexed) ? -1 : v.padded ? MLP32_K_SAVE_INDEXED_PAD : v.indexed ? MLP32_K_SAVE_INDEXED : MLP32_K_SAVE;
+  else if (v.indexed) k = -1;
+  else if (split) k = v.padded ? MLP32_KS_ROWS_PAD : v.by_rows ? MLP32_KS_ROWS : MLP32_KS_DENSE;
+  else k = v.padded ? MLP32_K_ROWS_PAD : v.by_rows ? MLP32_K_ROWS : MLP32_K_DENSE;
+  if (k < 0) {
+    h->err = std::string(v.what) + (v.indexed ? ": indexed rows are built for the saving forward" : v.padded ? ": padded rows are built for the indexed forward" : ": the saving forward reads record rows");
+    return SIGMAENV_EINVAL;
+  }
+  Mlp32sHead hd{};
+  if (head && split && !v.padded && m->out_dim == 4) { hd = *head; hd.on = 1; if (head_done) *head_done = true; }
+  HIPCHK(h, hipSetDevice(h->device));
+  size_t smem = split ? m->smem_s : m->smem;
+  const dim3 grid((v.rows + MLP32_ROWS - 1) / MLP32_ROWS);
+#ifdef SIGMAENV_PROFILE
+  if (getenv("SIGMAENV_TIMESTAMPS") && m->ts_groups < (int)grid.x) {
+    if (m->ts) (void)hipFree(m->ts);
+    m->ts = nullptr;
+    if (hipMalloc((void**)&m->ts, (size_t)grid.x * 16 * 8) == hipSuccess) { m->ts_groups = (int)grid.x; (void)hipMemsetAsync(m->ts, 0, (size_t)grid.x * 16 * 8, h->stream); }
+  }
+  if (getenv("SIGMAENV_MLP32_ONE_WG") && smem < 100 * 1024) smem = 100 * 1024;  // diagnostic: one workgroup per CU (more LDS than two can share)
+  const int stagger = getenv("SIGMAENV_MLP32_STAGGER") ? atoi(getenv("SIGMAENV_MLP32_STAGGER")) : 0;
+#endif
+  int slot = -1;  // the SIGMAENV_KERNEL_MLP32 timer brackets the non-saving forwards
+#define MLP32_LAUNCH(kernel, id, ...)                                                                     \
+  case id:                                                                                                \
+    if (const int rc = mlp32_lds_limit(h, id, reinterpret_cast<const void*>(kernel), smem)) return rc;    \
+    if (!save) slot = timer_begin(h, SIGMAENV_KERNEL_MLP32);                                              \
+    hipLaunchKernelGGL(kernel, grid, dim3(256), smem, h->stream, __VA_ARGS__ MLP32_TS_PASS);              \
+    break;
+#define MLP32_EXACT(kernel, id) MLP32_LAUNCH(kernel, id, m->w, v.in, v.rows, m->in_dim, out, v.rw, acts, v.ix, v.pd)
+#define MLP32_SPLIT(kernel, id) MLP32_LAUNCH(kernel, id, m->ws, v.in, v.rows, m->in_dim, out, hd, v.rw, v.pd)
+  switch (k) {  // (the cases' order is the kernels' order in the code object: kept, so that tools/kernel_isa_diff.sh compares a build with an older one kernel by kernel)
+    MLP32_SPLIT((sigmaenv_mlp32s_kernel<true, true>), MLP32_KS_ROWS_PAD)
+    MLP32_EXACT((sigmaenv_mlp32_kernel<true, false, false, true>), MLP32_K_ROWS_PAD)
+    MLP32_SPLIT((sigmaenv_mlp32s_kernel<true>), MLP32_KS_ROWS)
+    MLP32_SPLIT((sigmaenv_mlp32s_kernel<false>), MLP32_KS_DENSE)
+    MLP32_EXACT((sigmaenv_mlp32_kernel<true>), MLP32_K_ROWS)
+    MLP32_EXACT((sigmaenv_mlp32_kernel<false>), MLP32_K_DENSE)
+    MLP32_EXACT((sigmaenv_mlp32_kernel<true, true, true, true>), MLP32_K_SAVE_INDEXED_PAD)
+    MLP32_EXACT((sigmaenv_mlp32_kernel<true, true, true>), MLP32_K_SAVE_INDEXED)
+    MLP32_EXACT((sigmaenv_mlp32_kernel<true, true>), MLP32_K_SAVE)
+  }
+#undef MLP32_SPLIT
+#undef MLP32_EXACT
+#undef MLP32_LAUNCH
+  HIPCHK(h, hipGetLastError());
+  timer_end(h, SIGMAENV_KERNEL_MLP32, slot);
+  return SIGMAENV_OK;
+}
+
+// out[rows, out_dim] := mlp(in[rows, in_dim]) in fp32 (device pointers, `in` dense and 16-byte aligned)
+static int mlp32_forward_impl(sigmaenv_t* h, sigmaenv_mlp32* m, const float* in, int32_t rows, float* out, const Mlp32sHead* head, bool* head_done) {
+  if (head_done) *head_done = false;
+  if (!h || !m || !in || !out || rows < 0) return SIGMAENV_EINVAL;
+  Mlp32View v{};
+  v.what = "mlp32_forward";
+  v.in = in;
+  v.rows = rows;
+  return mlp32_launch(h, m, v, out, nullptr, head, head_done);
+}
+extern "C" int sigmaenv_mlp32_forward(sigmaenv_t* h, sigmaenv_mlp32* m, const float* in, int32_t rows, float* out) { return mlp32_forward_impl(h, m, in, rows, out, nullptr, nullptr); }
+// The network on rows that are not dense (mlp32_view); out is dense.  The staging of the input tile is the only difference to sigmaenv_mlp32_forward: same bits per
+// row in both modes.
+extern "C" int sigmaenv_mlp32_forward_rows(sigmaenv_t* h, sigmaenv_mlp32* m, const float* in, int32_t rows_per_block, int64_t row_stride, int32_t n_blocks, int64_t block_stride,
+                                           float* out) {
+  if (!h || !m || !in || !out || rows_per_block < 0 || n_blocks < 0) return SIGMAENV_EINVAL;  // (this entry point's own: before anything else, without a message, whatever the row count)
+  Mlp32View v;
+  if (const int rc = mlp32_view(h, m, "mlp32_forward_rows", in, rows_per_block, row_stride, n_blocks, block_stride, nullptr, 0, nullptr, &v)) return rc;
+  return mlp32_launch(h, m, v, out, nullptr, nullptr, nullptr);
 }
 // sigmaenv_mlp32_forward_rows on padded rows (Mlp32Pad): the row in memory holds in_dim / seg_dst segments of seg_src floats.  Both modes; no distribution head.
 extern "C" int sigmaenv_mlp32_forward_rows_pad(sigmaenv_t* h, sigmaenv_mlp32* m, const float* in, int32_t rows_per_block, int64_t row_stride, int32_t n_blocks, int64_t block_stride,
                                                int32_t seg_src, int32_t seg_dst, float* out) {
-  if (!h || !m || !in || !out || rows_per_block < 0 || n_blocks < 0) return SIGMAENV_EINVAL;
-  if ((int64_t)rows_per_block * n_blocks > INT32_MAX) { h->err = "mlp32_forward_rows_pad: more than 2^31 - 1 rows"; return SIGMAENV_EINVAL; }
-  if (seg_src < 1 || seg_dst < seg_src || m->in_dim % seg_dst) { h->err = "mlp32_forward_rows_pad: 1 <= seg_src <= seg_dst, and seg_dst divides the network's input width"; return SIGMAENV_EINVAL; }
-  if (rows_per_block == 0 || n_blocks == 0) return SIGMAENV_OK;
-  if (row_stride < (int64_t)(m->in_dim / seg_dst) * seg_src || ((uintptr_t)in & 3) || (n_blocks > 1 && block_stride < 0)) {
-    h->err = "mlp32_forward_rows_pad: row_stride below the source row's width, a negative block_stride or an input that is not 4-byte aligned";
-    return SIGMAENV_EINVAL;
-  }
-  Mlp32Rows rw{};
-  rw.rpb = rows_per_block; rw.row_stride = row_stride; rw.block_stride = block_stride; rw.aligned = 0;
+  if (!h || !m || !in || !out || rows_per_block < 0 || n_blocks < 0) return SIGMAENV_EINVAL;  // (as sigmaenv_mlp32_forward_rows)
   const Mlp32Pad pd{seg_src, seg_dst};
-  const int rows = rows_per_block * n_blocks;
-  const dim3 grid((rows + MLP32_ROWS - 1) / MLP32_ROWS);
-  HIPCHK(h, hipSetDevice(h->device));
-  const int slot = timer_begin(h, SIGMAENV_KERNEL_MLP32);
-  if (m->mode == SIGMAENV_MLP32_SPLIT) {
-    if (m->smem_s > 64 * 1024) HIPCHK(h, hipFuncSetAttribute(reinterpret_cast<const void*>(sigmaenv_mlp32s_kernel<true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)m->smem_s));
-#ifdef SIGMAENV_PROFILE
-    hipLaunchKernelGGL((sigmaenv_mlp32s_kernel<true, true>), grid, dim3(256), m->smem_s, h->stream, m->ws, in, rows, m->in_dim, out, Mlp32sHead{}, rw, pd, (unsigned long long*)nullptr, 0);
-#else
-    hipLaunchKernelGGL((sigmaenv_mlp32s_kernel<true, true>), grid, dim3(256), m->smem_s, h->stream, m->ws, in, rows, m->in_dim, out, Mlp32sHead{}, rw, pd);
-#endif
-  } else {
-    if (m->smem > 64 * 1024) HIPCHK(h, hipFuncSetAttribute(reinterpret_cast<const void*>(sigmaenv_mlp32_kernel<true, false, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)m->smem));
-#ifdef SIGMAENV_PROFILE
-    hipLaunchKernelGGL((sigmaenv_mlp32_kernel<true, false, false, true>), grid, dim3(256), m->smem, h->stream, m->w, in, rows, m->in_dim, out, rw, (float*)nullptr, Mlp32Index{}, pd, (unsigned long long*)nullptr, 0);
-#else
-    hipLaunchKernelGGL((sigmaenv_mlp32_kernel<true, false, false, true>), grid, dim3(256), m->smem, h->stream, m->w, in, rows, m->in_dim, out, rw, (float*)nullptr, Mlp32Index{}, pd);
-#endif
-  }
-  HIPCHK(h, hipGetLastError());
-  timer_end(h, SIGMAENV_KERNEL_MLP32, slot);
-  return SIGMAENV_OK;
-}
-// head: the actor's distribution head, run as the epilogue of the split-mode kernel (*head_done = true) -- the exact mode leaves it to the caller's head launch
-// rw: the rows' addresses (sigmaenv_mlp32_forward_rows); nullptr: dense
-static int mlp32_forward_impl(sigmaenv_t* h, sigmaenv_mlp32* m, const float* in, int32_t rows, float* out, const Mlp32sHead* head, bool* head_done, const Mlp32Rows* rw) {
-  if (head_done) *head_done = false;
-  if (!h || !m || !in || !out || rows < 0) return SIGMAENV_EINVAL;
-  if (rows == 0) return SIGMAENV_OK;
-  HIPCHK(h, hipSetDevice(h->device));
-  if (m->mode == SIGMAENV_MLP32_SPLIT) {
-    // the dynamic-LDS limit is a per-kernel attribute -- PER DEVICE (ADVICE r5: a second GPU driven from the same process never got the opt-in beyond 64 KB): raised
-    // when a model needs more than what was set for this device before (not once per forward); atomics: handles may be driven from several threads
-    static std::atomic<size_t> s_split_lds_set[2][64];  // [dense | record rows]: two kernels
-    const int dslot = h->device >= 0 && h->device < 64 ? h->device : 0;
-    const void* kfn = rw ? reinterpret_cast<const void*>(sigmaenv_mlp32s_kernel<true>) : reinterpret_cast<const void*>(sigmaenv_mlp32s_kernel<false>);
-    std::atomic<size_t>& lds_set = s_split_lds_set[rw ? 1 : 0][dslot];
-    if (m->smem_s > 64 * 1024 && m->smem_s > lds_set.load(std::memory_order_acquire)) {
-      HIPCHK(h, hipFuncSetAttribute(kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)m->smem_s));
-      size_t cur = lds_set.load(std::memory_order_relaxed);
-      while (cur < m->smem_s && !lds_set.compare_exchange_weak(cur, m->smem_s, std::memory_order_release)) {}
-    }
-    Mlp32sHead hd_{};
-    if (head && m->out_dim == 4) { hd_ = *head; hd_.on = 1; if (head_done) *head_done = true; }
-    const int slot = timer_begin(h, SIGMAENV_KERNEL_MLP32);
-#ifdef SIGMAENV_PROFILE
-    {
-      const int groups = (rows + MLP32_ROWS - 1) / MLP32_ROWS;
-      if (getenv("SIGMAENV_TIMESTAMPS") && m->ts_groups < groups) {
-        if (m->ts) (void)hipFree(m->ts);
-        m->ts = nullptr;
-        if (hipMalloc((void**)&m->ts, (size_t)groups * 16 * 8) == hipSuccess) { m->ts_groups = groups; (void)hipMemsetAsync(m->ts, 0, (size_t)groups * 16 * 8, h->stream); }
-      }
-    }
-    size_t smem_l = m->smem_s;
-    if (getenv("SIGMAENV_MLP32_ONE_WG")) {  // diagnostic: one workgroup per CU (more LDS than two can share)
-      smem_l = 100 * 1024 > smem_l ? 100 * 1024 : smem_l;
-      HIPCHK(h, hipFuncSetAttribute(kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem_l));
-    }
-    const int stagger_l = getenv("SIGMAENV_MLP32_STAGGER") ? atoi(getenv("SIGMAENV_MLP32_STAGGER")) : 0;
-    if (rw) hipLaunchKernelGGL(sigmaenv_mlp32s_kernel<true>, dim3((rows + MLP32_ROWS - 1) / MLP32_ROWS), dim3(256), smem_l, h->stream, m->ws, in, (int)rows, m->in_dim, out, hd_, *rw, Mlp32Pad{}, m->ts, stagger_l);
-    else hipLaunchKernelGGL(sigmaenv_mlp32s_kernel<false>, dim3((rows + MLP32_ROWS - 1) / MLP32_ROWS), dim3(256), smem_l, h->stream, m->ws, in, (int)rows, m->in_dim, out, hd_, Mlp32Rows{}, Mlp32Pad{}, m->ts, stagger_l);
-#else
-    if (rw) hipLaunchKernelGGL(sigmaenv_mlp32s_kernel<true>, dim3((rows + MLP32_ROWS - 1) / MLP32_ROWS), dim3(256), m->smem_s, h->stream, m->ws, in, (int)rows, m->in_dim, out, hd_, *rw, Mlp32Pad{});
-    else hipLaunchKernelGGL(sigmaenv_mlp32s_kernel<false>, dim3((rows + MLP32_ROWS - 1) / MLP32_ROWS), dim3(256), m->smem_s, h->stream, m->ws, in, (int)rows, m->in_dim, out, hd_, Mlp32Rows{}, Mlp32Pad{});
-#endif
-    HIPCHK(h, hipGetLastError());
-    timer_end(h, SIGMAENV_KERNEL_MLP32, slot);
-    return SIGMAENV_OK;
-  }
-  // the dynamic-LDS limit is a per-kernel attribute: set for THIS model right before its launch (models of different input widths coexist)
-  const void* kfn = rw ? reinterpret_cast<const void*>(sigmaenv_mlp32_kernel<true>) : reinterpret_cast<const void*>(sigmaenv_mlp32_kernel<false>);
-  if (m->smem > 64 * 1024) HIPCHK(h, hipFuncSetAttribute(kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)m->smem));
-  const int slot = timer_begin(h, SIGMAENV_KERNEL_MLP32);
-#ifdef SIGMAENV_PROFILE
-  {
-    const int groups = (rows + MLP32_ROWS - 1) / MLP32_ROWS;
-    if (getenv("SIGMAENV_TIMESTAMPS") && m->ts_groups < groups) {
-      if (m->ts) (void)hipFree(m->ts);
-      m->ts = nullptr;
-      if (hipMalloc((void**)&m->ts, (size_t)groups * 16 * 8) == hipSuccess) { m->ts_groups = groups; (void)hipMemsetAsync(m->ts, 0, (size_t)groups * 16 * 8, h->stream); }
-    }
-  }
-  size_t smem_l = m->smem;
-  if (getenv("SIGMAENV_MLP32_ONE_WG")) {  // diagnostic: one workgroup per CU (more LDS than two can share)
-    smem_l = 100 * 1024;
-    HIPCHK(h, hipFuncSetAttribute(kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem_l));
-  }
-  const int stagger_l = getenv("SIGMAENV_MLP32_STAGGER") ? atoi(getenv("SIGMAENV_MLP32_STAGGER")) : 0;
-  if (rw) hipLaunchKernelGGL(sigmaenv_mlp32_kernel<true>, dim3((rows + MLP32_ROWS - 1) / MLP32_ROWS), dim3(256), smem_l, h->stream, m->w, in, (int)rows, m->in_dim, out, *rw, (float*)nullptr, Mlp32Index{}, Mlp32Pad{}, m->ts, stagger_l);
-  else hipLaunchKernelGGL(sigmaenv_mlp32_kernel<false>, dim3((rows + MLP32_ROWS - 1) / MLP32_ROWS), dim3(256), smem_l, h->stream, m->w, in, (int)rows, m->in_dim, out, Mlp32Rows{}, (float*)nullptr, Mlp32Index{}, Mlp32Pad{}, m->ts, stagger_l);
-#else
-  if (rw) hipLaunchKernelGGL(sigmaenv_mlp32_kernel<true>, dim3((rows + MLP32_ROWS - 1) / MLP32_ROWS), dim3(256), m->smem, h->stream, m->w, in, (int)rows, m->in_dim, out, *rw, (float*)nullptr, Mlp32Index{}, Mlp32Pad{});
-  else hipLaunchKernelGGL(sigmaenv_mlp32_kernel<false>, dim3((rows + MLP32_ROWS - 1) / MLP32_ROWS), dim3(256), m->smem, h->stream, m->w, in, (int)rows, m->in_dim, out, Mlp32Rows{}, (float*)nullptr, Mlp32Index{}, Mlp32Pad{});
-#endif
-  HIPCHK(h, hipGetLastError());
-  timer_end(h, SIGMAENV_KERNEL_MLP32, slot);
-  return SIGMAENV_OK;
+  Mlp32View v;
+  if (const int rc = mlp32_view(h, m, "mlp32_forward_rows_pad", in, rows_per_block, row_stride, n_blocks, block_stride, nullptr, 0, &pd, &v)) return rc;
+  return mlp32_launch(h, m, v, out, nullptr, nullptr, nullptr);
 }
 
 // The actor in the reference's precision: exact-fp32 MLP (obs_dim -> 256 -> 256 -> 256 -> 4) + the distribution head.  Same outputs as

@@ -391,6 +391,59 @@ def test_bad_arguments_are_refused_before_any_launch(env):
     nf = C.c_uint64(5)
     assert lib.mlp32_backward_workspace(h, -1, C.byref(nf)) == EINVAL and lib.mlp32_backward_workspace(None, 4, C.byref(nf)) == EINVAL
     assert lib.mlp32_backward_workspace(h, 0, C.byref(nf)) == 0 and nf.value == 0
+    # The refusal table: what each of the eight row-taking entry points returns for argument sets that are refused before any launch or have no row (then the
+    # backward writes zero gradients, nothing else runs).  The codes are literals recorded from the library as it was when every entry point carried its own checks
+    # (-22 = SIGMAENV_EINVAL, 0 = SIGMAENV_OK).  The network has 7 inputs; x is 2 blocks of 32 rows; padded: one segment of 5 floats read as 7 columns.
+    idx = torch.tensor([1, 0], dtype=torch.int32, device="cuda")
+    at = lambda t, off: C.c_void_p(t.data_ptr() + off)  # noqa: E731
+    base = dict(src=p(x), rpb=32, rs=8, nb=2, bs=256, index=p(idx), n_index=2, pad=(5, 7), out=p(y), acts=p(acts), dout=p(y), ws=p(ws))
+    FWD, SAVE, BACK = ["forward_rows", "forward_rows_pad"], ["forward_save", "forward_save_indexed", "forward_save_indexed_pad"], ["backward", "backward_indexed", "backward_indexed_pad"]
+    EVERY = FWD + SAVE + BACK
+    INDEXED, PADDED = [n for n in EVERY if "indexed" in n], [n for n in EVERY if n.endswith("_pad")]
+    PLAIN = [n for n in EVERY if n not in PADDED]
+
+    def call(name, **over):
+        a = dict(base, **over)
+        rows, ix, back = (a["src"], a["rpb"], a["rs"], a["nb"], a["bs"]), (a["index"], a["n_index"]), (a["acts"], a["dout"], a["ws"], W, B)
+        args = {"forward_rows": rows + (a["out"],), "forward_rows_pad": rows + a["pad"] + (a["out"],), "forward_save": rows + (a["out"], a["acts"]),
+                "forward_save_indexed": rows + ix + (a["out"], a["acts"]), "forward_save_indexed_pad": rows + ix + a["pad"] + (a["out"], a["acts"]),
+                "backward": rows + back, "backward_indexed": rows + ix + back, "backward_indexed_pad": rows + ix + a["pad"] + back}[name]
+        return getattr(lib, "mlp32_" + name)(env.h, h, *args)
+
+    table = [  # (the argument set, what differs from `base`, the entry points it applies to, the recorded code)
+        ("null in", dict(src=None), EVERY, -22),
+        ("null out", dict(out=None), FWD + SAVE, -22),
+        ("null acts", dict(acts=None), SAVE + BACK, -22),
+        ("acts 4-byte aligned", dict(acts=at(acts, 4)), SAVE + BACK, -22),
+        ("workspace 4-byte aligned", dict(ws=at(ws, 4)), BACK, -22),
+        ("row_stride one below the width", dict(rs=6), PLAIN, -22),
+        ("row_stride one below the padded row's width", dict(rs=4), PADDED, -22),
+        ("negative rows_per_block", dict(rpb=-1), EVERY, -22),
+        ("negative n_blocks", dict(nb=-1), EVERY, -22),
+        ("negative n_index", dict(n_index=-1), INDEXED, -22),
+        ("2^31 rows", dict(rpb=65536, nb=32768, n_index=32768), EVERY, -22),
+        ("negative block_stride, two blocks", dict(bs=-8), EVERY, -22),
+        ("null index, n_index 2", dict(index=None), INDEXED, -22),
+        ("seg_src above seg_dst", dict(pad=(8, 7)), PADDED, -22),
+        ("seg_dst does not divide the input width", dict(pad=(3, 4)), PADDED, -22),
+        ("no rows: rows_per_block 0", dict(rpb=0), EVERY, 0),
+        ("no rows: n_blocks 0", dict(nb=0), [n for n in EVERY if n not in INDEXED], 0),
+        ("no rows: n_index 0", dict(n_index=0), INDEXED, 0),
+        ("no rows: null index, n_index 0", dict(index=None, n_index=0), INDEXED, 0),
+        ("no rows and a null in", dict(rpb=0, src=None), FWD, -22),
+        ("no rows and a null in", dict(rpb=0, src=None), SAVE + BACK, 0),
+        ("no rows: null index, n_index 0, null in", dict(index=None, n_index=0, src=None), INDEXED, 0),
+    ]
+    wrong = []
+    for label, over, names, code in table:
+        for name in names:
+            rc = call(name, **over)
+            print(f"{label:45s} {name:26s} {rc}")
+            if rc != code:
+                wrong.append((label, name, rc, code))
+            if "row_stride" in label and not lib.last_error(env.h).startswith(b"mlp32_" + name.encode() + b":"):
+                wrong.append((label, name, lib.last_error(env.h), "the entry point's name in front of the message"))
+    assert not wrong, wrong
     env.sync()
     assert all((t == 0).all() for t in gw + gb + [y])  # nothing ran
 

@@ -1,6 +1,6 @@
 """The network kernels against fp64 (tests/network_check.py) at the shapes the C-ABI accepts: sigmaenv_mlp32_* in both arithmetic modes over depth 2-4, input
 widths 1-4096 (every staging path of layer 0, the K = 256 path, chunked inputs beyond 256), 1-32 outputs and ragged row counts; the split form's range edges;
-output bounds; repeatability with models of different LDS needs interleaved on one handle; the MAPPO critic on wide observations; the bf16 actor at every
+output bounds; repeatability with models of different LDS needs interleaved on one handle, through every forward entry point; the MAPPO critic on wide observations; the bf16 actor at every
 width it takes.  Every case has a fixed seed."""
 import numpy as np
 import pytest
@@ -181,6 +181,61 @@ def test_repeatable_and_lds_settings_per_model(env):
         assert np.array_equal(run(env, nets[k], xs[k]), alone[k]), f"{specs[k][0]} interleaved differs from alone"
     for n in nets:
         n.close()
+
+
+LDS_WIDTHS = [8, SPLIT_MAX_IN, 8]  # a narrow network, the widest the split kernel's LDS takes, the narrow one again
+LDS_CASES = [(entry, mode) for entry in ("forward", "forward_rows", "forward_rows_pad") for mode in ("split", "exact")] + [
+    (entry, "exact") for entry in ("forward_save", "forward_save_indexed", "forward_save_indexed_pad")]  # (the saving forward is the exact chain in either mode)
+_lds_nets = {}
+
+
+def lds_net(in_dim, mode):
+    """(torch module, Mlp32) per (input width, mode), made once"""
+    from sigmarl_amd.actor import Mlp32
+    if (in_dim, mode) not in _lds_nets:
+        mlp = make_net(3, in_dim, 3, 1.0, 80 + in_dim)
+        _lds_nets[(in_dim, mode)] = (mlp, Mlp32(mlp, mode=mode))
+    return _lds_nets[(in_dim, mode)]
+
+
+@pytest.mark.parametrize("entry,mode", LDS_CASES, ids=lambda v: v)
+def test_every_forward_entry_point_gets_the_lds_its_network_needs(env, entry, mode):
+    """Each forward entry point, on one env handle, with networks of 8, 592 and 8 inputs in turn: the dynamic-LDS limit is kept per kernel instantiation and raised
+    when a network needs more than an earlier one left set -- a limit looked up under another kernel's key makes the wide launch fail with an error code.  65 rows
+    as 5 blocks of 13 (two tiles, the second ragged) at a row stride one float above the row's width and a base 3 floats into the tensor (4-byte aligned rows), NaN
+    around them; padded: segments of 3 floats read as 4 columns; indexed: 5 of a record's 7 blocks, one twice.  Every call succeeds and gives the bits of
+    sigmaenv_mlp32_forward on the dense (padded) copy of the rows in the same arithmetic; sigmaenv_mlp32_forward itself is held to fp64.  (The limit is also kept per
+    device: one GPU cannot show that.)"""
+    import torch
+    SRC, DST, RPB, NB, FRAMES, OFF = 3, 4, 13, 5, 7, 3
+    padded, indexed = entry.endswith("_pad"), "indexed" in entry
+    pick = np.array([6, 0, 3, 3, 1])
+    index = torch.from_numpy(pick.astype(np.int32)).cuda()
+    for in_dim in LDS_WIDTHS:
+        mlp, net = lds_net(in_dim, mode)
+        assert net.set_mode(mode) == mode
+        width, nrec = in_dim // DST * SRC if padded else in_dim, FRAMES if indexed else NB  # the row in memory; the record's blocks
+        rs = width + 1
+        x = make_input(nrec * RPB, width, 7 * in_dim)
+        rec = np.full(OFF + nrec * RPB * rs, np.nan, np.float32)
+        rec[OFF:].reshape(nrec * RPB, rs)[:, :width] = x
+        dense = x.reshape(nrec, RPB, width)[pick] if indexed else x
+        dense = dense.reshape(NB * RPB, width)
+        if padded:
+            dense = np.concatenate([dense.reshape(NB * RPB, -1, SRC), np.zeros((NB * RPB, in_dim // DST, DST - SRC), np.float32)], axis=2)
+        dense = np.ascontiguousarray(dense.reshape(NB * RPB, in_dim))
+        spec = (torch.from_numpy(rec).cuda(), OFF, RPB, rs, nrec, RPB * rs)
+        want = net.forward(env, torch.from_numpy(dense).cuda())
+        if entry == "forward":
+            env.sync()
+            nc.check(want.cpu().numpy(), mlp, dense, f"{entry} {mode} in={in_dim}")
+            continue
+        if entry.startswith("forward_rows"):
+            got = net.forward_rows(env, *spec, pad=(SRC, DST) if padded else None)
+        else:
+            got = net._forward_save(env, spec + (index if indexed else None,) + (((SRC, DST),) if padded else ()))[0]
+        env.sync()
+        assert torch.equal(got.reshape(want.shape).view(torch.int32), want.view(torch.int32)), f"{entry} {mode} in={in_dim}"
 
 
 @pytest.mark.parametrize("mode", ["split", "exact"])
