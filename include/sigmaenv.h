@@ -1059,6 +1059,64 @@ int sigmaenv_cbf_qp(sigmaenv_t* h, const float* actions, float* actions_safe, do
 int sigmaenv_cbf_regroup(sigmaenv_t* h);
 int sigmaenv_cbf_get_groups(sigmaenv_t* h, int32_t* groups_host);
 
+/* ---- the challenging initial-state buffer (sigmaenv_isb.inc; the index arithmetic and the decisions: sigmarl_amd/csrc/sigmaenv_isb.h) ---------------------
+ * Parameters.is_challenging_initial_state_buffer: a per-step history of the states (sigmarl/scenarios/road_traffic.py:702-708, :1226-1240), on an agent-agent
+ * collision the state n_steps_stored steps back goes into a circular bank (:1415-1427; CircularBuffer / InitialStateBuffer, sigmarl/helper_scenario.py:424-508), and
+ * a finished env restarts from a random bank entry with probability probability_use_recording (:857-873, world_state_rt_sim.py:57-71, :162-178).  In the reference
+ * the first use of a recording raises (`if initial_state:` on an [N, 8] tensor, world_state_rt_sim.py:162), so no golden exists: sigmaenv_isb.h is the specification
+ * -- rings, ranks, bank slots, the three draws DRAW_ISB_RECORD / _USE / _INDEX keyed (seed, counter, env_index_base + b, agent 0) -- and lists the four departures
+ * (the whole state row is kept and restored; one ring per env; one record draw per env; the restart is sigmaenv_reset(full_env = 1)).
+ * An entry of one env: its N rows of SIGMAENV_BUF_STATE and its N rows of SIGMAENV_BUF_PATH.  Everything is enqueued on the handle's stream; record, restart and
+ * settle never wait on the host, and no state, index or probability visits it.
+ *
+ * sigmaenv_isb_create   <- InitialStateBuffer / StateBuffer construction, road_traffic.py:702-708 (capacity 100, probability_record 1.0, probability_use_recording 0.2
+ *                          there; n_steps_stored from Parameters).  A bank of THIS handle (its B and N): capacity 1 .. 65536 entries, a ring of n_steps_stored
+ *                          (1 .. 1024) entries per env.  Allocates (do not call inside a stream capture) and ends with a sigmaenv_isb_reset.
+ * sigmaenv_isb_destroy  the bank; a bank outlives its handle only for this call.
+ * sigmaenv_isb_reset    <- CircularBuffer.reset (helper_scenario.py:465-469) + the first state_buffer.add: empties the bank (ptr = count = 0) and every ring, then
+ *                          pushes every env's current rows and takes the envs' episodes_reset as the bank's copy.
+ * sigmaenv_isb_record   <- state_buffer.add (road_traffic.py:1226-1240) and the recording of done() (:1415-1427).  Runs on the frame a step left, before any reset:
+ *                          push, collided[b] = any byte of SIGMAENV_BUF_COL_AGENTS[b], the record draw, the ordered write of nth_latest(n_steps_stored) of the R
+ *                          recording envs into the bank (the last `capacity` of them survive), ptr / count, pending[b] = env not done and a reset request
+ *                          (SIGMAENV_BUF_COL_FLAGS[b, ., 3]) set.  Two launches: one lane per env, then ONE workgroup that ranks the recorders.
+ * sigmaenv_isb_restart  <- reset_world_at's use of a recording (:857-873, world_state_rt_sim.py:57-71, :162-178).  Runs before sigmaenv_auto_reset: an env with
+ *                          done[b] restarts from entry j of the bank iff count >= 1 and u < p_use (count includes this step's recordings); the restart is
+ *                          sigmaenv_reset(full_env = 1) with the entry's N (path, state) rows, the entries staying on the device (step counter 0, episodes_reset + 1,
+ *                          done cleared, derived state, mutual distances, collision flags, prev_pos), followed by a fresh observation of the env.  Envs not chosen
+ *                          stay done for sigmaenv_auto_reset, whose draws are keyed per env and so do not move.  A loaded entry whose path index lies outside the
+ *                          path table is never used: its env stays done.
+ * sigmaenv_isb_settle   <- state_buffer.reset + add at the end of every reset_world_at (:909-923, single-agent resets included).  Runs after sigmaenv_auto_reset:
+ *                          every env whose episodes_reset differs from the bank's copy, and every env with pending[b], has its ring cleared and its current rows
+ *                          pushed; the copy is refreshed.
+ * sigmaenv_isb_attach(h, bank) / (h, NULL): while a bank is attached, every step of sigmaenv_rollout, sigmaenv_rollout_f32 and sigmaenv_rollout_f32_ex (every wrapper,
+ *                          and the CBF chain) runs as sigmaenv_step -> (sigmaenv_eval_accumulate, if an evaluator is attached as well) -> sigmaenv_isb_record ->
+ *                          sigmaenv_isb_restart -> sigmaenv_auto_reset -> sigmaenv_isb_settle with the action, the record row block, the (seed, counter0 + t) keys
+ *                          and the path range of the fused launch it replaces (a rollout with path_count 0 -- no device-side resets -- only records).  With
+ *                          p_use = 0 the rollout is the unattached one, bit for bit.  With nothing attached the rollouts are unchanged.  Direct calls of
+ *                          sigmaenv_step_autoreset, sigmaenv_step_autoreset_many and sigmaenv_step_autoreset_n never consult a bank.
+ * sigmaenv_isb_get      DEVICE pointers into the bank, for tests and checkpoints (no wait, no copy): see SIGMAENV_ISB_*.
+ * sigmaenv_isb_set      loads the first `count` (0 .. capacity) entries from DEVICE tensors state_rows f32 [count, N, 8] and path_rows i32 [count, N, 4] -- a saved
+ *                          bank, or a hand-made scenario set -- and sets count and ptr = count mod capacity.  The rings are left as they are. */
+typedef struct sigmaenv_isb sigmaenv_isb_t;
+#define SIGMAENV_ISB_BANK_STATE 0 /* f32 [capacity, N, 8] */
+#define SIGMAENV_ISB_BANK_PATH 1  /* i32 [capacity, N, 4] */
+#define SIGMAENV_ISB_WORDS 2      /* i32 [2]: ptr, count */
+#define SIGMAENV_ISB_RING_STATE 3 /* f32 [B, n_steps_stored, N, 8] */
+#define SIGMAENV_ISB_RING_PATH 4  /* i32 [B, n_steps_stored, N, 4] */
+#define SIGMAENV_ISB_HELD 5       /* i32 [B] */
+#define SIGMAENV_ISB_HEAD 6       /* i32 [B] */
+#define SIGMAENV_ISB_PENDING 7    /* u8  [B] */
+#define SIGMAENV_ISB_CHUNK 1024   /* envs per chunk of sigmaenv_isb_record's ranking workgroup (ISB_CHUNK of sigmaenv_isb.h) */
+int sigmaenv_isb_create(sigmaenv_t* h, int32_t capacity, int32_t n_steps_stored, float p_record, float p_use, sigmaenv_isb_t** out);
+void sigmaenv_isb_destroy(sigmaenv_isb_t* bank);
+int sigmaenv_isb_reset(sigmaenv_t* h, sigmaenv_isb_t* bank);
+int sigmaenv_isb_record(sigmaenv_t* h, sigmaenv_isb_t* bank, uint64_t seed, uint64_t counter);
+int sigmaenv_isb_restart(sigmaenv_t* h, sigmaenv_isb_t* bank, uint64_t seed, uint64_t counter);
+int sigmaenv_isb_settle(sigmaenv_t* h, sigmaenv_isb_t* bank);
+int sigmaenv_isb_attach(sigmaenv_t* h, sigmaenv_isb_t* bank);
+int sigmaenv_isb_get(sigmaenv_t* h, sigmaenv_isb_t* bank, int32_t what, void** dev_ptr, size_t* bytes);
+int sigmaenv_isb_set(sigmaenv_t* h, sigmaenv_isb_t* bank, const float* state_rows, const int32_t* path_rows, int32_t count);
+
 #ifdef __cplusplus
 }
 #endif

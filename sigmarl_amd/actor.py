@@ -32,7 +32,7 @@ import torch
 
 from . import capi
 from .env import SigmaEnv
-from .params import check_rollout_wrapper
+from .params import check_initial_state_bank, check_rollout_wrapper
 
 
 def make_mlp(obs_dim: int = 32, hidden: int = 256, n_out: int = 4) -> torch.nn.Sequential:
@@ -759,8 +759,12 @@ class Actor:
 
         ``obs_rec [T,B,N,D]`` (any precision, any wrapper): the root observations -- row t = ``env.obs`` as the final actor forward of step t read it, i.e. the
         ``observation`` of the collector's tensordict (the record row of step t - 1 holds it only where nothing was re-placed).  ``None``: the handle's setting is
-        left as it is (off unless ``env.set_rollout_obs_record`` set it, as an env shard that records into the whole batch's buffer does)."""
+        left as it is (off unless ``env.set_rollout_obs_record`` set it, as an env shard that records into the whole batch's buffer does).
+
+        Inside ``initial_states.InitialStateBank(env).attached()`` every step runs as step -> record -> restart -> auto_reset -> settle (``sigmaenv_isb_attach``).
+        An env whose parameters set ``is_challenging_initial_state_buffer`` is refused (``NotImplementedError``) without one."""
         check_rollout_wrapper(getattr(env, "parameters", None), wrapper, communication_noise)
+        check_initial_state_bank(getattr(env, "parameters", None), getattr(env, "_initial_states", None) is not None)
         if obs_rec is not None:
             check_record(obs_rec, (int(n_steps), env.B, env.N, env.D), "obs_rec")
             env.set_rollout_obs_record(obs_rec)

@@ -220,6 +220,11 @@ def prb_level_sizes(capacity: int) -> list:
     return n
 
 
+ISB_BANK_STATE, ISB_BANK_PATH, ISB_WORDS, ISB_RING_STATE, ISB_RING_PATH, ISB_HELD, ISB_HEAD, ISB_PENDING = range(8)  # SIGMAENV_ISB_*: what sigmaenv_isb_get points at
+ISB_CHUNK, ISB_MAX_CAPACITY, ISB_MAX_STEPS_STORED = 1024, 65536, 1024  # sigmaenv_isb.h
+ISB_DRAW_RECORD, ISB_DRAW_USE, ISB_DRAW_INDEX = 5100, 5101, 5102  # DRAW_ISB_* of the draw table (sigmaenv_dist.h)
+
+
 PPO_SUMS = 5  # SIGMAENV_PPO_SUMS: partial sums per workgroup of 256 rows in sigmaenv_ppo_head's workspace
 PRIORITY_ENTROPY_DRAW = 7350  # DRAW_PRIORITY_ENTROPY of the draw table (sigmaenv_dist.h): sigmaenv_ppo_head_1d's entropy sample
 PPO_RESULT = ("loss_objective", "loss_entropy", "loss_critic", "entropy", "clip_fraction", "kl_approx")  # result[0 .. 5]
@@ -386,6 +391,15 @@ _PRODUCT_ONLY = {
     "eval_get": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
     "eval_accumulate_study": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(EvalSrc), C.POINTER(EvalStudySrc)]),
     "eval_study_finish": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "isb_create": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_float, C.c_float, C.POINTER(C.c_void_p)]),
+    "isb_destroy": (None, [C.c_void_p]),
+    "isb_reset": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "isb_record": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64]),
+    "isb_restart": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64]),
+    "isb_settle": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "isb_attach": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "isb_get": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]),
+    "isb_set": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]),
 }
 
 

@@ -1263,6 +1263,7 @@ __global__ void sigmaenv_reset_scatter_kernel(DevBufs g, int N, int n, const int
   int k = blockIdx.x * blockDim.x + threadIdx.x;
   if (k >= n) return;
   int b = env_idx[k], i = agent_idx[k];
+  if (b < 0) return;  // an entry that is not used (sigmaenv_isb_restart fills one per agent of the batch on the device; sigmaenv_reset refuses a negative index on the host)
   size_t bi = (size_t)b * N + i;
   for (int q = 0; q < 8; ++q) g.state[bi * 8 + q] = state8[(size_t)k * 8 + q];
   for (int q = 0; q < 4; ++q) g.path[bi * 4 + q] = path_ids[(size_t)k * 4 + q];
@@ -1790,6 +1791,7 @@ __global__ void __launch_bounds__(512) sigmaenv_auto_reset_kernel(sigmaenv_confi
 // host side: the C-ABI
 // =====================================================================================================================
 struct sigmaenv_eval;  // sigmaenv_eval.inc
+struct sigmaenv_isb;   // sigmaenv_isb.inc
 struct sigmaenv {
   sigmaenv_config_t cfg;
   int device = 0;
@@ -1846,6 +1848,8 @@ struct sigmaenv {
   size_t wrap_ws_bytes = 0;
   sigmaenv_eval* eval_attached = nullptr;  // sigmaenv_eval_attach: the rollouts step as step -> accumulate -> auto_reset while set (sigmaenv_eval.inc)
   std::vector<sigmaenv_eval*> evals;       // the evaluators created on this handle (they outlive it only as orphans: sigmaenv_destroy)
+  sigmaenv_isb* isb_attached = nullptr;    // sigmaenv_isb_attach: the rollouts step as step -> record -> restart -> auto_reset -> settle while set (sigmaenv_isb.inc)
+  std::vector<sigmaenv_isb*> isbs;         // the initial-state banks created on this handle (orphans after sigmaenv_destroy, like the evaluators)
   std::string err;
 };
 
@@ -1918,12 +1922,14 @@ extern "C" int sigmaenv_obs_dim_full(int32_t n_agents, int32_t n_nearing, int32_
 extern "C" const char* sigmaenv_last_error(const sigmaenv_t* h) { return h ? h->err.c_str() : "null handle"; }
 
 static void eval_orphan(sigmaenv* h);  // sigmaenv_eval.inc: the handle's evaluators lose their owner
+static void isb_orphan(sigmaenv* h);   // sigmaenv_isb.inc: and its initial-state banks
 
 extern "C" void sigmaenv_destroy(sigmaenv_t* h) {
   if (!h) return;
   (void)hipSetDevice(h->device);
   (void)hipStreamSynchronize(h->stream);
   eval_orphan(h);
+  isb_orphan(h);
   for (void* p : h->allocs) (void)hipFree(p);
   for (auto& tm : h->timers)
     for (auto& ev : tm.pool) { (void)hipEventDestroy(ev.first); (void)hipEventDestroy(ev.second); }
@@ -2529,9 +2535,13 @@ extern "C" int sigmaenv_cbf_qp(sigmaenv_t* h, const float* actions, float* actio
 //
 // for_rollout (sigmaenv_rollout*: rollout_loop) with an evaluator attached (sigmaenv_eval_attach): the fused launch is taken apart into sigmaenv_step ->
 // sigmaenv_eval_accumulate -> sigmaenv_auto_reset -- the same action, record target and (seed, counter) -- so that the evaluator sees the step's outcome before the
-// re-placements clear it; the header promises the same end state and record as the fused launch, bit for bit.  Without an attachment, and for every other caller,
-// nothing changes.
+// re-placements clear it; the header promises the same end state and record as the fused launch, bit for bit.  With an initial-state bank attached
+// (sigmaenv_isb_attach) the same split carries the bank's three calls: step -> (accumulate) -> sigmaenv_isb_record -> sigmaenv_isb_restart -> sigmaenv_auto_reset ->
+// sigmaenv_isb_settle; a rollout without device-side resets (path_count 0) only records.  Without an attachment, and for every other caller, nothing changes.
 static int eval_accumulate_impl(sigmaenv* h, sigmaenv_eval* ev, const sigmaenv_eval_src_t* src, const sigmaenv_eval_study_src_t* ssrc);  // sigmaenv_eval.inc
+extern "C" int sigmaenv_isb_record(sigmaenv_t* h, sigmaenv_isb* k, uint64_t seed, uint64_t counter);  // sigmaenv_isb.inc
+extern "C" int sigmaenv_isb_restart(sigmaenv_t* h, sigmaenv_isb* k, uint64_t seed, uint64_t counter);
+extern "C" int sigmaenv_isb_settle(sigmaenv_t* h, sigmaenv_isb* k);
 static bool eval_nominal_from_cbf(const sigmaenv* h);  // sigmaenv_eval.inc: does the chain run the CBF-QP (and SIGMAENV_BUF_CBF_NOMINAL hold the nominal action)?
 static int launch_cbf_then_step(sigmaenv* h, StepLaunch l, bool for_rollout = false) {
   if (!h || !l.actions) return SIGMAENV_EINVAL;
@@ -2543,12 +2553,19 @@ static int launch_cbf_then_step(sigmaenv* h, StepLaunch l, bool for_rollout = fa
     if (rc) return rc;
     if (h->cbf_cfg.is_apply_cbf_action || h->cbf_cfg.is_grouping) l.actions = (const float*)h->cbf_safe;
   }
-  if (for_rollout && h->eval_attached) {
+  if (for_rollout && (h->eval_attached || h->isb_attached)) {
     int rc = launch_step(h, {l.actions, l.slab, 0, 0, 0, 0});  // sigmaenv_step
     if (rc) return rc;
-    rc = eval_accumulate_impl(h, h->eval_attached, nullptr, nullptr);  // (a study evaluator takes a study frame: sigmaenv_eval_accumulate_study with no override)
+    if (h->eval_attached) {
+      rc = eval_accumulate_impl(h, h->eval_attached, nullptr, nullptr);  // (a study evaluator takes a study frame: sigmaenv_eval_accumulate_study with no override)
+      if (rc) return rc;
+    }
+    if (h->isb_attached && (rc = sigmaenv_isb_record(h, h->isb_attached, l.seed, l.counter)) != 0) return rc;
+    if (l.path_count == 0) return SIGMAENV_OK;
+    if (h->isb_attached && (rc = sigmaenv_isb_restart(h, h->isb_attached, l.seed, l.counter)) != 0) return rc;
+    rc = sigmaenv_auto_reset(h, l.seed, l.counter, l.path_first, l.path_count);
     if (rc) return rc;
-    return l.path_count != 0 ? sigmaenv_auto_reset(h, l.seed, l.counter, l.path_first, l.path_count) : SIGMAENV_OK;
+    return h->isb_attached ? sigmaenv_isb_settle(h, h->isb_attached) : SIGMAENV_OK;
   }
   return launch_step(h, l);
 }
@@ -2730,4 +2747,6 @@ extern "C" int sigmaenv_trig_selftest(sigmaenv_t* h, int32_t kind, int32_t n, co
 #include "sigmaenv_ppo.inc"
 #include "sigmaenv_prb.h"
 #include "sigmaenv_prb.inc"
+#include "sigmaenv_isb.h"
+#include "sigmaenv_isb.inc"
 #include "sigmaenv_cbf.inc"

@@ -1,7 +1,7 @@
 // sigmaenv_dist.h -- everything that samples on the device, stated ONCE: the counter-based generator, the table of its draw ids, the conversions of a word into a
 // uniform / a bounded integer / a normal pair, and the TanhNormal head of the policies (torchrl's NormalParamExtractor "biased_softplus_1.0" + TanhNormal as
 // sigmarl/modules/decision_making_module.py:50-82 and priority_module.py:34-66 build them; torchrl is third-party and absent: restated from its published
-// behaviour).  The kernels of sigmaenv.hip, sigmaenv_actor.inc, sigmaenv_wrappers.inc, sigmaenv_ppo.inc and sigmaenv_prb.inc run these functions on the device; a host
+// behaviour).  The kernels of sigmaenv.hip, sigmaenv_actor.inc, sigmaenv_wrappers.inc, sigmaenv_ppo.inc, sigmaenv_prb.inc and sigmaenv_isb.inc run these functions on the device; a host
 // program runs them on the host (tests/test_dist_check.py holds the generator, the uniforms and the bounded draw bit for bit to tests/policy_head_check.py, the
 // normals and the head to its float64 reference within its criterion, and the table to every Python mirror; tests/test_comm_noise_check.py holds the communication noise
 // at the end of this file to tests/comm_noise_check.py).
@@ -40,6 +40,9 @@ SIGMA_HD uint32_t rng_u32(uint64_t seed, uint64_t counter, uint32_t env, uint32_
 #define DRAW_AGENT_TRY 2000u     /* + 2 t, + 2 t + 1: try t of a single-agent reset                              reset_candidate     (env, agent) */
 #define DRAW_AGENT_SPEED 3000u   /* the start speed after a single-agent reset                                   auto_reset_tile     (env, agent) */
 #define DRAW_SCENARIO 5000u      /* cpm_mixed: the sub-scenario a finished env draws                             draw_scenario       (env, 0) */
+#define DRAW_ISB_RECORD 5100u    /* initial-state bank: does a collided env record?                               isb record          (env, 0)   sigmaenv_isb.h */
+#define DRAW_ISB_USE 5101u       /* does a finished env restart from the bank?                                   isb restart         (env, 0) */
+#define DRAW_ISB_INDEX 5102u     /* which bank entry                                                             isb restart         (env, 0) */
 #define DRAW_ACTOR 7000u         /* u1, + 1: u2 of the actor's normal pair                                       actor_distribution  (env, agent) */
 #define DRAW_PRIORITY 7100u      /* u1, + 1: u2 of the priority score's normal (cosine branch)                   priority_head       (env, agent) */
 #define DRAW_SHUFFLE 7200u       /* the random priority order: position i draws j in [0, i]                      priority_random     (env, agent = i) */
@@ -54,6 +57,8 @@ static_assert(DRAW_AGENT_TRY + 2u * AUTO_RESET_MAX_TRIES <= DRAW_AGENT_SPEED && 
 static_assert(DRAW_SCENARIO < DRAW_ACTOR && DRAW_ACTOR + 1u < DRAW_PRIORITY && DRAW_PRIORITY + 1u < DRAW_SHUFFLE && DRAW_SHUFFLE < DRAW_ENTROPY &&
               DRAW_ENTROPY + 1u < DRAW_PRIORITY_ENTROPY && DRAW_PRIORITY_ENTROPY + 1u < DRAW_REPLAY && DRAW_REPLAY < DRAW_COMM_NOISE && DRAW_COMM_NOISE + 2u * COMM_NOISE_MAX_COLUMNS <= DRAW_OBS_NOISE,
               "the streams overlap, or the open-ended noise range is not the highest");
+static_assert(DRAW_SCENARIO < DRAW_ISB_RECORD && DRAW_ISB_RECORD < DRAW_ISB_USE && DRAW_ISB_USE < DRAW_ISB_INDEX && DRAW_ISB_INDEX < DRAW_ACTOR,
+              "the initial-state bank's draws leave their gap between the scenario draw and the actor's");
 
 // ---- a word -> a number ------------------------------------------------------------------------------------------------------------------------------------------------
 // U[0, 1): (k >> 8) * 2^-24, exact in fp32; never 1

@@ -40,6 +40,7 @@ import torch
 
 from . import capi
 from .actor import Actor, Critic, Mlp32, PriorityNet, check_record, load_source, source_pairs
+from .params import check_initial_state_bank
 
 TD_GAMMA = 0.9  # compute_td_error's discount as the trainer calls it (mappo_cavs.py:383, :454) -- not Parameters.gamma
 
@@ -90,7 +91,7 @@ BASE_OBS, PRIORITY = ("info", "base_observation"), ("info", "priority")  # the r
 
 
 def collect(env, actor, critic, T: int, params=None, gamma: float | None = None, lmbda: float | None = None, td_gamma: float = TD_GAMMA, td_error: bool = True,
-            seed: int = 0, counter0: int = 0, returns: "EpisodeReturns | None" = None, priority_critic=None, **rollout_kw) -> dict:
+            seed: int = 0, counter0: int = 0, returns: "EpisodeReturns | None" = None, priority_critic=None, initial_states=None, **rollout_kw) -> dict:
     """One learner-ready batch: ``T`` steps of the device rollout (``Actor.rollout``, ``rollout_kw`` = its wrapper / path / precision arguments), the critic on
     both sides of every step, GAE and the TD-error priorities -- enqueued on the env's stream, nothing copied in between.  ``gamma`` / ``lmbda`` come from
     ``params`` (a ``Parameters``; default: the env's) unless given.  Returns device tensors under the reference tensordict's keys:
@@ -109,7 +110,18 @@ def collect(env, actor, critic, T: int, params=None, gamma: float | None = None,
     reference RUNS: its priority loss module never re-keys ``advantage`` / ``value_target`` (``sigmarl/modules/priority_module.py:102-113``: the two ``set_keys``
     entries are commented out), so ``priority_module.GAE``, run after the base GAE (``sigmarl/mappo_cavs.py:370-378``), overwrites both keys and BOTH losses train on
     the priority critic's pair.  So with a ``priority_critic`` ``batch["advantage"]`` / ``batch["value_target"]`` are the PRIORITY critic's pair and the base critic's
-    stay available as ``batch["base_advantage"]`` / ``batch["base_value_target"]``; ``td_error`` stays the base critic's (``compute_td_error`` reads its values)."""
+    stay available as ``batch["base_advantage"]`` / ``batch["base_value_target"]``; ``td_error`` stays the base critic's (``compute_td_error`` reads its values).
+
+    ``initial_states`` (an ``initial_states.InitialStateBank`` of this env): the rollout runs inside ``initial_states.attached()``; parameters that set
+    ``is_challenging_initial_state_buffer`` are refused (``NotImplementedError``) without one."""
+    if initial_states is not None:
+        from .initial_states import InitialStateBank
+
+        if not (isinstance(initial_states, InitialStateBank) and initial_states.env is env):
+            raise TypeError("collect(): initial_states must be an initial_states.InitialStateBank of this env")
+        with initial_states.attached():
+            return collect(env, actor, critic, T, params, gamma, lmbda, td_gamma, td_error, seed, counter0, returns, priority_critic, **rollout_kw)
+    check_initial_state_bank(params if params is not None else getattr(env, "parameters", None), getattr(env, "_initial_states", None) is not None)
     if returns is not None and not (isinstance(returns, EpisodeReturns) and returns.env is env):
         raise TypeError("collect(): returns must be a learn.EpisodeReturns of this env")
     p = params if params is not None else getattr(env, "parameters", None)
@@ -872,7 +884,7 @@ def steps_per_iteration(params, frames: int, num_epochs: int | None = None, mini
 
 def train_iteration(env, actor, critic, actor_module, critic_module, optim, returns: EpisodeReturns, params=None, *, i_iter: int = 1, buffer: PrioritizedBuffer | None = None,
                     frames_per_batch: int | None = None, seed: int = 0, counter0: int = 0, generator: torch.Generator | None = None, td_gamma: float = TD_GAMMA,
-                    rollout_kw: dict | None = None, priority=None, **update_kw):
+                    rollout_kw: dict | None = None, priority=None, initial_states=None, **update_kw):
     """Iteration ``i_iter`` (1-based) of the reference's training loop (``sigmarl/mappo_cavs.py:126-150``) from its parts:
       1. ``collect`` with ``T = frames_per_batch // env.B`` steps (``frames_per_batch``: ``params``' unless given; not a multiple of ``env.B``: ``ValueError``) and
          ``returns``: the rollout, the critic's values, GAE, the TD-error priorities, the episode returns;
@@ -889,7 +901,10 @@ def train_iteration(env, actor, critic, actor_module, critic_module, optim, retu
     the tuple.  The priority head's entropy draw of step ``k`` is keyed with the base head's ``(seed, counter)`` under ``DRAW_PRIORITY_ENTROPY``, a further entry of the
     table: the statement above holds for it as it does for the others.  The learning rate of the next iteration goes into ``optim`` ALONE, as in the reference:
     ``_update_learning_rate`` walks ``optimization_module.optim.param_groups`` and nothing else, so the priority optimiser trains at the ``lr`` it was built with
-    (``sigmarl/modules/priority_module.py:122``) in every iteration."""
+    (``sigmarl/modules/priority_module.py:122``) in every iteration.
+
+    ``initial_states`` (an ``InitialStateBank`` of this env, ``Parameters.is_challenging_initial_state_buffer``): handed to ``collect``; the bank persists across
+    iterations."""
     p = params if params is not None else getattr(env, "parameters", None)
     if p is None:
         raise ValueError("train_iteration(): a Parameters (frames_per_batch, the discounts, the schedule)")
@@ -906,7 +921,7 @@ def train_iteration(env, actor, critic, actor_module, critic_module, optim, retu
     rkw = dict(rollout_kw or {})
     if priority is not None:
         rkw.update(priority=priority[0], priority_critic=priority[1])
-    batch = collect(env, actor, critic, T, params=p, td_gamma=td_gamma, td_error=True, seed=seed, counter0=counter0 + (k - 1) * T, returns=returns, **rkw)
+    batch = collect(env, actor, critic, T, params=p, td_gamma=td_gamma, td_error=True, seed=seed, counter0=counter0 + (k - 1) * T, returns=returns, initial_states=initial_states, **rkw)
     stats = batch["episode_stats"]
     if buffer is not None:
         buffer.extend(batch["td_error"])
@@ -917,7 +932,7 @@ def train_iteration(env, actor, critic, actor_module, critic_module, optim, retu
 
 
 def train(env, actor, critic, actor_module, critic_module, optim, params=None, *, n_iters: int | None = None, on_iteration=None, returns: EpisodeReturns | None = None,
-          buffer: PrioritizedBuffer | None = None, episode_reward_mean_list: list | None = None, **iteration_kw) -> list:
+          buffer: PrioritizedBuffer | None = None, episode_reward_mean_list: list | None = None, initial_states=None, **iteration_kw) -> list:
     """The reference's training loop (``sigmarl/mappo_cavs.py:121-150``): ``train_iteration`` for ``i_iter = 1 .. n_iters`` (``params.n_iters`` unless given; the
     schedule always runs over ``params.n_iters``) with one ``EpisodeReturns`` carried through (a new one unless given).  After every iteration, as ``_log_and_save``
     and ``_save_intermediate_model`` (``:468-515``) do: ``mean = EpisodeReturns.mean(stats)`` -- the one host read of the iteration -- is appended to
@@ -925,7 +940,8 @@ def train(env, actor, critic, actor_module, critic_module, optim, params=None, *
     rounding; never true for a NaN); if improved ``params.episode_reward_intermediate = mean``, else ``params.episode_reward_mean_current`` falls back to the best
     so far, as the reference's does.  Then ``on_iteration(i_iter, batch, infos, mean, improved)`` if given: the place where a caller saves models -- this loop writes
     no files.  The optimiser starts from whatever ``lr`` it holds (``params.lr`` in the reference).  Returns ``episode_reward_mean_list``.  ``iteration_kw`` may hold
-    ``rollout_kw=dict(wrapper="prioritized")`` and ``priority=(...)`` (``train_iteration``): the ``is_using_prioritized_marl`` / ``"marl"`` configuration end to end."""
+    ``rollout_kw=dict(wrapper="prioritized")`` and ``priority=(...)`` (``train_iteration``): the ``is_using_prioritized_marl`` / ``"marl"`` configuration end to end.
+    ``initial_states``: one ``InitialStateBank`` for every iteration (``is_challenging_initial_state_buffer``)."""
     p = params if params is not None else getattr(env, "parameters", None)
     if p is None:
         raise ValueError("train(): a Parameters")
@@ -933,7 +949,7 @@ def train(env, actor, critic, actor_module, critic_module, optim, params=None, *
     returns = returns if returns is not None else EpisodeReturns(env)
     means = episode_reward_mean_list if episode_reward_mean_list is not None else []
     for i_iter in range(1, n + 1):
-        batch, infos, stats = train_iteration(env, actor, critic, actor_module, critic_module, optim, returns, p, i_iter=i_iter, buffer=buffer, **iteration_kw)
+        batch, infos, stats = train_iteration(env, actor, critic, actor_module, critic_module, optim, returns, p, i_iter=i_iter, buffer=buffer, initial_states=initial_states, **iteration_kw)
         mean = EpisodeReturns.mean(stats)
         means.append(mean)
         p.episode_reward_mean_current = mean

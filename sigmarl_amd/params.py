@@ -144,6 +144,15 @@ def check_rollout_wrapper(p: Parameters | None, wrapper: str | None, communicati
                                   "would ignore it: pass communication_noise=params.communication_noise(p)")
 
 
+def check_initial_state_bank(p: Parameters | None, attached: bool) -> None:
+    """Parameters that ask for the challenging initial-state buffer (``is_challenging_initial_state_buffer``, road_traffic.py:702-708, :857-873, :1415-1427) and a
+    rollout with no ``initial_states.InitialStateBank`` attached: ``NotImplementedError`` -- the rollout would ignore what the parameters ask for; refused, never
+    ignored (the rule of ``check_rollout_wrapper`` for communication noise).  A bank attached without the flag is the caller's choice and runs."""
+    if p is not None and getattr(p, "is_challenging_initial_state_buffer", False) and not attached:
+        raise NotImplementedError("the parameters ask for is_challenging_initial_state_buffer and this rollout would ignore it: run it inside "
+                                  "initial_states.InitialStateBank(env).attached() (learn.collect / train_iteration / train: initial_states=bank)")
+
+
 def check_supported(p: Parameters) -> None:
     """Raise for observation/feature flags the fused step does not implement (fail loudly, never silently differ)."""
     bad = []
@@ -167,8 +176,8 @@ def check_supported(p: Parameters) -> None:
     # n_points_short_term is a build constant of the library: every value in 1 .. 8 has its own build (capi.variant_path; `make NS=k`)
     if not (1 <= int(p.n_points_short_term) <= capi.MAX_SHORT_TERM):
         bad.append(f"n_points_short_term={p.n_points_short_term} (1 .. {capi.MAX_SHORT_TERM})")
-    if p.is_challenging_initial_state_buffer:
-        bad.append("is_challenging_initial_state_buffer=True")
+    # is_challenging_initial_state_buffer IS built, as a device object next to the env: initial_states.InitialStateBank (sigmaenv_isb_*); a rollout of such parameters
+    # without a bank attached is refused by check_initial_state_bank, the host-driven VMAS surface by ScenarioRoadTraffic
     # is_using_opponent_modeling IS built: the placeholder columns (observation_provider_rt.py:606-611, capi.OBS_OPPONENT_PAD) and the gather of the
     # neighbours' tentative actions into them (SigmaEnv.opponent_fill; helper_training.py:1117-1137).
     # is_using_prioritized_marl: the environment's share is two extra info() entries (road_traffic.py:1513-1520, :1616-1625), built in scenario.info();

@@ -286,6 +286,10 @@ class ScenarioRoadTraffic(BaseScenario):
     """Drop-in for ``sigmarl.scenarios.road_traffic.ScenarioRoadTraffic`` (callbacks :104-1635; rendering is out of scope)."""
 
     def make_world(self, batch_dim: int, device, **kwargs):
+        if getattr(getattr(self, "parameters", None), "is_challenging_initial_state_buffer", False):
+            # this surface's resets are driven from the host (reset_world_at); the buffer lives on the device, in the rollouts that keep the host out of the loop
+            raise NotImplementedError("is_challenging_initial_state_buffer is not built on the VMAS surface (host-driven resets): use sigmarl_amd.initial_states."
+                                      "InitialStateBank with the device rollout (Actor.rollout / learn.collect)")
         device = torch.device(device)
         if device.type != "cuda":
             raise RuntimeError("sigmarl_amd.ScenarioRoadTraffic runs on an MI355X only (device='cuda:<i>'); there is no CPU fallback")
