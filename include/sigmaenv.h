@@ -345,6 +345,15 @@ typedef struct sigmaenv_launch_shape {
 } sigmaenv_launch_shape_t;
 int sigmaenv_launch_shape(const sigmaenv_t* h, sigmaenv_launch_shape_t* out);
 
+/* The pruned scan's create-time neighbour table of ONE polyline, on the host (no device, no handle): from its nch <= 64 chunk boxes (boxes[c] = min x, min y,
+ * max x, max y; min > max: a chunk without segments) and the vehicle's length and width, what sigmaenv_create uploads -- rows[c]: 32 bytes = a list of 28 chunk
+ * indices, one byte each, without c itself: the chunks within the tight radius of chunk c, then those only within the near radius, then those only within the far
+ * radius, each ring ascending; then three counts, the lengths of the tight / near / far prefix of the list, and a pad byte 0.  The bytes past the list's end repeat
+ * its last entry.  A count of 255 marks a level with more than 28 neighbours, as every wider level then is (the list stops with the widest level that fits; for a
+ * marked level the kernel takes the search over the group boxes) -- and, if masks is not NULL, masks[c][3]: the same three neighbourhoods as bit sets, c's own bit
+ * included.  Lets a host test hold the lists to the masks. */
+int sigmaenv_neigh_rows(const float* boxes, int32_t nch, float length, float width, uint8_t* rows, uint64_t* masks);
+
 /* The device side of the arithmetic contract's trigonometry (include/sigma_trig_f32.h; torch.sin / cos / tan / atan as called by
  * sigmarl/dynamics.py:103-111,161-168 and helper_scenario.py:795-810), evaluated on arrays: kind 0 sin, 1 cos, 2 tan, 3 atan of
  * in[0..n) -> out[0..n) (device pointers, f32).  Lets the GPU test-suite hold the device functions to the same bits as the host's. */

@@ -331,6 +331,7 @@ _PRODUCT_ONLY = {
     "set_rollout_slab_stride": (C.c_int, [C.c_void_p, C.c_int64]),
     "set_rollout_obs_record": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64]),
     "trig_selftest": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
+    "neigh_rows": (C.c_int, [C.c_void_p, C.c_int32, C.c_float, C.c_float, C.c_void_p, C.c_void_p]),
     "step_autoreset": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_int32, C.c_int32]),
     "step_autoreset_n": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_int64, C.c_uint64, C.c_uint64, C.c_int32, C.c_int32]),
     "step_autoreset_many": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int32, C.c_int32]),

@@ -374,30 +374,74 @@ __device__ __forceinline__ bool box_within(const float4 b, float px, float py, f
 struct MaskTask {
   int sl, pl, path, k, npt, nch;
   float ax, ay, bx, by;          // the segment that was closest last step
-  unsigned long long nm_tight, nm_near, nm_far;
+  uint4 row_lo, row_hi;          // the NeighRow of the chunk of that segment, as loaded (stage 1 -> stage 2)
   int lvl;                       // neighbour level the threshold selects: 0 tight, 1 near, 2 far, 3 none (two-level search over all boxes)
   int own;                       // chunk of the segment that was closest last step
   const float4* box;
   float px, py, T2;
-  unsigned long long rest;  // neighbour-mask bits to test
-  bool fast;
+  int cnt;                       // the length of the level's prefix of the row's list (list position j is byte j % 4 of word j / 4)
+  bool own_within;               // the own chunk is within T by construction (T + dg reaches no farther than the widest level): its bit is set untested
+  bool fast;                     // the candidates come from the list (else: the two-level search)
 };
+// The ONE reader of a NeighRow: the prefix length of the level the threshold asks for, or, where that level was cut at create time (as every wider one then was),
+// level 3: the two-level search.  Exact either way: the list only says WHICH boxes are tested, box_within decides.
+__device__ __forceinline__ void neigh_row_load(const DevMap& m, MaskTask& mt, int chunk) {
+  const uint4* r = reinterpret_cast<const uint4*>(m.chunk_neigh + (((size_t)mt.path * 3 + mt.pl) * m.nch + chunk));
+  mt.row_lo = r[0]; mt.row_hi = r[1];
+}
+__device__ __forceinline__ void neigh_list_select(MaskTask& mt, int lvl) {
+  const uint32_t cw = mt.row_hi.w;  // NeighRow::cnt
+  const uint32_t cnt = (cw >> (8 * (lvl & 3))) & 0xFFu;  // (level 3 reads the pad byte: 0)
+  const bool marked = cnt == NEIGH_OVERFLOW;
+  mt.lvl = marked ? 3 : lvl;
+  mt.fast = lvl < 3 && !marked;
+  mt.cnt = marked ? 0 : (int)cnt;
+}
+// The candidate chunks among the listed neighbours: list positions 0 .. 7 with their eight box loads in flight together, then four positions at a time; a lane takes
+// part in a round while its prefix reaches into it, so the wavefront runs as many rounds as its longest prefix needs.  Within a round no position is checked against
+// the count (see NeighRow).  The position is a constant, so a byte is one bit-field extract, and the box comes from the table base (scalar) plus a 32-bit lane
+// offset.  Call with the lanes that have a task.
+template <int POS0, int WIDTH>
+__device__ __forceinline__ void neigh_round(const DevMap& m, const MaskTask& mt, unsigned row0, unsigned long long& mk) {
+  const uint32_t word[8] = {mt.row_lo.x, mt.row_lo.y, mt.row_lo.z, mt.row_lo.w, mt.row_hi.x, mt.row_hi.y, mt.row_hi.z, mt.row_hi.w};
+  const char* const base = reinterpret_cast<const char*>(m.chunk_box);
+  unsigned idx[WIDTH];
+  float4 b[WIDTH];
+#pragma unroll
+  for (int q = 0; q < WIDTH; ++q) {
+    idx[q] = (word[(POS0 + q) / 4] >> (8 * ((POS0 + q) % 4))) & 0xFFu;
+    b[q] = *reinterpret_cast<const float4*>(base + (size_t)(row0 + idx[q] * (unsigned)sizeof(float4)));
+  }
+#pragma unroll
+  for (int q = 0; q < WIDTH; ++q) mk |= (unsigned long long)box_within(b[q], mt.px, mt.py, mt.T2) << idx[q];
+}
+__device__ __forceinline__ unsigned long long neigh_candidates(const DevMap& m, const MaskTask& mt) {
+  unsigned long long mk = 0ull;
+  const unsigned row0 = (unsigned)((mt.path * 3 + mt.pl) * m.nch) * (unsigned)sizeof(float4);
+  if (0 < mt.cnt) neigh_round<0, 8>(m, mt, row0, mk);
+  if (8 < mt.cnt) neigh_round<8, 4>(m, mt, row0, mk);
+  if (12 < mt.cnt) neigh_round<12, 4>(m, mt, row0, mk);
+  if (16 < mt.cnt) {  // (dense maps only)
+    neigh_round<16, 4>(m, mt, row0, mk);
+    if (20 < mt.cnt) neigh_round<20, 4>(m, mt, row0, mk);
+    if (24 < mt.cnt) neigh_round<24, 4>(m, mt, row0, mk);
+  }
+  return mk;
+}
 __device__ __forceinline__ void mask_stage1(const DevMap& m, MaskTask& mt, int task, int path, int cp) {
   mt.sl = task / 3; mt.pl = task - mt.sl * 3; mt.path = path;
   const int pl = mt.pl;
   const float* poly = m.center + (size_t)pl * m.poly_stride + (size_t)path * m.P * 2;
   mt.box = m.chunk_box + ((size_t)path * 3 + pl) * m.nch;
-  const ulonglong4* neigh = m.chunk_neigh + ((size_t)path * 3 + pl) * m.nch;
   // One round trip: the point count, and -- speculatively, the index is almost always in range -- the segment that was closest
-  // last step together with the neighbour masks of its chunk.
+  // last step together with the neighbour lists of its chunk.
   int k = cp - 1;
   k = k < 0 ? 0 : (k > m.P - 2 ? m.P - 2 : k);
   mt.k = k;
   mt.npt = m.n_center[pl * m.n_paths + path];
   const Seg4 sg = load_segment(reinterpret_cast<const float2*>(poly), k);
   mt.ax = sg.ax; mt.ay = sg.ay; mt.bx = sg.bx; mt.by = sg.by;
-  const ulonglong4 nm = neigh[k / SIGMAENV_CHUNK];
-  mt.nm_tight = nm.x; mt.nm_near = nm.y; mt.nm_far = nm.z;
+  neigh_row_load(m, mt, k / SIGMAENV_CHUNK);
   mt.own = k / SIGMAENV_CHUNK;
 }
 template <bool COLLIDE>
@@ -408,8 +452,7 @@ __device__ __forceinline__ void mask_stage2(const DevMap& m, const Smem& s, Mask
     const int k = npt - 2 < 0 ? 0 : npt - 2;
     const Seg4 sg = load_segment(reinterpret_cast<const float2*>(poly), k);
     mt.ax = sg.ax; mt.ay = sg.ay; mt.bx = sg.bx; mt.by = sg.by;
-    const ulonglong4 nm = (m.chunk_neigh + ((size_t)mt.path * 3 + pl) * m.nch)[k / SIGMAENV_CHUNK];
-    mt.nm_tight = nm.x; mt.nm_near = nm.y; mt.nm_far = nm.z;
+    neigh_row_load(m, mt, k / SIGMAENV_CHUNK);
     mt.own = k / SIGMAENV_CHUNK;
   }
   const float px = s.st[sl * 8], py = s.st[sl * 8 + 1];
@@ -452,30 +495,16 @@ __device__ __forceinline__ void mask_stage2(const DevMap& m, const Smem& s, Mask
   mt.T2 = T * T;
   mt.nch = (npt - 1 + SIGMAENV_CHUNK - 1) / SIGMAENV_CHUNK;
   // Every chunk within T of the agent is within T + dg of the chunk of that segment (the segment lies inside its chunk's box and is
-  // dg away), i.e. in the precomputed neighbour mask of that radius (the wider one mostly serves the agent whose query points are
-  // stale): only those few boxes are tested, eight loads in flight at a time.
-  mt.fast = T + dg <= m.neigh_radius_far;
-  mt.lvl = mt.fast ? ((T + dg <= m.neigh_radius_tight) ? 0 : ((T + dg <= m.neigh_radius) ? 1 : 2)) : 3;
-  mt.rest = mt.fast ? (mt.lvl == 0 ? mt.nm_tight : (mt.lvl == 1 ? mt.nm_near : mt.nm_far)) : 0ull;
+  // dg away), i.e. in the precomputed neighbour list of that radius (the wider one mostly serves the agent whose query points are
+  // stale): only those few boxes are tested (neigh_candidates).
+  mt.own_within = T + dg <= m.neigh_radius_far;
+  neigh_list_select(mt, mt.own_within ? ((T + dg <= m.neigh_radius_tight) ? 0 : ((T + dg <= m.neigh_radius) ? 1 : 2)) : 3);
 }
 __device__ __forceinline__ void mask_stage3(const DevMap& m, const Smem& s, MaskTask& mt, int task) {
   const float px = mt.px, py = mt.py, T2 = mt.T2;
   const int nch = mt.nch;
-  unsigned long long mk = 0ull;
-  unsigned long long rest = mt.rest;
-  if (mt.fast && mt.own < nch) { mk |= 1ull << mt.own; rest &= ~(1ull << mt.own); }  // (see scan_tile_balanced)
-  while (rest) {  // one pass unless the neighbourhood has more than eight chunks (dense map regions with the wide radius)
-    int idx[8];
-#pragma unroll
-    for (int q = 0; q < 8; ++q) { idx[q] = rest ? (__ffsll((long long)rest) - 1) : -1; rest &= rest - 1ull; }
-    float4 b[8];
-#pragma unroll
-    for (int q = 0; q < 8; ++q) b[q] = mt.box[idx[q] < 0 ? 0 : idx[q]];
-#pragma unroll
-    for (int q = 0; q < 8; ++q) {
-      if (idx[q] >= 0 && idx[q] < nch && box_within(b[q], px, py, T2)) mk |= 1ull << idx[q];
-    }
-  }
+  unsigned long long mk = neigh_candidates(m, mt);
+  if (mt.own_within && mt.own < nch) mk |= 1ull << mt.own;  // (see scan_tile_balanced)
   if (!mt.fast) {
     // far from the own path (or a NaN state): two-level search over all boxes -- the <= 8 group boxes, then the 8 chunk boxes of
     // every group within the threshold
@@ -1978,6 +2007,22 @@ static int poison_probe(hipStream_t stream) {
 }
 #endif
 
+extern "C" int sigmaenv_neigh_rows(const float* boxes, int32_t nch, float length, float width, uint8_t* rows, uint64_t* masks) {
+  if (!boxes || !rows || nch < 1 || nch > 64) return SIGMAENV_EINVAL;
+  float radius[3];
+  neigh_radii(length, width, radius);
+  std::vector<NeighRow> r((size_t)nch);
+  std::vector<unsigned long long> mk((size_t)nch * 3);
+  std::vector<float4> bx((size_t)nch);
+  for (int c = 0; c < nch; ++c) bx[c] = make_float4(boxes[4 * c], boxes[4 * c + 1], boxes[4 * c + 2], boxes[4 * c + 3]);
+  neigh_rows_build(bx.data(), nch, radius, r.data(), mk.data());
+  memcpy(rows, r.data(), r.size() * sizeof(NeighRow));
+  if (masks) {
+    for (size_t i = 0; i < mk.size(); ++i) masks[i] = (uint64_t)mk[i];
+  }
+  return SIGMAENV_OK;
+}
+
 extern "C" int sigmaenv_create(const sigmaenv_config_t* cfg, const sigmaenv_map_t* map, int device_id, void* hip_stream, sigmaenv_t** out) {
   if (!cfg || !map || !out) return SIGMAENV_EINVAL;
   *out = nullptr;
@@ -2090,14 +2135,11 @@ extern "C" int sigmaenv_create(const sigmaenv_config_t* cfg, const sigmaenv_map_
   if (const char* e = getenv("SIGMAENV_PRUNE")) prune = prune && atoi(e) != 0;
   float4 *d_box = nullptr, *d_gbox = nullptr;
   std::vector<float4> hb, hg;  // must outlive the asynchronous uploads below
-  std::vector<ulonglong4> hn;
-  ulonglong4* d_neigh = nullptr;
-  const float neigh_radius_far = 9.0f * (sqrtf((float)((double)cfg->length / 2.0) * (float)((double)cfg->length / 2.0) +
-                                               (float)((double)cfg->width / 2.0) * (float)((double)cfg->width / 2.0)) * 1.00001f + 1e-5f);
-  const float neigh_radius_tight = 3.6f * (sqrtf((float)((double)cfg->length / 2.0) * (float)((double)cfg->length / 2.0) +
-                                                 (float)((double)cfg->width / 2.0) * (float)((double)cfg->width / 2.0)) * 1.00001f + 1e-5f);
-  const float neigh_radius = 6.0f * (sqrtf((float)((double)cfg->length / 2.0) * (float)((double)cfg->length / 2.0) +
-                                           (float)((double)cfg->width / 2.0) * (float)((double)cfg->width / 2.0)) * 1.00001f + 1e-5f);
+  std::vector<NeighRow> hn;
+  NeighRow* d_neigh = nullptr;
+  float radius[3];  // tight, near, far
+  neigh_radii(cfg->length, cfg->width, radius);
+  const float neigh_radius_tight = radius[0], neigh_radius = radius[1], neigh_radius_far = radius[2];
   if (prune) {
     hb.assign((size_t)np * 3 * nch, make_float4(1e30f, 1e30f, -1e30f, -1e30f));
     for (int p = 0; p < np; ++p) {
@@ -2126,28 +2168,11 @@ extern "C" int sigmaenv_create(const sigmaenv_config_t* cfg, const sigmaenv_map_
     }
     ALLOC(d_gbox, hg.size() * sizeof(float4));
     H2D(d_gbox, hg.data(), hg.size() * sizeof(float4));
-    // neighbour masks: chunks whose box is within neigh_radius of a chunk's box (double arithmetic, inclusive with slack)
-    hn.assign((size_t)np * 3 * nch, make_ulonglong4(0ull, 0ull, 0ull, 0ull));
-    for (size_t pq = 0; pq < (size_t)np * 3; ++pq) {
-      for (int a = 0; a < nch; ++a) {
-        const float4& A = hb[pq * nch + a];
-        if (A.x > A.z) continue;
-        unsigned long long bits = 0ull, bits_far = 0ull, bits_tight = 0ull;
-        for (int b2 = 0; b2 < nch; ++b2) {
-          const float4& Bx = hb[pq * nch + b2];
-          if (Bx.x > Bx.z) continue;
-          double dx = std::max(std::max((double)A.x - Bx.z, (double)Bx.x - A.z), 0.0);
-          double dy = std::max(std::max((double)A.y - Bx.w, (double)Bx.y - A.w), 0.0);
-          const double dd = std::sqrt(dx * dx + dy * dy);
-          if (dd <= (double)neigh_radius_tight + 1e-5) bits_tight |= 1ull << b2;
-          if (dd <= (double)neigh_radius + 1e-5) bits |= 1ull << b2;
-          if (dd <= (double)neigh_radius_far + 1e-5) bits_far |= 1ull << b2;
-        }
-        hn[pq * nch + a] = make_ulonglong4(bits_tight, bits, bits_far, 0ull);
-      }
-    }
-    ALLOC(d_neigh, hn.size() * sizeof(ulonglong4));
-    H2D(d_neigh, hn.data(), hn.size() * sizeof(ulonglong4));
+    // neighbour lists: per chunk, the chunks whose box is within each of the three radii of its box (neigh_rows_build)
+    hn.resize((size_t)np * 3 * nch);
+    for (size_t pq = 0; pq < (size_t)np * 3; ++pq) neigh_rows_build(hb.data() + pq * nch, nch, radius, hn.data() + pq * nch, nullptr);
+    ALLOC(d_neigh, hn.size() * sizeof(NeighRow));
+    H2D(d_neigh, hn.data(), hn.size() * sizeof(NeighRow));
   }
   const float lh = (float)((double)cfg->length / 2.0), wh = (float)((double)cfg->width / 2.0);
   const float rect_radius = sqrtf(lh * lh + wh * wh) * 1.00001f + 1e-5f;

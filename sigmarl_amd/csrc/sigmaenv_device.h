@@ -12,6 +12,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <algorithm>
+#include <cmath>
+
 #include "../../include/sigmaenv.h"
 #include "../../include/sigma_trig_f32.h"
 #include "sigmaenv_dist.h"  // rng_u32, the draw table and the word-to-number conversions
@@ -40,6 +43,67 @@ __device__ __forceinline__ void sigma_poison_lds() {
 __device__ __forceinline__ void sigma_poison_lds() {}
 #endif
 
+// A chunk's neighbours at the three radii of sigmaenv_create, as the step kernel walks them: ONE list of chunk indices, one byte each (a pruned map has at most 64
+// chunks per polyline), WITHOUT the chunk itself -- its bit is set untested: first the chunks within the tight radius, then those only within the near radius, then
+// those only within the far radius, each ring ascending; cnt[l] is the length of level l's prefix.  The kernel tests whole groups of positions, so what follows a
+// prefix may be tested too: that is a chunk of a wider ring (a superset of boxes gives the same candidates, box_within decides), and past the list's end its last
+// entry again (a chunk tested twice sets the same bit); an empty list is all 0.  A level with more neighbours than the list holds has the count NEIGH_OVERFLOW, as
+// has every wider level, and the list stops with the widest level that fits: for a marked level the kernel takes the two-level search over the group boxes
+// (neigh_list_select is the one reader).  32 bytes: what mask_stage1 fetches in its one speculative round trip.
+#define NEIGH_CAP 28
+#define NEIGH_OVERFLOW 0xFFu
+struct alignas(16) NeighRow {
+  uint8_t list[NEIGH_CAP];
+  uint8_t cnt[3];  // tight, near, far: prefix lengths, or NEIGH_OVERFLOW
+  uint8_t pad;
+};
+static_assert(sizeof(NeighRow) == 32, "NeighRow is two 16-byte loads");
+// The three radii, in multiples of the vehicle rectangle's half diagonal (with the slack of rect_radius): tight, near, far.
+inline void neigh_radii(float length, float width, float radius[3]) {
+  const float lh = (float)((double)length / 2.0), wh = (float)((double)width / 2.0);
+  const float r = sqrtf(lh * lh + wh * wh) * 1.00001f + 1e-5f;
+  radius[0] = 3.6f * r; radius[1] = 6.0f * r; radius[2] = 9.0f * r;
+}
+inline void neigh_rows_build(const float4* box, int nch, const float radius[3], NeighRow* rows, unsigned long long* masks) {
+  for (int a = 0; a < nch; ++a) {
+    NeighRow r{};
+    unsigned long long bits[3] = {0ull, 0ull, 0ull};
+    const float4& A = box[a];
+    if (!(A.x > A.z)) {
+      for (int b = 0; b < nch; ++b) {
+        const float4& B = box[b];
+        if (B.x > B.z) continue;
+        const double dx = std::max(std::max((double)A.x - B.z, (double)B.x - A.z), 0.0);
+        const double dy = std::max(std::max((double)A.y - B.w, (double)B.y - A.w), 0.0);
+        const double dd = std::sqrt(dx * dx + dy * dy);
+        for (int l = 0; l < 3; ++l) {
+          if (dd <= (double)radius[l] + 1e-5) bits[l] |= 1ull << b;
+        }
+      }
+    }
+    int n = 0;
+    for (int l = 0; l < 3; ++l) {
+      const unsigned long long ring = bits[l] & ~(l ? bits[l - 1] : 0ull) & ~(1ull << (a & 63));
+      const int len = n + __builtin_popcountll(ring);
+      if (n == (int)NEIGH_OVERFLOW || len > NEIGH_CAP) {
+        n = NEIGH_OVERFLOW;
+      } else {
+        for (int b = 0; b < nch && b < 64; ++b) {  // (a pruned map has real segments in at most 64 chunks; the table's stride may count padding beyond)
+          if ((ring >> b) & 1ull) r.list[n++] = (uint8_t)b;
+        }
+      }
+      r.cnt[l] = (uint8_t)n;
+      if (masks) masks[a * 3 + l] = bits[l];
+    }
+    int stored = 0;
+    for (int l = 0; l < 3; ++l) {
+      if (r.cnt[l] != NEIGH_OVERFLOW) stored = r.cnt[l];
+    }
+    for (int j2 = stored; j2 < NEIGH_CAP && stored > 0; ++j2) r.list[j2] = r.list[stored - 1];
+    rows[a] = r;
+  }
+}
+
 struct DevMap {
   const float* center;  // [n_paths][P][2] padded (world_state_rt.py:313-420)
   const float* left;
@@ -53,7 +117,7 @@ struct DevMap {
   // pruning table: axis-aligned boxes of runs of CHUNK consecutive real segments, [n_paths][3 (centre,left,right)][nch]
   const float4* chunk_box;  // (min_x, min_y, max_x, max_y)
   const float4* group_box;  // union boxes of groups of 8 consecutive chunks, [n_paths][3][8]
-  const ulonglong4* chunk_neigh;  // [n_paths][3][nch]: bit c set iff the box of chunk c is within neigh_radius_tight (.x) / neigh_radius (.y) / neigh_radius_far (.z) of this chunk's box
+  const NeighRow* chunk_neigh;  // [n_paths][3][nch]: per chunk, the chunks whose box is within neigh_radius_tight / neigh_radius / neigh_radius_far of its box, as index lists
   float neigh_radius, neigh_radius_far;
   int32_t nch;              // boxes per polyline (stride); 0 disables pruning (brute-force scan)
   const float* start_table; // derived state of an agent freshly placed on centre-line point pt of path p, [n_paths][P][START_ROW]

@@ -341,20 +341,8 @@ __device__ __forceinline__ void scan_tile_balanced(const DevMap& m, const CfgDer
 #endif
       const float px = mt.px, py = mt.py, T2 = mt.T2;
       const int nch = mt.nch;
-      unsigned long long rest = mt.rest;
-      if (mt.fast && mt.own < nch) { mk |= 1ull << mt.own; rest &= ~(1ull << mt.own); }  // the chunk of last step's closest segment is within T by construction
-      while (rest) {  // the boxes of the neighbour chunks, eight loads in flight
-        int idx[8];
-#pragma unroll
-        for (int q = 0; q < 8; ++q) { idx[q] = rest ? (__ffsll((long long)rest) - 1) : -1; rest &= rest - 1ull; }
-        float4 b[8];
-#pragma unroll
-        for (int q = 0; q < 8; ++q) b[q] = mt.box[idx[q] < 0 ? 0 : idx[q]];
-#pragma unroll
-        for (int q = 0; q < 8; ++q) {
-          if (idx[q] >= 0 && idx[q] < nch && box_within(b[q], px, py, T2)) mk |= 1ull << idx[q];
-        }
-      }
+      mk = neigh_candidates(m, mt);  // the boxes of the listed neighbour chunks
+      if (mt.own_within && mt.own < nch) mk |= 1ull << mt.own;  // the chunk of last step's closest segment is within T by construction
       if (!mt.fast) {  // far from the own path: two-level search over all boxes
         const float4* gbox = m.group_box + ((size_t)mt.path * 3 + pl) * 8;
         unsigned gm = 0u;
