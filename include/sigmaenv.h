@@ -1115,6 +1115,8 @@ typedef struct sigmaenv_isb sigmaenv_isb_t;
 #define SIGMAENV_ISB_HELD 5       /* i32 [B] */
 #define SIGMAENV_ISB_HEAD 6       /* i32 [B] */
 #define SIGMAENV_ISB_PENDING 7    /* u8  [B] */
+#define SIGMAENV_ISB_EPISODES 8   /* i32 [B]: the bank's copy of the envs' episodes_reset (sigmaenv_isb_settle compares against it); with ids 0 .. 7 every word a
+                                   * checkpoint of the bank holds */
 #define SIGMAENV_ISB_CHUNK 1024   /* envs per chunk of sigmaenv_isb_record's ranking workgroup (ISB_CHUNK of sigmaenv_isb.h) */
 int sigmaenv_isb_create(sigmaenv_t* h, int32_t capacity, int32_t n_steps_stored, float p_record, float p_use, sigmaenv_isb_t** out);
 void sigmaenv_isb_destroy(sigmaenv_isb_t* bank);
@@ -1125,6 +1127,41 @@ int sigmaenv_isb_settle(sigmaenv_t* h, sigmaenv_isb_t* bank);
 int sigmaenv_isb_attach(sigmaenv_t* h, sigmaenv_isb_t* bank);
 int sigmaenv_isb_get(sigmaenv_t* h, sigmaenv_isb_t* bank, int32_t what, void** dev_ptr, size_t* bytes);
 int sigmaenv_isb_set(sigmaenv_t* h, sigmaenv_isb_t* bank, const float* state_rows, const int32_t* path_rows, int32_t count);
+
+/* ---- Snapshot and restore of a handle's state (sigmarl_amd/csrc/sigmaenv_snapshot.h, sigmaenv_snapshot.inc) --------------------------------------------------------
+ * The reference resumes a training run from the policy's and the critic's weights alone (is_load_model / is_continue_train, sigmarl/mappo_cavs.py:100-105, :219-306):
+ * the envs start afresh.  Here every draw is a function of (seed, counter, env, agent, draw id) and no kernel uses atomics, so a handle whose buffers are put back
+ * continues bit for bit.  The STATE of a handle is every device buffer whose content at the start of a call can change a later result -- the 21 SIGMAENV_BUF_*,
+ * reset_mask, reset_full, fresh (SIGMAENV_OBS_BOUNDARY_POINTS), cbf_groups (CBF tables attached with is_grouping) -- and two host words (the count of stand-alone
+ * sigmaenv_observe calls, the validity of the CBF groups).  sigmaenv_snapshot.h is the one statement of the segment table (id, element size, bytes per env, outer
+ * blocks and their stride, offset in the blob; offsets are multiples of 16; a total) and lists what is deliberately not state: scratch, staging, workspaces, timing
+ * pools and the caller's settings (slab pointer and strides, observation record, attached evaluator or bank, lanelet and scenario lists).
+ *
+ * sigmaenv_state_layout   fills the host header of the handle as it stands: magic, layout version, the seven quantities the layout is a function of (n_envs, n_agents,
+ *                         n_nearing, obs_dim, n_short_term, obs_flags, cbf: 0 none / 1 tables attached / 2 attached with groups), total_bytes and the two host words.
+ *                         No build id: a blob outlives a rebuild that leaves the layout alone.  Launches nothing, waits for nothing.
+ * sigmaenv_state_save     packs every segment into dev_blob (DEVICE, 16-byte aligned, bytes == total_bytes) in ONE launch on the handle's stream; no host wait.  Every
+ *                         byte of the blob is written (the padding between segments with zeros): equal states give equal blobs.  The
+ *                         host words of that moment are the ones sigmaenv_state_layout returns when called next to it.
+ * sigmaenv_state_restore  the inverse.  env_mask == NULL: every env, and the handle takes over the header's host words.  Otherwise env_mask is a DEVICE u8 [n_envs]:
+ *                         only envs with a non-zero byte are written, in every segment; no word of another env is stored to (not even with its own value), and the
+ *                         host words stay.  Afterwards the selected envs' buffers are the snapshot's bits; nothing is re-derived.  ONE launch, no host wait.
+ * Refused with SIGMAENV_EINVAL before any launch (sigmaenv_last_error names the reason): a null or not 16-byte aligned blob; bytes != total_bytes; a header whose
+ * magic, version or any of the seven quantities differs from the handle's (the message names the first difference). */
+#define SIGMAENV_STATE_MAGIC 0x50414E53u /* "SNAP" */
+#define SIGMAENV_STATE_VERSION 1u
+typedef struct sigmaenv_state_header {
+  uint32_t magic, version;
+  int32_t n_envs, n_agents, n_nearing, obs_dim, n_short_term, obs_flags, cbf;
+  uint32_t observe_calls;     /* host word: stand-alone sigmaenv_observe calls so far */
+  uint32_t cbf_groups_valid;  /* host word: the grouped CBF-QP has formed its partition */
+  uint32_t reserved0;
+  uint64_t total_bytes;
+  uint32_t reserved[2];
+} sigmaenv_state_header_t;
+int sigmaenv_state_layout(sigmaenv_t* h, sigmaenv_state_header_t* out);
+int sigmaenv_state_save(sigmaenv_t* h, void* dev_blob, size_t bytes);
+int sigmaenv_state_restore(sigmaenv_t* h, const sigmaenv_state_header_t* hdr, const void* dev_blob, size_t bytes, const uint8_t* env_mask);
 
 #ifdef __cplusplus
 }

@@ -221,8 +221,35 @@ def prb_level_sizes(capacity: int) -> list:
 
 
 ISB_BANK_STATE, ISB_BANK_PATH, ISB_WORDS, ISB_RING_STATE, ISB_RING_PATH, ISB_HELD, ISB_HEAD, ISB_PENDING = range(8)  # SIGMAENV_ISB_*: what sigmaenv_isb_get points at
+ISB_EPISODES = 8  # SIGMAENV_ISB_EPISODES: the bank's copy of the envs' episodes_reset (with 0 .. 7: every word of the bank)
 ISB_CHUNK, ISB_MAX_CAPACITY, ISB_MAX_STEPS_STORED = 1024, 65536, 1024  # sigmaenv_isb.h
 ISB_DRAW_RECORD, ISB_DRAW_USE, ISB_DRAW_INDEX = 5100, 5101, 5102  # DRAW_ISB_* of the draw table (sigmaenv_dist.h)
+
+
+STATE_MAGIC, STATE_VERSION = 0x50414E53, 1  # SIGMAENV_STATE_MAGIC ("SNAP"), SIGMAENV_STATE_VERSION
+STATE_CBF_NONE, STATE_CBF_ATTACHED, STATE_CBF_GROUPED = 0, 1, 2  # the header's ``cbf`` quantity (sigmaenv_snapshot.h)
+
+
+class StateHeader(C.Structure):
+    """``sigmaenv_state_header_t`` (sigmaenv_state_layout / _restore): magic, layout version, the seven quantities the segment table is a function of, the handle's two
+    host words and the blob's size."""
+
+    _fields_ = [("magic", C.c_uint32), ("version", C.c_uint32), ("n_envs", C.c_int32), ("n_agents", C.c_int32), ("n_nearing", C.c_int32), ("obs_dim", C.c_int32),
+                ("n_short_term", C.c_int32), ("obs_flags", C.c_int32), ("cbf", C.c_int32), ("observe_calls", C.c_uint32), ("cbf_groups_valid", C.c_uint32),
+                ("reserved0", C.c_uint32), ("total_bytes", C.c_uint64), ("reserved", C.c_uint32 * 2)]
+
+    QUANTITIES = ("n_envs", "n_agents", "n_nearing", "obs_dim", "n_short_term", "obs_flags", "cbf")
+    WORDS = ("magic", "version") + QUANTITIES + ("observe_calls", "cbf_groups_valid", "total_bytes")
+
+    def as_dict(self) -> dict:
+        return {k: int(getattr(self, k)) for k in self.WORDS}
+
+    @classmethod
+    def from_dict(cls, d: dict) -> "StateHeader":
+        h = cls()
+        for k in cls.WORDS:
+            setattr(h, k, int(d[k]))
+        return h
 
 
 PPO_SUMS = 5  # SIGMAENV_PPO_SUMS: partial sums per workgroup of 256 rows in sigmaenv_ppo_head's workspace
@@ -401,6 +428,9 @@ _PRODUCT_ONLY = {
     "isb_attach": (C.c_int, [C.c_void_p, C.c_void_p]),
     "isb_get": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t)]),
     "isb_set": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]),
+    "state_layout": (C.c_int, [C.c_void_p, C.POINTER(StateHeader)]),
+    "state_save": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
+    "state_restore": (C.c_int, [C.c_void_p, C.POINTER(StateHeader), C.c_void_p, C.c_size_t, C.c_void_p]),
 }
 
 

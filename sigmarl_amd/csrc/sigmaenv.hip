@@ -2775,3 +2775,5 @@ extern "C" int sigmaenv_trig_selftest(sigmaenv_t* h, int32_t kind, int32_t n, co
 #include "sigmaenv_isb.h"
 #include "sigmaenv_isb.inc"
 #include "sigmaenv_cbf.inc"
+#include "sigmaenv_snapshot.h"
+#include "sigmaenv_snapshot.inc"

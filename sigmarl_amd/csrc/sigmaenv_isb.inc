@@ -318,6 +318,7 @@ extern "C" int sigmaenv_isb_get(sigmaenv_t* h, sigmaenv_isb* k, int32_t what, vo
     case SIGMAENV_ISB_HELD: *dev_ptr = k->held; *bytes = B * 4; break;
     case SIGMAENV_ISB_HEAD: *dev_ptr = k->head; *bytes = B * 4; break;
     case SIGMAENV_ISB_PENDING: *dev_ptr = k->pending; *bytes = B; break;
+    case SIGMAENV_ISB_EPISODES: *dev_ptr = k->epi; *bytes = B * 4; break;
     default: h->err = "isb_get: unknown item"; return SIGMAENV_EINVAL;
   }
   return SIGMAENV_OK;

@@ -97,6 +97,29 @@ def device_view(ptr, shape, kind, device_index, owner):
     return t
 
 
+class Snapshot:
+    """The state of a ``SigmaEnv`` at one moment (``SigmaEnv.snapshot``): ``header``, the words of ``sigmaenv_state_header_t`` as a dict (magic, layout version, the
+    seven quantities the layout is a function of, the handle's two host words, ``total_bytes``); ``blob``, one ``uint8`` tensor of ``total_bytes`` bytes (the segment
+    table: ``sigmarl_amd/csrc/sigmaenv_snapshot.h``); ``reset_counter``, the env object's running counter of the calls that name none.  ``cpu()`` / ``to(device)``
+    return a snapshot with the blob there; ``state_dict()`` / ``from_state_dict`` are the plain form a checkpoint file holds."""
+
+    def __init__(self, header: dict, blob: torch.Tensor, reset_counter: int = 0):
+        self.header, self.blob, self.reset_counter = dict(header), blob, int(reset_counter)
+
+    def to(self, device) -> "Snapshot":
+        return Snapshot(self.header, self.blob.to(device), self.reset_counter)
+
+    def cpu(self) -> "Snapshot":
+        return self.to("cpu")
+
+    def state_dict(self) -> dict:
+        return {"header": dict(self.header), "blob": self.blob, "reset_counter": self.reset_counter}
+
+    @classmethod
+    def from_state_dict(cls, d: dict) -> "Snapshot":
+        return cls(d["header"], d["blob"], d.get("reset_counter", 0))
+
+
 class SigmaEnv:
     """One env shard on one GPU.  ``step(actions)`` is one fused HIP launch over agents x envs."""
 
@@ -387,6 +410,60 @@ class SigmaEnv:
 
     def sync(self):
         self._chk(self.lib.sync(self.h), "sync")
+
+    # ---- snapshot and restore (sigmaenv_state_*) ------------------------------------------------------------------------------
+    def state_header(self) -> "capi.StateHeader":
+        """``sigmaenv_state_layout``: the host header of the handle as it stands (no launch, no wait)."""
+        hdr = capi.StateHeader()
+        self._chk(self.lib.state_layout(self.h, C.byref(hdr)), "state_layout")
+        return hdr
+
+    def _on_stream(self, what, fn, tensors):
+        """``fn()`` on the env's stream after what torch's current stream holds, which then waits for it."""
+        cur = torch.cuda.current_stream(self.device)
+        with torch.cuda.device(self.device):
+            self.stream.wait_stream(cur)
+            self._chk(fn(), what)
+            cur.wait_stream(self.stream)
+        for t in tensors:
+            t.record_stream(self.stream)
+
+    def snapshot(self, out: "Snapshot | None" = None) -> "Snapshot":
+        """Every device buffer a later result can depend on, packed into one ``uint8`` CUDA tensor by ONE launch on the env's stream (``sigmaenv_state_save``); nothing
+        waits on the host.  ``out``: a snapshot of this env's layout on its device whose blob is overwritten (no allocation)."""
+        hdr = self.state_header()
+        n = int(hdr.total_bytes)
+        if out is None:
+            blob = torch.empty((n,), dtype=torch.uint8, device=self.device)
+        else:
+            blob = out.blob
+            if not (isinstance(blob, torch.Tensor) and blob.is_cuda and blob.device == self.device and blob.dtype == torch.uint8 and blob.is_contiguous() and blob.numel() == n):
+                raise ValueError(f"snapshot(out=): the blob must be a contiguous uint8 tensor of {n} bytes on {self.device}")
+        self._on_stream("state_save", lambda: self.lib.state_save(self.h, C.c_void_p(blob.data_ptr()), n), (blob,))
+        if out is None:
+            return Snapshot(hdr.as_dict(), blob, self._reset_counter)
+        out.header, out.reset_counter = hdr.as_dict(), self._reset_counter
+        return out
+
+    def restore(self, snap: "Snapshot", envs: torch.Tensor | None = None) -> None:
+        """The inverse of ``snapshot`` (``sigmaenv_state_restore``, ONE launch, no host wait).  ``envs=None``: every env, and the handle's host words and the running
+        reset counter go back too.  ``envs``: a bool or uint8 CUDA tensor ``[B]`` -- only the envs with a non-zero entry are rewound, in every buffer; the others keep
+        every word, and the host words stay.  Refused before any launch: a snapshot of another layout (the message names the first difference), a blob that is not
+        on the env's device."""
+        blob = snap.blob
+        if not (isinstance(blob, torch.Tensor) and blob.is_cuda and blob.device == self.device and blob.dtype == torch.uint8 and blob.is_contiguous()):
+            raise TypeError(f"restore: the snapshot's blob must be a contiguous uint8 CUDA tensor on {self.device} (Snapshot.to)")
+        mask = None
+        if envs is not None:
+            if not (isinstance(envs, torch.Tensor) and envs.is_cuda and envs.device == self.device and envs.dtype in (torch.bool, torch.uint8) and tuple(envs.shape) == (self.B,)):
+                raise TypeError(f"restore: envs must be a bool or uint8 CUDA tensor [{self.B}] on {self.device}")
+            mask = (envs.view(torch.uint8) if envs.dtype == torch.bool else envs).contiguous()
+        hdr = capi.StateHeader.from_dict(snap.header)
+        self._on_stream("state_restore", lambda: self.lib.state_restore(self.h, C.byref(hdr), C.c_void_p(blob.data_ptr()), blob.numel(),
+                                                                       C.c_void_p(mask.data_ptr()) if mask is not None else None),
+                        (blob,) + ((mask,) if mask is not None else ()))
+        if envs is None:
+            self._reset_counter = int(snap.reset_counter)
 
     def launch_shape(self) -> dict:
         """What the handle launches (``sigmaenv_launch_shape``): the step kernel's tiling (``wave_G`` envs per wavefront tile, ``wave_wpb`` tiles per workgroup,

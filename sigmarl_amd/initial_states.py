@@ -45,6 +45,8 @@ class InitialStateBank:
         layout = {capi.ISB_BANK_STATE: ("f32", (cap, N, 8)), capi.ISB_BANK_PATH: ("i32", (cap, N, 4)), capi.ISB_WORDS: ("i32", (2,)),
                   capi.ISB_RING_STATE: ("f32", (B, S, N, 8)), capi.ISB_RING_PATH: ("i32", (B, S, N, 4)), capi.ISB_HELD: ("i32", (B,)), capi.ISB_HEAD: ("i32", (B,)),
                   capi.ISB_PENDING: ("u8", (B,))}
+        if hasattr(env.lib, "state_save"):  # (an older build under SIGMAENV_LIB_OLD_ABI=1 has neither the snapshot entry points nor this id)
+            layout[capi.ISB_EPISODES] = ("i32", (B,))
         for what, (kind, shape) in layout.items():
             p, nb = C.c_void_p(), C.c_size_t()
             env._chk(env.lib.isb_get(env.h, self.bank, what, C.byref(p), C.byref(nb)), "isb_get")
@@ -97,6 +99,41 @@ class InitialStateBank:
     def view(self, what: int) -> torch.Tensor:
         """Zero-copy view of one of the bank's device arrays (``capi.ISB_*``): for tests and checkpoints."""
         return self._views[what]
+
+    _STATE_KEYS = {"bank_state": capi.ISB_BANK_STATE, "bank_path": capi.ISB_BANK_PATH, "words": capi.ISB_WORDS, "ring_state": capi.ISB_RING_STATE,
+                   "ring_path": capi.ISB_RING_PATH, "held": capi.ISB_HELD, "head": capi.ISB_HEAD, "pending": capi.ISB_PENDING, "episodes": capi.ISB_EPISODES}
+
+    def state_dict(self) -> dict:
+        """Every word of the bank and of the rings (copies on the device, enqueued behind the env's stream; ``.cpu()`` them for a file) with the four settings."""
+        if capi.ISB_EPISODES not in self._views:
+            raise RuntimeError("InitialStateBank.state_dict: this build of the library does not expose the bank's episodes copy")
+        e = self.env
+        with torch.cuda.device(e.device):
+            torch.cuda.current_stream(e.device).wait_stream(e.stream)
+        d = {k: self._views[w].clone() for k, w in self._STATE_KEYS.items()}
+        d.update(capacity=self.capacity, n_steps_stored=self.n_steps_stored, probability_record=self.probability_record,
+                 probability_use_recording=self.probability_use_recording)
+        return d
+
+    def load_state_dict(self, d: dict) -> None:
+        """The inverse: refuses (before any copy) a dict of another ``capacity`` / ``n_steps_stored`` or with a tensor of another shape or dtype; the message names
+        it.  The probabilities are settings of this object and stay."""
+        if capi.ISB_EPISODES not in self._views:
+            raise RuntimeError("InitialStateBank.load_state_dict: this build of the library does not expose the bank's episodes copy")
+        for k in ("capacity", "n_steps_stored"):
+            if int(d[k]) != getattr(self, k):
+                raise ValueError(f"InitialStateBank.load_state_dict: {k} is {d[k]} in the dict, {getattr(self, k)} here")
+        for k, w in self._STATE_KEYS.items():
+            t, v = d[k], self._views[w]
+            if not isinstance(t, torch.Tensor) or t.shape != v.shape or t.dtype != v.dtype:
+                raise ValueError(f"InitialStateBank.load_state_dict: {k} must be a {v.dtype} tensor {list(v.shape)}")
+        e = self.env
+        with torch.cuda.device(e.device):
+            cur = torch.cuda.current_stream(e.device)
+            cur.wait_stream(e.stream)
+            for k, w in self._STATE_KEYS.items():
+                self._views[w].copy_(d[k].to(e.device))
+            e.stream.wait_stream(cur)
 
     @property
     def count(self) -> int:

@@ -205,6 +205,16 @@ class EpisodeReturns:
     def reset(self) -> None:
         self.carry.zero_()
 
+    def state_dict(self) -> dict:
+        """The carry (a copy): all this object holds from one rollout to the next."""
+        return {"carry": self.carry.clone()}
+
+    def load_state_dict(self, d: dict) -> None:
+        c = d["carry"]
+        if not isinstance(c, torch.Tensor) or c.shape != self.carry.shape or c.dtype != self.carry.dtype:
+            raise ValueError(f"EpisodeReturns.load_state_dict: carry must be a float32 tensor {list(self.carry.shape)}")
+        self.carry.copy_(c)
+
     def update(self, slab: torch.Tensor, T: int | None = None, env_first: int = 0, episode_reward=None):
         """The records ``slab [T, Bt, W]`` of the rollout that followed the last one this object saw (``Bt >= env.B``: the env owns the envs ``[env_first,
         env_first + env.B)`` of the buffer, as for ``gae``): returns ``(episode_reward [T,B,N], stats)`` -- ``episode_reward[t,b,i]`` the return of agent ``i``'s
@@ -592,13 +602,41 @@ class Adam:
                     mine.zero_()
         self.t = steps.pop() if steps else 0
 
+    def state_dict(self) -> dict:
+        """What a later step depends on besides the parameters themselves: both moments of every parameter (copies; ``state[k][i] = (exp_avg, exp_avg_sq)`` in the
+        optimiser's order), the step count ``t``, ``lr``, ``betas`` and ``eps``."""
+        return {"t": int(self.t), "lr": float(self.lr), "betas": (float(self.betas[0]), float(self.betas[1])), "eps": float(self.eps),
+                "state": [[(m.clone(), v.clone()) for m, v in mom] for mom in self.state]}
+
+    def load_state_dict(self, d: dict) -> None:
+        """The inverse.  Refused before any copy (``ValueError`` naming the tensor): another number of networks or parameters, a moment of another shape or dtype."""
+        st = d["state"]
+        if len(st) != len(self.state):
+            raise ValueError(f"Adam.load_state_dict: {len(st)} networks in the dict, {len(self.state)} here")
+        for k, (mine, theirs) in enumerate(zip(self.state, st)):
+            if len(mine) != len(theirs):
+                raise ValueError(f"Adam.load_state_dict: network {k} has {len(theirs)} parameters in the dict, {len(mine)} here")
+            for i, ((m, v), (m2, v2)) in enumerate(zip(mine, theirs)):
+                for a, b, name in ((m, m2, "exp_avg"), (v, v2, "exp_avg_sq")):
+                    if not isinstance(b, torch.Tensor) or a.shape != b.shape or a.dtype != b.dtype:
+                        raise ValueError(f"Adam.load_state_dict: {name} of network {k} parameter {i} must be a {a.dtype} tensor {list(a.shape)}, "
+                                         f"got {list(b.shape) if isinstance(b, torch.Tensor) else type(b).__name__}")
+        for mine, theirs in zip(self.state, st):
+            for (m, v), (m2, v2) in zip(mine, theirs):
+                m.copy_(m2)
+                v.copy_(v2)
+        self.t, self.lr, self.betas, self.eps = int(d["t"]), float(d["lr"]), (float(d["betas"][0]), float(d["betas"][1])), float(d["eps"])
+
 
 class PrioritizedBuffer:
     """The reference's prioritized replay buffer (``Parameters.is_prb``: ``TensorDictPrioritizedReplayBuffer(alpha=0.7, beta=0.6, priority_key="td_error")`` sized
     ``frames_per_batch``, ``sigmarl/mappo_cavs.py:321-332``) as a device object (``sigmaenv_prb_*``; every formula and the order of every sum:
     ``include/sigmaenv.h``, ``sigmarl_amd/csrc/sigmaenv_prb.h``): the priorities ``q[f]`` of the frames ``f = t * B + b`` of the batch ``collect`` returned and a
     sum / min hierarchy over them.  The frames themselves stay where ``collect`` put them; the buffer hands out their indices.  ``capacity``: the frames it can hold
-    (``T * B``).  Everything is allocated here; ``extend`` / ``sample`` / ``refresh`` enqueue on the env's stream and nothing waits on the host."""
+    (``T * B``).  Everything is allocated here; ``extend`` / ``sample`` / ``refresh`` enqueue on the env's stream and nothing waits on the host.
+
+    A checkpoint (``sigmarl_amd.checkpoint``) holds nothing of it and it has no ``state_dict``: ``extend`` replaces the whole content at the start of every
+    iteration, so nothing of one iteration's buffer reaches the next."""
 
     def __init__(self, env, capacity: int, alpha: float = 0.7, beta: float = 0.6, eps: float = 1e-8):
         self._h = None
@@ -932,7 +970,8 @@ def train_iteration(env, actor, critic, actor_module, critic_module, optim, retu
 
 
 def train(env, actor, critic, actor_module, critic_module, optim, params=None, *, n_iters: int | None = None, on_iteration=None, returns: EpisodeReturns | None = None,
-          buffer: PrioritizedBuffer | None = None, episode_reward_mean_list: list | None = None, initial_states=None, **iteration_kw) -> list:
+          buffer: PrioritizedBuffer | None = None, episode_reward_mean_list: list | None = None, initial_states=None, start_iter: int = 1, checkpoint=None,
+          checkpoint_every: int = 0, **iteration_kw) -> list:
     """The reference's training loop (``sigmarl/mappo_cavs.py:121-150``): ``train_iteration`` for ``i_iter = 1 .. n_iters`` (``params.n_iters`` unless given; the
     schedule always runs over ``params.n_iters``) with one ``EpisodeReturns`` carried through (a new one unless given).  After every iteration, as ``_log_and_save``
     and ``_save_intermediate_model`` (``:468-515``) do: ``mean = EpisodeReturns.mean(stats)`` -- the one host read of the iteration -- is appended to
@@ -941,14 +980,30 @@ def train(env, actor, critic, actor_module, critic_module, optim, params=None, *
     so far, as the reference's does.  Then ``on_iteration(i_iter, batch, infos, mean, improved)`` if given: the place where a caller saves models -- this loop writes
     no files.  The optimiser starts from whatever ``lr`` it holds (``params.lr`` in the reference).  Returns ``episode_reward_mean_list``.  ``iteration_kw`` may hold
     ``rollout_kw=dict(wrapper="prioritized")`` and ``priority=(...)`` (``train_iteration``): the ``is_using_prioritized_marl`` / ``"marl"`` configuration end to end.
-    ``initial_states``: one ``InitialStateBank`` for every iteration (``is_challenging_initial_state_buffer``)."""
+    ``initial_states``: one ``InitialStateBank`` for every iteration (``is_challenging_initial_state_buffer``).
+
+    Stop and go on: the loop runs ``i_iter = start_iter .. n_iters``.  With ``checkpoint`` a path and ``checkpoint_every = m > 0`` the state of the run
+    (``sigmarl_amd.checkpoint.save``: env snapshot, modules, optimiser moments, the returns' carry, the generator, the bank, ``params``' two running numbers, the means)
+    is written after every ``m``-th iteration and after the last -- AFTER ``set_lr`` and ``on_iteration``, so the file describes the moment before iteration
+    ``i_iter + 1`` -- which needs ``optim`` (and the priority optimiser) to be a ``learn.Adam``.  ``resume`` continues from such a file, bit for bit the run that was
+    never stopped.  With the defaults nothing is written and no launch is added."""
     p = params if params is not None else getattr(env, "parameters", None)
     if p is None:
         raise ValueError("train(): a Parameters")
     n = int(n_iters if n_iters is not None else p.n_iters)
+    first, every = int(start_iter), int(checkpoint_every)
+    if first < 1:
+        raise ValueError(f"train(): start_iter = {start_iter} is 1-based")
+    if every < 0 or (every > 0 and checkpoint is None):
+        raise ValueError("train(): checkpoint_every > 0 needs checkpoint=, a path")
+    if checkpoint is not None and every > 0:
+        pr = iteration_kw.get("priority")
+        for what, o in (("optim", optim),) + ((("the priority optimiser", pr[4]),) if pr is not None else ()):
+            if not isinstance(o, Adam):
+                raise TypeError(f"train(): checkpoint= needs {what} to be a learn.Adam (a torch optimiser keeps moments this loop cannot save)")
     returns = returns if returns is not None else EpisodeReturns(env)
     means = episode_reward_mean_list if episode_reward_mean_list is not None else []
-    for i_iter in range(1, n + 1):
+    for i_iter in range(first, n + 1):
         batch, infos, stats = train_iteration(env, actor, critic, actor_module, critic_module, optim, returns, p, i_iter=i_iter, buffer=buffer, initial_states=initial_states, **iteration_kw)
         mean = EpisodeReturns.mean(stats)
         means.append(mean)
@@ -960,4 +1015,45 @@ def train(env, actor, critic, actor_module, critic_module, optim, params=None, *
             p.episode_reward_mean_current = p.episode_reward_intermediate
         if on_iteration is not None:
             on_iteration(i_iter, batch, infos, mean, improved)
+        if checkpoint is not None and every > 0 and (i_iter % every == 0 or i_iter == n):
+            _save_checkpoint(checkpoint, env, actor_module, critic_module, optim, returns, p, i_iter, means, initial_states, iteration_kw)
     return means
+
+
+def _checkpoint_parts(actor, critic, actor_module, critic_module, optim, priority):
+    """The name -> object dicts ``sigmarl_amd.checkpoint`` takes, from ``train``'s arguments."""
+    modules, networks, optims = {"policy": actor_module, "critic": critic_module}, {"policy": actor, "critic": critic}, {"base": optim}
+    if priority is not None:
+        pnet, pcritic, pmodule, pcritic_module, poptim = priority
+        modules.update(priority_policy=pmodule, priority_critic=pcritic_module)
+        networks.update(priority_policy=pnet, priority_critic=pcritic)
+        optims["priority"] = poptim
+    return modules, networks, optims
+
+
+def _save_checkpoint(path, env, actor_module, critic_module, optim, returns, p, i_iter, means, initial_states, iteration_kw):
+    from . import checkpoint as ck
+
+    modules, _, optims = _checkpoint_parts(None, None, actor_module, critic_module, optim, iteration_kw.get("priority"))
+    ck.save(path, env=env, modules=modules, optims=optims, returns=returns, i_iter=i_iter, seed=int(iteration_kw.get("seed", 0)),
+            counter0=int(iteration_kw.get("counter0", 0)), params=p, means=means, generator=iteration_kw.get("generator"), initial_states=initial_states)
+
+
+def resume(path, env, actor, critic, actor_module, critic_module, optim, params=None, *, returns: EpisodeReturns | None = None, initial_states=None, **train_kw) -> list:
+    """``checkpoint.restore`` of the file at ``path`` into the given, newly built objects -- the env, the torch modules, the device networks (``load``), the optimisers
+    (moments, ``t``, ``lr``, then ``resolve``), the returns' carry, ``train_kw``'s ``generator`` and ``priority`` tuple, the bank, ``params``' two running numbers --
+    followed by ``train(start_iter=ckpt["i_iter"] + 1, episode_reward_mean_list=<the file's means>, ...)``.  ``seed`` / ``counter0`` come from the file unless
+    ``train_kw`` names them.  Every further keyword is ``train``'s (``checkpoint=`` / ``checkpoint_every=`` among them: the resumed run goes on writing).  Returns the
+    list of means of the whole run."""
+    from . import checkpoint as ck
+
+    p = params if params is not None else getattr(env, "parameters", None)
+    returns = returns if returns is not None else EpisodeReturns(env)
+    ckpt = ck.load(path)
+    modules, networks, optims = _checkpoint_parts(actor, critic, actor_module, critic_module, optim, train_kw.get("priority"))
+    ck.restore(ckpt, env=env, modules=modules, networks=networks, optims=optims, returns=returns, params=p, generator=train_kw.get("generator"),
+               initial_states=initial_states)
+    train_kw.setdefault("seed", ckpt["seed"])
+    train_kw.setdefault("counter0", ckpt["counter0"])
+    return train(env, actor, critic, actor_module, critic_module, optim, p, returns=returns, initial_states=initial_states, start_iter=int(ckpt["i_iter"]) + 1,
+                 episode_reward_mean_list=list(ckpt["means"]), **train_kw)
