@@ -452,7 +452,7 @@ int sigmaenv_actor_load_device(sigmaenv_t* h, sigmaenv_actor_t* a, const float* 
  *       grad_w / grad_b: HOST arrays of DEVICE pointers, one per layer, as sigmaenv_mlp32_load_device takes the weights; OVERWRITTEN, not accumulated.  `in` and the
  *       four row arguments, and `acts`, are those of the sigmaenv_mlp32_forward_save call; workspace: device f32, 16-byte aligned; after the call its first
  *       (n - 1) * rows * 256 floats hold g_l, l = 0 .. n - 2, as [n - 1][rows][256] (the rest: the ranges' partial sums).  The gradient with respect to the input is
- *       not computed.
+ *       not computed here (sigmaenv_mlp32_backward_dx, below, computes it).
  * Arithmetic and summation order.  fp32 throughout; every sum is an fma chain (v_mfma_f32_32x32x2_f32: one rounding per term) or a chain of fp32 additions:
  *   g_{l-1}[r, k]  the chain over the features f = 0, 1, .. of g_l[r, f] W_l[f, k] from 0, times fl(1 - a^2) formed with ONE rounding (fma(-a, a, 1)), rounded once more;
  *   grad_w[l][f, k]  the rows are cut into ranges of len = max(256, ceil(rows / 64) rounded up to a multiple of 64) rows: range i = [i len, min(rows, (i + 1) len));
@@ -497,6 +497,32 @@ int sigmaenv_mlp32_forward_save_indexed_pad(sigmaenv_t* h, sigmaenv_mlp32_t* m, 
 int sigmaenv_mlp32_backward_indexed_pad(sigmaenv_t* h, sigmaenv_mlp32_t* m, const float* in, int32_t rows_per_block, int64_t row_stride, int32_t n_blocks,
                                         int64_t block_stride, const int32_t* index, int32_t n_index, int32_t seg_src, int32_t seg_dst, const float* acts,
                                         const float* dout, float* workspace, float* const* grad_w, float* const* grad_b);
+
+/* The gradient with respect to the INPUT rows: dx [rows, dims[0]] := g_0 W_0, dx[r, k] the chain over the features f = 0, 1, .., 255 of g_0[r, f] W_0[f, k] from 0
+ * (v_mfma_f32_32x32x2_f32: one rounding per term; no factor), g_0 the delta of the first layer as above.  It needs layer 0's weights in the transposed exact form,
+ * which a handle holds only when it was asked to:
+ *   sigmaenv_mlp32_create_input_grad   sigmaenv_mlp32_create (same arguments, refusals and results) whose handle ALSO holds that form -- dims[0] padded to 32 times 256
+ *       floats -- and keeps it current wherever its weights are rewritten (sigmaenv_mlp32_load_device, sigmaenv_optim_step's repack: the same per-slot statement).
+ *       Every other entry point treats the two kinds of handle alike; a handle from sigmaenv_mlp32_create allocates, packs and runs what it always did.
+ *   sigmaenv_mlp32_input_grad_workspace   *n_floats := (n - 1) * rows * 256, the floats of sigmaenv_mlp32_input_grad's workspace (0 for rows = 0).
+ *   sigmaenv_mlp32_input_grad   from acts [n - 1][rows][256] (sigmaenv_mlp32_forward_save's) and dout [rows, dims[n]]: ONE launch -- the delta kernel's instantiation that
+ *       ends with the contraction above --; no input row is read and no dW kernel runs.  workspace: device f32, 16-byte aligned; afterwards it holds g_l,
+ *       l = 0 .. n - 2, as [n - 1][rows][256].  dx: device f32, dense, 4-byte alignment suffices (rows of an odd width are stored column by column, 16-byte
+ *       stores only when dims[0] is a multiple of 4 and dx is 16-byte aligned); OVERWRITTEN; columns >= dims[0] and rows >= rows are never written.
+ *   sigmaenv_mlp32_backward_dx   the arguments of sigmaenv_mlp32_backward_indexed_pad, then dx.  index = NULL with n_index = 0 means the record's own blocks
+ *       (sigmaenv_mlp32_backward -- NOT the empty minibatch of the _indexed entry points), seg_src = seg_dst = 0 means no padding; padded rows need an index, as
+ *       there.  That one delta launch, then the dW and sum kernels of the entry points above: grad_w / grad_b are bit for bit theirs on the same arguments, dx is
+ *       bit for bit sigmaenv_mlp32_input_grad's.  The workspace is sigmaenv_mlp32_backward_workspace's.  With padding dx still has dims[0] columns (the network's
+ *       input row, padding columns included).
+ * No atomics; a function of acts, dout and the weights alone: the same bits every run, whatever the layout the input rows were read from.  rows = 0: nothing is
+ * launched for dx, SIGMAENV_OK (backward_dx still writes the gradients as zeros).  A handle without the form: SIGMAENV_EINVAL with sigmaenv_last_error set, as for a
+ * null or misaligned pointer, before any launch. */
+int sigmaenv_mlp32_create_input_grad(int32_t n_layers, const int32_t* dims, const float* const* weights, const float* const* biases, sigmaenv_mlp32_t** out);
+int sigmaenv_mlp32_input_grad_workspace(const sigmaenv_mlp32_t* m, int64_t rows, uint64_t* n_floats);
+int sigmaenv_mlp32_input_grad(sigmaenv_t* h, sigmaenv_mlp32_t* m, const float* acts, const float* dout, int32_t rows, float* workspace, float* dx);
+int sigmaenv_mlp32_backward_dx(sigmaenv_t* h, sigmaenv_mlp32_t* m, const float* in, int32_t rows_per_block, int64_t row_stride, int32_t n_blocks, int64_t block_stride,
+                               const int32_t* index, int32_t n_index, int32_t seg_src, int32_t seg_dst, const float* acts, const float* dout, float* workspace,
+                               float* const* grad_w, float* const* grad_b, float* dx);
 
 /* n_steps x (sigmaenv_actor_forward; sigmaenv_step_autoreset) enqueued back to back (SyncDataCollectorCustom.rollout,
  * sigmarl/helper_training.py:687-788, without its per-step Python): actions_buf device f32 [B,N,2] scratch; optional records:

@@ -16,7 +16,9 @@ Weights come from any ``torch.nn.Sequential`` of four ``Linear`` layers (the par
 ``Mlp32.load`` / ``Actor.load`` put a learner's updated CUDA parameters into the existing device networks (``sigmaenv_mlp32_load_device`` /
 ``sigmaenv_actor_load_device``: packed by a kernel, no weight visits the host), so that collect -> torch update -> load -> collect stays on the device.
 ``Mlp32.apply`` / ``Actor.apply`` / ``Critic.apply`` differentiate the fp32 networks on the device (``sigmaenv_mlp32_forward_save`` / ``sigmaenv_mlp32_backward``); with
-``index=`` on a minibatch of frames picked out of the records (``*_indexed``), which ``sigmarl_amd.learn`` (``ppo_head``, ``update``) trains from.
+``index=`` on a minibatch of frames picked out of the records (``*_indexed``), which ``sigmarl_amd.learn`` (``ppo_head``, ``update``) trains from.  Networks made with
+``input_grad=True`` also give the gradient with respect to the input rows: ``apply`` on a dense ``x`` that requires one, ``Mlp32.input_grad`` without autograd
+(``sigmaenv_mlp32_backward_dx`` / ``sigmaenv_mlp32_input_grad``); ``sigmarl_amd.saliency`` is its first consumer.
 
 The distribution heads (actor, priority actor) and ``random_ranks``: the draw of every row -- the counter-based generator keyed by (seed, the low 32 bits of
 counter, env_index_base + env, agent), Box-Muller with z0 the cosine and z1 the sine branch -- the action and the log-probability are pinned against fp64 on every
@@ -94,6 +96,33 @@ class _Mlp32Function(torch.autograd.Function):
         return (None, None, None, None, *[t for q in zip(gw, gb) for t in q])
 
 
+class _Mlp32InputFunction(torch.autograd.Function):
+    """``Mlp32.apply`` on a dense ``x`` that requires a gradient (a network made with ``input_grad=True``): ``x`` is a tensor input next to the parameters.
+    Backwards, the parameters' gradients are computed only if one of them needs its own and ``dx`` only if ``x`` does (``sigmaenv_mlp32_backward_dx`` /
+    ``sigmaenv_mlp32_input_grad`` / ``sigmaenv_mlp32_backward``); no double backward."""
+
+    @staticmethod
+    def forward(ctx, net, env, shape, x, *params):
+        spec = (x.detach(), 0, x.numel() // net.in_dim, net.in_dim, 1, 0, None)
+        y, acts = net._forward_save(env, spec)
+        ctx.net, ctx.env, ctx.spec, ctx.acts = net, env, spec, acts
+        ctx.version = net._version
+        return y.view(shape)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dy):
+        net = ctx.net
+        if net._version != ctx.version:
+            raise RuntimeError("Mlp32.apply: load() replaced the network's weights between this forward and its backward")
+        want_dx, want_params = ctx.needs_input_grad[3], any(ctx.needs_input_grad[4:])
+        gw, gb, dx = net._backward_dx(ctx.env, ctx.spec, ctx.acts, dy, want_params, want_dx)
+        x = ctx.spec[0]
+        ctx.acts = ctx.spec = None
+        grads = [t for q in zip(gw, gb) for t in q] if want_params else [None] * (len(ctx.needs_input_grad) - 4)
+        return (None, None, None, dx.view(x.shape) if want_dx else None, *grads)
+
+
 def _env_list(env):
     envs = list(env) if isinstance(env, (list, tuple)) else [env]
     if not envs:
@@ -116,9 +145,10 @@ class Mlp32:
     to exact when a weight is outside +-255 or the input is wider than 592) or ``"exact"`` (``v_mfma_f32_32x32x2_f32`` fma chains).  Input widths 1 to 4096.  Both are
     held to torch.nn in fp64 within the precision class of torch.nn in fp32 (tests/network_check.py)."""
 
-    def __init__(self, mlp: torch.nn.Module, lib: capi.Library | None = None, mode: str = "split"):
+    def __init__(self, mlp: torch.nn.Module, lib: capi.Library | None = None, mode: str = "split", input_grad: bool = False):
         if mode not in ("split", "exact"):
             raise ValueError("mode must be 'split' or 'exact'")
+        self._input_grad = bool(input_grad)  # the handles also hold layer 0's transposed form (sigmaenv_mlp32_create_input_grad): ``apply`` differentiates through ``x``
         self.mode = mode          # the mode in force (after a ``load``: what the weights allow)
         self._requested = mode    # the mode asked for
         self._handles = {}
@@ -155,9 +185,10 @@ class Mlp32:
             PA = C.c_void_p * len(ws)
             wp, bp = PA(*[w.ctypes.data for w in ws]), PA(*[b.ctypes.data for b in bs])
             h = C.c_void_p()
-            rc = lib.mlp32_create(len(ws), dims.ctypes.data_as(C.c_void_p), wp, bp, C.byref(h))
+            create = lib.mlp32_create_input_grad if self._input_grad else lib.mlp32_create
+            rc = create(len(ws), dims.ctypes.data_as(C.c_void_p), wp, bp, C.byref(h))
             if rc != 0:
-                raise RuntimeError(f"sigmaenv_mlp32_create failed with code {rc}")
+                raise RuntimeError(f"sigmaenv_mlp32_create{'_input_grad' if self._input_grad else ''} failed with code {rc}")
             if self._requested == "exact":
                 lib.mlp32_set_mode(h, capi.MLP32_EXACT)
             ent = self._handles[lib.path] = (lib, h)
@@ -452,6 +483,59 @@ class Mlp32:
             t.record_stream(env.stream)
         return gw, gb
 
+    def _backward_dx(self, env, spec, acts, dout, want_params=True, want_dx=True):
+        """(grad_w, grad_b, dx [n, in_dim]) on the env's stream, ordered as ``_forward_save``; what is not wanted is ``None`` and is not computed:
+        ``sigmaenv_mlp32_backward_dx`` for both, ``sigmaenv_mlp32_input_grad`` for ``dx`` alone (one launch, no input row read), ``_backward`` for the parameters alone."""
+        if not want_dx:
+            return (*self._backward(env, spec, acts, dout), None) if want_params else (None, None, None)
+        if not self._input_grad:
+            raise RuntimeError("the gradient with respect to the input needs a network made with input_grad=True")
+        base, offset, rpb, rs, nb, bs, index, *pad = spec
+        n, dev = rpb * (nb if index is None else index.numel()), env.device
+        dims = [int(d) for d in self._keep[0]]
+        cur = torch.cuda.current_stream(dev)
+        dout = dout.reshape(n, self.out_dim).to(torch.float32).contiguous()
+        nf = C.c_uint64()
+        h = self.handle(env.lib)
+        rc = (env.lib.mlp32_backward_workspace if want_params else env.lib.mlp32_input_grad_workspace)(h, n, C.byref(nf))
+        if rc != 0:
+            raise RuntimeError(f"sigmaenv_mlp32_{'backward' if want_params else 'input_grad'}_workspace failed with code {rc}")
+        ws = torch.empty((max(int(nf.value), 4),), dtype=torch.float32, device=dev)
+        dx = torch.empty((n, self.in_dim), dtype=torch.float32, device=dev)
+        gw = [torch.empty((dims[l + 1], dims[l]), dtype=torch.float32, device=dev) for l in range(len(dims) - 1)] if want_params else None
+        gb = [torch.empty((dims[l + 1],), dtype=torch.float32, device=dev) for l in range(len(dims) - 1)] if want_params else None
+        p = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
+        with torch.cuda.device(dev):
+            env.stream.wait_stream(cur)
+            if want_params:
+                PA = C.c_void_p * len(gw)
+                src, (seg_src, seg_dst) = C.c_void_p(base.data_ptr() + 4 * offset), (pad[0] if pad else (0, 0))
+                self._chk_grad(env, env.lib.mlp32_backward_dx(env.h, h, src, rpb, rs, nb, bs, None if index is None else p(index), 0 if index is None else index.numel(),
+                                                              seg_src, seg_dst, p(acts), p(dout), p(ws), PA(*[t.data_ptr() for t in gw]), PA(*[t.data_ptr() for t in gb]), p(dx)),
+                               "mlp32_backward_dx")
+            else:
+                self._chk_grad(env, env.lib.mlp32_input_grad(env.h, h, p(acts), p(dout), n, p(ws), p(dx)), "mlp32_input_grad")
+            cur.wait_stream(env.stream)
+        for t in [base, acts, dout, ws, dx] + (gw + gb if want_params else []) + ([] if index is None else [index]):
+            t.record_stream(env.stream)
+        return gw, gb, dx
+
+    def input_grad(self, env: SigmaEnv, x: torch.Tensor | None = None, *, rows=None, index: torch.Tensor | None = None, check_index: bool = True, pad=None, dout: torch.Tensor):
+        """``(y, dx)`` without autograd (a network made with ``input_grad=True``): the network's outputs on the rows -- ``x`` dense, or ``rows`` / ``index`` / ``pad``
+        read where they lie, as ``apply`` takes them -- and the gradient of ``sum(y * dout)`` with respect to them, ``dx [n, in_dim]`` dense in the order of the
+        rows (``pad``: the network's ``in_dim`` columns, padding included).  ``dout``: float32 CUDA, ``n * out_dim`` elements.  One saving forward and one launch
+        (``sigmaenv_mlp32_input_grad``); the same bits for the same rows whatever their layout; the parameters are not looked at.  Streams: as ``apply``."""
+        if not self._input_grad:
+            raise RuntimeError("input_grad: the network was not made with input_grad=True")
+        if isinstance(x, torch.Tensor):
+            x = x.detach()
+        spec, shape = self._rows_spec(x, rows, env, index, check_index, pad)
+        n = int(np.prod(shape[:-1]))
+        if not (isinstance(dout, torch.Tensor) and dout.is_cuda and dout.dtype == torch.float32 and dout.device == env.device and dout.numel() == n * self.out_dim):
+            raise TypeError(f"input_grad: dout must be a float32 CUDA tensor of {n * self.out_dim} elements on {env.device}")
+        y, acts = self._forward_save(env, spec)
+        return y.view(shape), self._backward_dx(env, spec, acts, dout.detach(), want_params=False)[2]
+
     def apply(self, env: SigmaEnv, x: torch.Tensor | None = None, *, rows=None, index: torch.Tensor | None = None, check_index: bool = True, pad=None) -> torch.Tensor:
         """The network with a ``grad_fn``: ``y = apply(env, x)`` for dense ``x [..., in_dim]`` (``y [..., out_dim]``) or ``apply(env, rows=(base, offset,
         rows_per_block, row_stride, n_blocks, block_stride))`` for rows read where they lie, as ``forward_rows`` addresses them (``y [n_blocks, rows_per_block,
@@ -462,21 +546,26 @@ class Mlp32:
         read such a block as zeros).  ``pad = (src, dst)`` (with ``index``; ``forward_rows``'s): the rows in memory are segments of ``src`` floats read as ``dst``
         columns, the rest zero -- values and gradients bit for bit those of the rows gathered and padded dense.  A ``torch.autograd.Function`` whose inputs are the parameters of the module the
         network was built or last ``load``ed from (float32 CUDA tensors on the env's device): ``loss.backward()`` fills their ``.grad``, so ``clip_grad_norm_`` and
-        ``torch.optim.Adam`` work unchanged.  The forward is the EXACT fp32 chain whatever mode the network runs in (``sigmaenv_mlp32_forward_save``); the gradient
-        with respect to the input is not built (``x.requires_grad``: ``NotImplementedError``).
+        ``torch.optim.Adam`` work unchanged.  The forward is the EXACT fp32 chain whatever mode the network runs in (``sigmaenv_mlp32_forward_save``).  The gradient
+        with respect to the input: a network made with ``input_grad=True`` takes a dense ``x`` with ``requires_grad`` and its ``backward`` fills ``x.grad``
+        (``sigmaenv_mlp32_backward_dx``; once differentiable); without the flag ``x.requires_grad`` raises ``NotImplementedError``, and so does ``rows=(base, ...)``
+        with ``base.requires_grad`` in both cases (a gradient scattered into a record is not built).
 
         Stale weights: the packed weights on the device are those of construction / the last ``load``.  If a parameter has been modified in place since (the
         optimiser stepped and ``load`` was not called) ``apply`` raises ``RuntimeError``: the forward would use the old numbers and credit the gradient to the new.
 
         Streams: the kernels run on the env's stream after everything torch's current stream holds, and torch's current stream then waits for them -- forwards
         and backwards alike (``load``'s discipline)."""
-        spec, shape = self._rows_spec(x, rows, env, index, check_index, pad)
+        through_x = self._input_grad and isinstance(x, torch.Tensor) and x.requires_grad
+        spec, shape = self._rows_spec(x.detach() if through_x else x, rows, env, index, check_index, pad)
         for t in self._params:
             if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.device == env.device):
                 raise TypeError(f"apply: the network's parameters must be float32 CUDA tensors on {env.device}: load(env, module) with the module on the device first")
         if any(t._version != v for t, v in zip(self._params, self._param_versions)):
             raise RuntimeError("apply: a parameter changed since the network was built or last loaded (an optimiser step?): call load(env, module) first -- the device "
                                "holds the old weights")
+        if through_x:
+            return _Mlp32InputFunction.apply(self, env, shape, x, *self._params)
         return _Mlp32Function.apply(self, env, spec, shape, *self._params)
 
 
@@ -574,8 +663,8 @@ class PriorityNet(Mlp32):
     without placeholder columns), a 1-D TanhNormal on [-1, 1] for the scores and ``rank_agents`` (agents by descending score; ties to the lower index).
     ``forward`` is the network alone (``Mlp32``); ``scores`` runs all three (``sigmaenv_priority_forward``)."""
 
-    def __init__(self, mlp: torch.nn.Module, lib: capi.Library | None = None, mode: str = "split"):
-        super().__init__(mlp, lib, mode)
+    def __init__(self, mlp: torch.nn.Module, lib: capi.Library | None = None, mode: str = "split", input_grad: bool = False):
+        super().__init__(mlp, lib, mode, input_grad)
         if self.out_dim != 2:
             raise ValueError("a priority network has 2 outputs (loc, scale)")
 
@@ -610,12 +699,12 @@ def random_ranks(env: SigmaEnv, seed: int = 0, counter: int = 0) -> torch.Tensor
 
 
 class Actor:
-    def __init__(self, mlp: torch.nn.Module, low, high, lib: capi.Library | None = None, precision: str = "fp32", mode: str = "split"):
+    def __init__(self, mlp: torch.nn.Module, low, high, lib: capi.Library | None = None, precision: str = "fp32", mode: str = "split", input_grad: bool = False):
         if precision not in ("fp32", "bf16"):
             raise ValueError("precision must be 'fp32' (the reference's arithmetic) or 'bf16' (fast inference variant)")
         self.precision = precision
         self.lib = lib or capi.load_library()
-        self._mlp32 = Mlp32(mlp, self.lib, mode=mode)  # the exact network (also kept by the bf16 variant: a caller may ask for either per call)
+        self._mlp32 = Mlp32(mlp, self.lib, mode=mode, input_grad=input_grad)  # the exact network (also kept by the bf16 variant: a caller may ask for either per call)
         import weakref
 
         self._scratch_by_env = weakref.WeakKeyDictionary()  # SigmaEnv -> {kind: tensor}

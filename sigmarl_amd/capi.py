@@ -384,7 +384,12 @@ _PRODUCT_ONLY = {
                                                  C.c_void_p, C.c_void_p]),
     "mlp32_backward_indexed_pad": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_int64, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
                                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "ppo_head": (C.c_int, [C.c_void_p, C.POINTER(PpoHeadArgs)]),
+    "mlp32_create_input_grad": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]),
+    "mlp32_input_grad_workspace": (C.c_int, [C.c_void_p, C.c_int64, C.POINTER(C.c_uint64)]),
+    "mlp32_input_grad": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
+    "mlp32_backward_dx": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_int64, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
+                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "ppo_head":(C.c_int, [C.c_void_p, C.POINTER(PpoHeadArgs)]),
     "ppo_head_1d": (C.c_int, [C.c_void_p, C.POINTER(PpoHead1dArgs)]),
     "optim_workspace": (C.c_int, [C.c_void_p, C.POINTER(OptimArgs), C.POINTER(C.c_uint64)]),
     "optim_step": (C.c_int, [C.c_void_p, C.POINTER(OptimArgs)]),

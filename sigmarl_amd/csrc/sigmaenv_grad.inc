@@ -6,7 +6,9 @@
 //     g_{l-1} = (g_l W_l) (.) (1 - a_l^2)       l = n - 1 .. 1        (sigmaenv_mlp32_delta_kernel)
 //     dW_l    = g_l^T a_l,   db_l = sum_rows g_l                       (sigmaenv_mlp32_dw_kernel per layer, then sigmaenv_mlp32_dw_sum_kernel)
 // All products are fp32 fma chains on v_mfma_f32_32x32x2_f32, as the forward's.  (A split-fp16 backward needs a scaling rule for g, whose range is not the
-// forward's: out of scope, DESIGN.md section 7.)  The gradient with respect to the input is not computed.
+// forward's: out of scope, DESIGN.md section 7.)
+//     dX      = g_0 W_0                                                 (the DX instantiation of the delta kernel: sigmaenv_mlp32_input_grad / sigmaenv_mlp32_backward_dx)
+// the gradient with respect to the input rows, for a handle that holds layer 0's transposed form (sigmaenv_mlp32_create_input_grad).
 //
 // Mapping.
 //  * delta: one workgroup walks a 64-row tile BACKWARDS through all layers in LDS, as the forward walks it forwards: g_l lies in the forward's activation layout
@@ -14,6 +16,11 @@
 //    contracts over the features with one 16-byte load per lane and k block), each wavefront owns two 32-wide tiles of the 256 outputs x both row tiles.  The chain
 //    of an element runs over the features f = 0, 1, .. in order.  Epilogue: times fma(-a, a, 1) -- ONE rounding of 1 - a^2, so the factor keeps its relative
 //    precision where |a| -> 1 -- one more for the product; rows past R are zeros.
+//  * dX (DX): after the l = 1 epilogue g_0 is parked in LDS as every g_l above it is, and contracted with layer 0's transposed exact form [Kp / 32][32][2][32][4],
+//    Kp = in_dim padded to 32: the same loop -- one 16-byte weight load per lane and k block, two blocks ahead --, a wavefront owning two 32-wide tiles of the input
+//    columns x both row tiles, one pass per 256 columns; tiles at or beyond Kp are skipped (wavefront-uniform; LDS is only read here: no barrier in the passes).  An
+//    element is ONE chain over f = 0 .. 255 from zero; no factor.  dX is [rows, in_dim] dense: a lane holds four consecutive columns of a row, stored with one 16-byte
+//    store when in_dim is a multiple of 4 and dX 16-byte aligned (launch-uniform), else column by column; columns >= in_dim and rows >= R are never stored.
 //  * dW: the contraction runs over the rows, and both operands are stored with the row as the slow index: lane (m, h) of a wavefront loads g[row 2 u + h][f0 + m]
 //    and a[row 2 u + h][k0 + m] with 4-byte loads that are coalesced over m -- the operand layout of the matrix instruction as it is, no LDS.  A workgroup owns a
 //    128 x 128 block of dW_l (wavefront: 2 x 2 tiles of 32 x 32, 64 accumulators) and one RANGE of rows; tiles beyond F or K are skipped (wavefront-uniform).
@@ -38,11 +45,15 @@ static inline long long range_len(long long rows) {
 static inline int n_ranges(long long rows) { return rows > 0 ? (int)((rows + range_len(rows) - 1) / range_len(rows)) : 0; }
 
 struct DeltaNet {
-  const float* wt[MLP32_MAX_LAYERS];  // layer l >= 1: the transposed exact form [256 / 32][FQ_l][2][32][4]
+  const float* wt[MLP32_MAX_LAYERS];  // layer l >= 1: the transposed exact form [256 / 32][FQ_l][2][32][4]; DX: layer 0's [Kp / 32][32][2][32][4]
   int n_layers, F_last, FQ_last;      // the output layer's width and its blocks of 8
 };
 
-__global__ void __launch_bounds__(256, 2) sigmaenv_mlp32_delta_kernel(DeltaNet g, const float* __restrict__ dout, const float* __restrict__ acts, float* __restrict__ delta, int R) {
+// DX: the instantiation that also writes dx [R][K] = g_0 W_0 (K = in_dim; dx16: K % 4 == 0 and dx 16-byte aligned, decided on the host); the other one ignores the
+// last three arguments
+template <bool DX>
+__global__ void __launch_bounds__(256, 2) sigmaenv_mlp32_delta_kernel(DeltaNet g, const float* __restrict__ dout, const float* __restrict__ acts, float* __restrict__ delta, int R,
+                                                                      float* __restrict__ dx, int K, int dx16) {
   sigma_poison_lds();
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
   float* x = reinterpret_cast<float*>(smem_raw);  // [256 / 8][2][64][4]: g_l of the tile (mlp32_act_idx)
@@ -98,7 +109,7 @@ __global__ void __launch_bounds__(256, 2) sigmaenv_mlp32_delta_kernel(DeltaNet g
           }
           acc[ft][rt][4 * q + 0] = d.x; acc[ft][rt][4 * q + 1] = d.y; acc[ft][rt][4 * q + 2] = d.z; acc[ft][rt][4 * q + 3] = d.w;
         }
-    if (l > 1) {
+    if (l > 1 || DX) {  // (DX: g_0 is parked too)
       __syncthreads();  // every wavefront is done reading g_l
 #pragma unroll
       for (int ft = 0; ft < 2; ++ft)
@@ -115,6 +126,53 @@ __global__ void __launch_bounds__(256, 2) sigmaenv_mlp32_delta_kernel(DeltaNet g
     }
   }
 #undef GRAD_SEL
+  if constexpr (DX) {
+    // dX = g_0 W_0: column tiles 2 wave, 2 wave + 1 of each pass of 8; LDS is only read from here on
+    const int KT = (K + 31) / 32;
+    const float4* xb = x4 + h * MLP32_ROWS + m;
+    for (int t0 = 2 * wave; t0 < KT; t0 += 8) {
+      const bool on1 = t0 + 1 < KT;  // the wavefront's second tile exists (else its fragments are the first tile's again: never beyond the form; not stored)
+      const int KQ = MLP32_H / 8;
+      const size_t o1 = on1 ? (size_t)KQ * 64 : 0;
+      const float4* wa = reinterpret_cast<const float4*>(g.wt[0]) + (size_t)t0 * KQ * 64 + lane;
+      f32x16_t acc[2][2];
+#pragma unroll
+      for (int ft = 0; ft < 2; ++ft)
+#pragma unroll
+        for (int rt = 0; rt < 2; ++rt)
+#pragma unroll
+          for (int j = 0; j < 16; ++j) acc[ft][rt][j] = 0.0f;
+      float4 a0 = wa[0], a1 = wa[o1], n0 = wa[64], n1 = wa[o1 + 64];
+      for (int kq = 0; kq < KQ; ++kq) {
+        const int kn = kq + 2 < KQ ? kq + 2 : KQ - 1;  // weights two blocks ahead
+        const float4 p0 = wa[(size_t)kn * 64], p1 = wa[o1 + (size_t)kn * 64];
+        const float4 b0 = xb[(size_t)kq * (MLP32_ROWS * 2)], b1 = xb[(size_t)kq * (MLP32_ROWS * 2) + 32];
+        mlp32_mfma4(acc[0][0], a0, b0); mlp32_mfma4(acc[0][1], a0, b1);
+        mlp32_mfma4(acc[1][0], a1, b0); mlp32_mfma4(acc[1][1], a1, b1);
+        a0 = n0; a1 = n1; n0 = p0; n1 = p1;
+      }
+      // columns (t0 + ft) 32 + 8 q + 4 h + {0, 1, 2, 3} of row rt 32 + m
+#pragma unroll
+      for (int ft = 0; ft < 2; ++ft)
+#pragma unroll
+        for (int rt = 0; rt < 2; ++rt)
+#pragma unroll
+          for (int q = 0; q < 4; ++q) {
+            const long long row = row0 + rt * 32 + m;
+            const int k = (t0 + ft) * 32 + 8 * q + 4 * h;
+            if (row >= R || k >= K) continue;  // (a tile at or beyond Kp lies beyond K)
+            float* d = dx + (size_t)row * K + k;
+            if (dx16) {
+              *reinterpret_cast<float4*>(d) = make_float4(acc[ft][rt][4 * q + 0], acc[ft][rt][4 * q + 1], acc[ft][rt][4 * q + 2], acc[ft][rt][4 * q + 3]);
+            } else {
+              d[0] = acc[ft][rt][4 * q + 0];
+              if (k + 1 < K) d[1] = acc[ft][rt][4 * q + 1];
+              if (k + 2 < K) d[2] = acc[ft][rt][4 * q + 2];
+              if (k + 3 < K) d[3] = acc[ft][rt][4 * q + 3];
+            }
+          }
+    }
+  }
 }
 
 // one layer's dW / db partial sums
@@ -233,7 +291,7 @@ static inline size_t partial_floats(const sigmaenv_mlp32* m) {  // one range's p
 }  // namespace grad
 
 static int mlp32_grad_load(sigmaenv_t* h, sigmaenv_mlp32* m, const float* const* weights_dev) {
-  for (int l = 1; l < m->w.n_layers; ++l) {
+  for (int l = m->wt[0] ? 0 : 1; l < m->w.n_layers; ++l) {  // (layer 0's form: a handle made by sigmaenv_mlp32_create_input_grad)
     const int K = m->dims[l], F = m->dims[l + 1], n = load_exact_t_slots(F, K);
     hipLaunchKernelGGL(grad::sigmaenv_load_mlp32_t_kernel, dim3(load::grid_for(n)), dim3(256), 0, h->stream, weights_dev[l], m->wt[l], F, K, n);
     HIPCHK(h, hipGetLastError());
@@ -275,9 +333,35 @@ extern "C" int sigmaenv_mlp32_backward_workspace(const sigmaenv_mlp32* m, int64_
   return SIGMAENV_OK;
 }
 
+// the delta launch: g_l, l = n - 2 .. 0, into delta [n - 1][R][256]; dx (not null: the DX instantiation, the handle holds layer 0's transposed form) [R][in_dim] as well
+static int mlp32_delta_launch(sigmaenv_t* h, const sigmaenv_mlp32* m, const float* acts, const float* dout, float* delta, int R, float* dx) {
+  const int n = m->w.n_layers;
+  grad::DeltaNet g{};
+  for (int l = dx ? 0 : 1; l < n; ++l) g.wt[l] = m->wt[l];
+  g.n_layers = n; g.F_last = m->out_dim; g.FQ_last = (m->out_dim + 7) / 8;
+  const dim3 grid((unsigned)(((int64_t)R + MLP32_ROWS - 1) / MLP32_ROWS));
+  const size_t smem = (size_t)MLP32_H * MLP32_ROWS * sizeof(float);
+  if (dx) {
+    const int dx16 = (m->in_dim & 3) == 0 && ((uintptr_t)dx & 15) == 0;
+    hipLaunchKernelGGL(grad::sigmaenv_mlp32_delta_kernel<true>, grid, dim3(256), smem, h->stream, g, dout, acts, delta, R, dx, m->in_dim, dx16);
+  } else {
+    hipLaunchKernelGGL(grad::sigmaenv_mlp32_delta_kernel<false>, grid, dim3(256), smem, h->stream, g, dout, acts, delta, R, (float*)nullptr, 0, 0);
+  }
+  HIPCHK(h, hipGetLastError());
+  return SIGMAENV_OK;
+}
+
+// the refusals of both entry points that write dx, made before any launch
+static int mlp32_dx_check(sigmaenv_t* h, const sigmaenv_mlp32* m, const std::string& what, int64_t rows, const float* dx) {
+  if (!m->wt[0]) { h->err = what + ": the handle does not hold layer 0's transposed form: create it with sigmaenv_mlp32_create_input_grad"; return SIGMAENV_EINVAL; }
+  if (rows > 0 && (!dx || ((uintptr_t)dx & 3))) { h->err = what + ": a null dx or one that is not 4-byte aligned"; return SIGMAENV_EINVAL; }
+  return SIGMAENV_OK;
+}
+
+// dx: nullptr for the entry points without it; want_dx: sigmaenv_mlp32_backward_dx
 static int mlp32_backward_impl(sigmaenv_t* h, sigmaenv_mlp32* m, const char* what_c, const float* in, int32_t rows_per_block, int64_t row_stride, int32_t n_blocks,
                                int64_t block_stride, const int32_t* index, int32_t n_index, const float* acts, const float* dout, float* workspace, float* const* grad_w,
-                               float* const* grad_b, const Mlp32Pad* pad = nullptr) {
+                               float* const* grad_b, const Mlp32Pad* pad = nullptr, bool want_dx = false, float* dx = nullptr) {
   if (!h) return SIGMAENV_EINVAL;
   const std::string what(what_c);
   if (!m) { h->err = what + ": null network handle"; return SIGMAENV_EINVAL; }
@@ -296,18 +380,12 @@ static int mlp32_backward_impl(sigmaenv_t* h, sigmaenv_mlp32* m, const char* wha
     h->err = what + ": null acts / dout / workspace, or acts / workspace not 16-byte aligned";
     return SIGMAENV_EINVAL;
   }
+  if (want_dx) { if (const int rc = mlp32_dx_check(h, m, what, rows, dx)) return rc; }
   HIPCHK(h, hipSetDevice(h->device));
   const int R = (int)rows, ranges = grad::n_ranges(rows);
   float* delta = workspace;                                            // [n - 1][R][256]
   float* pw = workspace ? workspace + (size_t)(n - 1) * (size_t)R * MLP32_H : nullptr;  // [ranges][F K] then [ranges][F] of the layer in work
-  if (R > 0) {
-    grad::DeltaNet g{};
-    for (int l = 1; l < n; ++l) g.wt[l] = m->wt[l];
-    g.n_layers = n; g.F_last = m->out_dim; g.FQ_last = (m->out_dim + 7) / 8;
-    hipLaunchKernelGGL(grad::sigmaenv_mlp32_delta_kernel, dim3((unsigned)((rows + MLP32_ROWS - 1) / MLP32_ROWS)), dim3(256), (size_t)MLP32_H * MLP32_ROWS * sizeof(float), h->stream, g,
-                       dout, acts, delta, R);
-    HIPCHK(h, hipGetLastError());
-  }
+  if (R > 0) { if (const int rc = mlp32_delta_launch(h, m, acts, dout, delta, R, want_dx ? dx : nullptr)) return rc; }
   for (int l = n - 1; l >= 0; --l) {
     const int K = m->dims[l], F = m->dims[l + 1];
     float* pb = pw ? pw + (size_t)ranges * F * K : nullptr;
@@ -349,4 +427,33 @@ extern "C" int sigmaenv_mlp32_backward_indexed_pad(sigmaenv_t* h, sigmaenv_mlp32
   if (!index && n_index == 0) return mlp32_backward_impl(h, m, "mlp32_backward_indexed_pad", in, rows_per_block, row_stride, 0, block_stride, nullptr, 0, acts, dout, workspace, grad_w, grad_b);
   const Mlp32Pad pd{seg_src, seg_dst};
   return mlp32_backward_impl(h, m, "mlp32_backward_indexed_pad", in, rows_per_block, row_stride, n_blocks, block_stride, index, n_index, acts, dout, workspace, grad_w, grad_b, &pd);
+}
+
+// ---- the gradient with respect to the input rows (contracts: include/sigmaenv.h) ----
+extern "C" int sigmaenv_mlp32_input_grad_workspace(const sigmaenv_mlp32* m, int64_t rows, uint64_t* n_floats) {
+  if (!m || !n_floats || rows < 0 || rows > INT32_MAX) return SIGMAENV_EINVAL;
+  *n_floats = (uint64_t)(m->w.n_layers - 1) * (uint64_t)rows * MLP32_H;  // g_l, l = 0 .. n - 2
+  return SIGMAENV_OK;
+}
+extern "C" int sigmaenv_mlp32_input_grad(sigmaenv_t* h, sigmaenv_mlp32* m, const float* acts, const float* dout, int32_t rows, float* workspace, float* dx) {
+  if (!h) return SIGMAENV_EINVAL;
+  const std::string what("mlp32_input_grad");
+  if (!m) { h->err = what + ": null network handle"; return SIGMAENV_EINVAL; }
+  if (rows < 0) { h->err = what + ": a negative row count"; return SIGMAENV_EINVAL; }
+  if (rows > 0 && (!acts || !dout || !workspace || ((uintptr_t)acts & 15) || ((uintptr_t)dout & 3) || ((uintptr_t)workspace & 15))) {
+    h->err = what + ": null acts / dout / workspace, or acts / workspace not 16-byte aligned";
+    return SIGMAENV_EINVAL;
+  }
+  if (const int rc = mlp32_dx_check(h, m, what, rows, dx)) return rc;
+  if (rows == 0) return SIGMAENV_OK;
+  HIPCHK(h, hipSetDevice(h->device));
+  return mlp32_delta_launch(h, m, acts, dout, workspace, rows, dx);
+}
+// index == nullptr and n_index == 0: the rows are the record's blocks (sigmaenv_mlp32_backward); seg_src == seg_dst == 0: no padding
+extern "C" int sigmaenv_mlp32_backward_dx(sigmaenv_t* h, sigmaenv_mlp32* m, const float* in, int32_t rows_per_block, int64_t row_stride, int32_t n_blocks, int64_t block_stride,
+                                          const int32_t* index, int32_t n_index, int32_t seg_src, int32_t seg_dst, const float* acts, const float* dout, float* workspace,
+                                          float* const* grad_w, float* const* grad_b, float* dx) {
+  const Mlp32Pad pd{seg_src, seg_dst};
+  return mlp32_backward_impl(h, m, "mlp32_backward_dx", in, rows_per_block, row_stride, n_blocks, block_stride, index, n_index, acts, dout, workspace, grad_w, grad_b,
+                             seg_src || seg_dst ? &pd : nullptr, true, dx);
 }

@@ -440,7 +440,8 @@ __global__ void sigmaenv_actor_head_kernel(const float* __restrict__ out4, int R
 struct sigmaenv_mlp32 {
   Mlp32Weights w{};
   Mlp32sWeights ws{};   // the split-fp16 form of the same network (sigmaenv_mlp32s.inc)
-  float* wt[MLP32_MAX_LAYERS] = {};  // the exact form of the TRANSPOSED weights of layers 1 .. n_layers - 1, for the backward pass (sigmaenv_grad.inc)
+  float* wt[MLP32_MAX_LAYERS] = {};  // the exact form of the TRANSPOSED weights of layers 1 .. n_layers - 1, for the backward pass (sigmaenv_grad.inc); layer 0's only in a
+                                     // handle made by sigmaenv_mlp32_create_input_grad (else nullptr): kept current by every path that rewrites weights
   int mode = SIGMAENV_MLP32_SPLIT;       // the mode in force
   int requested = SIGMAENV_MLP32_SPLIT;  // the mode asked for (sigmaenv_mlp32_set_mode): in force again when sigmaenv_mlp32_load_device brings the weights back into range
   bool split_ok = true;    // the split form may run: every weight inside its range and split_fits
@@ -462,8 +463,8 @@ extern "C" void sigmaenv_mlp32_destroy(sigmaenv_mlp32* m) {
 }
 
 // n_layers torch.nn.Linear layers (weights[l]: [dims[l + 1], dims[l]] row-major fp32, biases[l]: [dims[l + 1]]), Tanh between them; hidden widths
-// must be 256, dims[n_layers] <= 32.
-extern "C" int sigmaenv_mlp32_create(int32_t n_layers, const int32_t* dims, const float* const* weights, const float* const* biases, sigmaenv_mlp32** out) {
+// must be 256, dims[n_layers] <= 32.  input_grad: the handle also holds layer 0's transposed form (sigmaenv_mlp32_create_input_grad).
+static int mlp32_create_impl(int32_t n_layers, const int32_t* dims, const float* const* weights, const float* const* biases, bool input_grad, sigmaenv_mlp32** out) {
   if (!out || !dims || !weights || !biases || n_layers < 2 || n_layers > MLP32_MAX_LAYERS) return SIGMAENV_EINVAL;
   for (int l = 1; l < n_layers; ++l) if (dims[l] != MLP32_H) return SIGMAENV_EINVAL;
   if (dims[0] < 1 || dims[0] > 4096 || dims[n_layers] < 1 || dims[n_layers] > 32) return SIGMAENV_EINVAL;
@@ -487,17 +488,17 @@ extern "C" int sigmaenv_mlp32_create(int32_t n_layers, const int32_t* dims, cons
   bool out_of_range = false;
   for (int l = 0; l < n_layers; ++l) {
     Mlp32Layer a = pack_mlp32_layer(dims, l, n_layers, m->split_fits);
-    std::vector<float> ew(a.n_exact), eb(a.fp_exact), sb(load_split_biases(a.output_layer != 0), 0.0f), tw(l > 0 ? load_exact_t_slots(a.F, a.K) : 0);
+    std::vector<float> ew(a.n_exact), eb(a.fp_exact), sb(load_split_biases(a.output_layer != 0), 0.0f), tw(l > 0 || input_grad ? load_exact_t_slots(a.F, a.K) : 0);
     std::vector<uint16_t> sw((size_t)2 * load_split_pairs(a.F, a.K, a.output_layer != 0), 0);
     a.w = weights[l]; a.b = biases[l];
     a.ew = ew.data(); a.eb = eb.data(); a.sw = sw.data(); a.sb = sb.data();
     for (int i = 0, n = pack_mlp32_lanes(a); i < n; ++i) out_of_range |= pack_mlp32_slot(a, i);
-    for (int i = 0; i < (int)tw.size(); ++i) pack_mlp32_t_slot(weights[l], tw.data(), a.F, a.K, i);  // the backward pass's form (sigmaenv_grad.inc): layers 1 .. n_layers - 1
+    for (int i = 0; i < (int)tw.size(); ++i) pack_mlp32_t_slot(weights[l], tw.data(), a.F, a.K, i);  // the backward pass's form (sigmaenv_grad.inc): layers 1 .. n_layers - 1, layer 0 on request
     int rc = pack_upload(m->allocs, ew.data(), ew.size() * 4, (const void**)&m->w.w[l]);
     if (!rc) rc = pack_upload(m->allocs, eb.data(), eb.size() * 4, (const void**)&m->w.b[l]);
     if (!rc) rc = pack_upload(m->allocs, sw.data(), sw.size() * 2, (const void**)&m->ws.w[l]);
     if (!rc) rc = pack_upload(m->allocs, sb.data(), sb.size() * 4, (const void**)&m->ws.b[l]);
-    if (!rc && l > 0) rc = pack_upload(m->allocs, tw.data(), tw.size() * 4, (const void**)&m->wt[l]);
+    if (!rc && !tw.empty()) rc = pack_upload(m->allocs, tw.data(), tw.size() * 4, (const void**)&m->wt[l]);
     if (rc) { sigmaenv_mlp32_destroy(m); return rc; }
     m->w.K[l] = load_exact_kp(a.K); m->w.F[l] = a.F; m->w.Fp[l] = a.fp_exact;
     m->ws.KB[l] = load_split_kb(a.K); m->ws.F[l] = a.F;
@@ -508,6 +509,12 @@ extern "C" int sigmaenv_mlp32_create(int32_t n_layers, const int32_t* dims, cons
   if (hipMemcpy(m->range_word, &word, 4, hipMemcpyHostToDevice) != hipSuccess) { sigmaenv_mlp32_destroy(m); return SIGMAENV_EHIP; }
   *out = m;
   return SIGMAENV_OK;
+}
+extern "C" int sigmaenv_mlp32_create(int32_t n_layers, const int32_t* dims, const float* const* weights, const float* const* biases, sigmaenv_mlp32** out) {
+  return mlp32_create_impl(n_layers, dims, weights, biases, false, out);
+}
+extern "C" int sigmaenv_mlp32_create_input_grad(int32_t n_layers, const int32_t* dims, const float* const* weights, const float* const* biases, sigmaenv_mlp32** out) {
+  return mlp32_create_impl(n_layers, dims, weights, biases, true, out);
 }
 
 // SIGMAENV_MLP32_EXACT / SIGMAENV_MLP32_SPLIT (include/sigmaenv.h); a network with a weight outside the split form's range stays exact

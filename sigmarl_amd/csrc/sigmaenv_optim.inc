@@ -197,8 +197,8 @@ extern "C" int sigmaenv_optim_step(sigmaenv_t* h, const sigmaenv_optim_args_t* a
       L.a.sw = reinterpret_cast<uint16_t*>(const_cast<f16x8_t*>(m->ws.w[l])); L.a.sb = const_cast<float*>(m->ws.b[l]);
       L.a.range = m->range_word;
       L.n_a = pack_mlp32_lanes(L.a);
-      L.tw = l > 0 ? m->wt[l] : nullptr;
-      L.n_t = l > 0 ? load_exact_t_slots(F, K) : 0;
+      L.tw = m->wt[l];  // (layer 0: only a handle made by sigmaenv_mlp32_create_input_grad holds the form)
+      L.n_t = m->wt[l] ? load_exact_t_slots(F, K) : 0;
       if (nk.actor) {
         L.y = pack_actor_layer(nk.actor->D, l);
         L.y.w = nk.weights[l]; L.y.b = nk.biases[l];
