@@ -75,23 +75,30 @@ def source_pairs(source):
     return [tuple(q) for q in source]
 
 
+def _save_forward(ctx, net, env, spec, shape):
+    """The saving forward of both ``apply`` Functions, and what their backward needs of it: the row addressing, the activations, the weights' version."""
+    y, acts = net._forward_save(env, spec)
+    ctx.net, ctx.env, ctx.spec, ctx.acts, ctx.version = net, env, spec, acts, net._version
+    return y.view(shape)
+
+
+def _saved_net(ctx):
+    if ctx.net._version != ctx.version:
+        raise RuntimeError("Mlp32.apply: load() replaced the network's weights between this forward and its backward")
+    return ctx.net
+
+
 class _Mlp32Function(torch.autograd.Function):
     """``Mlp32.apply``: ``sigmaenv_mlp32_forward_save`` forwards, ``sigmaenv_mlp32_backward`` backwards; the inputs are the network's parameters (weight, bias per
     layer), the rows are a constant."""
 
     @staticmethod
     def forward(ctx, net, env, spec, shape, *params):
-        y, acts = net._forward_save(env, spec)
-        ctx.net, ctx.env, ctx.spec, ctx.acts = net, env, spec, acts
-        ctx.version = net._version
-        return y.view(shape)
+        return _save_forward(ctx, net, env, spec, shape)
 
     @staticmethod
     def backward(ctx, dy):
-        net = ctx.net
-        if net._version != ctx.version:
-            raise RuntimeError("Mlp32.apply: load() replaced the network's weights between this forward and its backward")
-        gw, gb = net._backward(ctx.env, ctx.spec, ctx.acts, dy)
+        gw, gb = _saved_net(ctx)._backward(ctx.env, ctx.spec, ctx.acts, dy)
         ctx.acts = None
         return (None, None, None, None, *[t for q in zip(gw, gb) for t in q])
 
@@ -103,20 +110,13 @@ class _Mlp32InputFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, net, env, shape, x, *params):
-        spec = (x.detach(), 0, x.numel() // net.in_dim, net.in_dim, 1, 0, None)
-        y, acts = net._forward_save(env, spec)
-        ctx.net, ctx.env, ctx.spec, ctx.acts = net, env, spec, acts
-        ctx.version = net._version
-        return y.view(shape)
+        return _save_forward(ctx, net, env, (x.detach(), 0, x.numel() // net.in_dim, net.in_dim, 1, 0, None), shape)
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, dy):
-        net = ctx.net
-        if net._version != ctx.version:
-            raise RuntimeError("Mlp32.apply: load() replaced the network's weights between this forward and its backward")
         want_dx, want_params = ctx.needs_input_grad[3], any(ctx.needs_input_grad[4:])
-        gw, gb, dx = net._backward_dx(ctx.env, ctx.spec, ctx.acts, dy, want_params, want_dx)
+        gw, gb, dx = _saved_net(ctx)._backward_dx(ctx.env, ctx.spec, ctx.acts, dy, want_params, want_dx)
         x = ctx.spec[0]
         ctx.acts = ctx.spec = None
         grads = [t for q in zip(gw, gb) for t in q] if want_params else [None] * (len(ctx.needs_input_grad) - 4)
@@ -224,13 +224,7 @@ class Mlp32:
         lib = group[0].lib
         h = self.handle(lib)
         wp, bp = self._device_pointers()
-
-        def call(env):
-            rc = lib.mlp32_load_device(env.h, h, wp, bp)
-            if rc != 0:
-                raise RuntimeError(f"sigmaenv_mlp32_load_device failed with code {rc}: {lib.last_error(env.h).decode()}")
-
-        self._ordered_pack(group, call)
+        self._ordered_pack(group, lambda env: env._chk(lib.mlp32_load_device(env.h, h, wp, bp), "mlp32_load_device"))
         self._handle_version[lib.path] = self._version
 
     def _snapshot(self, envs, ws, bs):
@@ -329,9 +323,7 @@ class Mlp32:
             out = torch.empty((*x.shape[:-1], self.out_dim), dtype=torch.float32, device=x.device)
         if rows == 0:
             return out
-        rc = env.lib.mlp32_forward(env.h, self.handle(env.lib, env), C.c_void_p(x.data_ptr()), rows, C.c_void_p(out.data_ptr()))
-        if rc != 0:
-            raise RuntimeError(f"sigmaenv_mlp32_forward failed with code {rc}: {env.lib.last_error(env.h).decode()}")
+        env._chk(env.lib.mlp32_forward(env.h, self.handle(env.lib, env), C.c_void_p(x.data_ptr()), rows, C.c_void_p(out.data_ptr())), "mlp32_forward")
         return out
 
     def _pad(self, pad, what):
@@ -356,37 +348,27 @@ class Mlp32:
         of which the last ``dst - src`` are zero -- bit for bit ``forward`` on the rows copied dense and padded, without that copy."""
         if not (base.is_cuda and base.dtype == torch.float32 and base.is_contiguous()):
             raise TypeError("the rows must lie in a contiguous float32 CUDA tensor")
-        offset, rpb, rs, nb, bs = int(offset), int(rows_per_block), int(row_stride), int(n_blocks), int(block_stride)
-        src, dst, width = self._pad(pad, "forward_rows")
-        if rpb < 0 or nb < 0 or offset < 0 or rs < width or bs < 0:
-            raise ValueError(f"forward_rows: counts and offsets must be >= 0 and row_stride >= the width of a row in memory, {width}")
-        if rpb and nb and offset + (nb - 1) * bs + (rpb - 1) * rs + width > base.numel():
-            raise ValueError("forward_rows: the last row ends beyond the tensor")
+        offset, rpb, rs, nb, bs, src, dst = check_rows(self, base, offset, rows_per_block, row_stride, n_blocks, block_stride, pad, "forward_rows")
         if out is None:
             out = torch.empty((nb, rpb, self.out_dim), dtype=torch.float32, device=base.device)
         elif not (out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and out.numel() == nb * rpb * self.out_dim):
             raise TypeError(f"out must be a contiguous float32 CUDA tensor of {nb * rpb * self.out_dim} elements")
         if rpb == 0 or nb == 0:
             return out
+        rows = (env.h, self.handle(env.lib, env), C.c_void_p(base.data_ptr() + 4 * offset), rpb, rs, nb, bs)
         if pad is not None:
-            rc = env.lib.mlp32_forward_rows_pad(env.h, self.handle(env.lib, env), C.c_void_p(base.data_ptr() + 4 * offset), rpb, rs, nb, bs, src, dst, C.c_void_p(out.data_ptr()))
-            if rc != 0:
-                raise RuntimeError(f"sigmaenv_mlp32_forward_rows_pad failed with code {rc}: {env.lib.last_error(env.h).decode()}")
-            return out
-        rc = env.lib.mlp32_forward_rows(env.h, self.handle(env.lib, env), C.c_void_p(base.data_ptr() + 4 * offset), rpb, rs, nb, bs, C.c_void_p(out.data_ptr()))
-        if rc != 0:
-            raise RuntimeError(f"sigmaenv_mlp32_forward_rows failed with code {rc}: {env.lib.last_error(env.h).decode()}")
+            env._chk(env.lib.mlp32_forward_rows_pad(*rows, src, dst, C.c_void_p(out.data_ptr())), "mlp32_forward_rows_pad")
+        else:
+            env._chk(env.lib.mlp32_forward_rows(*rows, C.c_void_p(out.data_ptr())), "mlp32_forward_rows")
         return out
 
 
     # ---- the network differentiated (sigmaenv_mlp32_forward_save / sigmaenv_mlp32_backward) ----
-    def _index(self, env, index, n_blocks, check_index):
-        """The minibatch's block indices, checked before any launch: a contiguous int32 CUDA tensor ``[M]`` on the env's device (``TypeError``) whose entries --
-        unless ``check_index`` is false -- lie in ``[0, n_blocks)`` (``ValueError``; ``min`` / ``max`` on the device, one host wait)."""
-        if not (isinstance(index, torch.Tensor) and index.is_cuda and index.dtype == torch.int32 and index.dim() == 1 and index.is_contiguous()
-                and index.device == env.device):
-            raise TypeError(f"apply: index must be a contiguous int32 CUDA tensor [M] on {env.device}")
-        if check_index and index.numel():
+    def _index(self, env, index, n_blocks, in_range):
+        """The minibatch's block indices, checked before any launch: ``check_index``'s tensor (``TypeError``) whose entries -- unless ``in_range`` is false --
+        lie in ``[0, n_blocks)`` (``ValueError``; ``min`` / ``max`` on the device, one host wait)."""
+        check_index(index, env, "apply")
+        if in_range and index.numel():
             lo, hi = (int(v) for v in torch.stack((index.min(), index.max())).tolist())
             if lo < 0 or hi >= n_blocks:
                 raise ValueError(f"apply: index entries in [{lo}, {hi}] are not all inside the record's {n_blocks} blocks")
@@ -410,12 +392,7 @@ class Mlp32:
             raise TypeError("the rows must lie in a contiguous float32 CUDA tensor")
         if base.requires_grad:
             raise NotImplementedError("apply: the gradient with respect to the input is not built (rows base requires_grad)")
-        offset, rpb, rs, nb, bs = int(offset), int(rpb), int(rs), int(nb), int(bs)
-        src, dst, width = self._pad(pad, "apply")
-        if rpb < 0 or nb < 0 or offset < 0 or rs < width or bs < 0:
-            raise ValueError(f"apply: counts and offsets must be >= 0 and row_stride >= the width of a row in memory, {width}")
-        if rpb and nb and offset + (nb - 1) * bs + (rpb - 1) * rs + width > base.numel():
-            raise ValueError("apply: the last row ends beyond the tensor")
+        offset, rpb, rs, nb, bs, src, dst = check_rows(self, base, offset, rpb, rs, nb, bs, pad, "apply")
         if index is not None:
             index = self._index(env, index, nb, check_index)
             if pad is not None:
@@ -423,101 +400,69 @@ class Mlp32:
             return (base, offset, rpb, rs, nb, bs, index), (index.numel(), rpb, self.out_dim)
         return (base, offset, rpb, rs, nb, bs, None), (nb, rpb, self.out_dim)
 
-    def _chk_grad(self, env, rc, what):
-        if rc != 0:
-            raise RuntimeError(f"sigmaenv_{what} failed with code {rc}: {env.lib.last_error(env.h).decode()}")
+    @staticmethod
+    def _picked(index, pad):
+        """Which of an entry point's three forms a row addressing takes -- plain, ``_indexed``, ``_indexed_pad`` -- and the arguments that form adds."""
+        if index is None:
+            return "", ()
+        args = (C.c_void_p(index.data_ptr()), index.numel())
+        return ("_indexed_pad", (*args, *pad[0])) if pad else ("_indexed", args)
 
     def _forward_save(self, env, spec):
-        """(y [rows, out_dim], acts [n_layers - 1, rows, 256]) on the env's stream, ordered after and before torch's current stream."""
+        """(y [rows, out_dim], acts [n_layers - 1, rows, 256]) on the env's stream, ordered after and before torch's current stream (``SigmaEnv._on_stream``)."""
         base, offset, rpb, rs, nb, bs, index, *pad = spec  # (an eighth entry: (src, dst) of padded rows, with an index)
         n, dev = rpb * (nb if index is None else index.numel()), env.device
-        cur = torch.cuda.current_stream(dev)
         y = torch.empty((n, self.out_dim), dtype=torch.float32, device=dev)
         acts = torch.empty((len(self._keep[1]) - 1, n, 256), dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
+        with torch.cuda.device(dev):  # a handle that is behind the last ``load`` is packed here, ahead of the first wait: on the env's stream, so before the kernel
             h = self.handle(env.lib, env)
-            env.stream.wait_stream(cur)
-            src = C.c_void_p(base.data_ptr() + 4 * offset)
-            if index is None:
-                self._chk_grad(env, env.lib.mlp32_forward_save(env.h, h, src, rpb, rs, nb, bs, C.c_void_p(y.data_ptr()), C.c_void_p(acts.data_ptr())), "mlp32_forward_save")
-            elif pad:
-                self._chk_grad(env, env.lib.mlp32_forward_save_indexed_pad(env.h, h, src, rpb, rs, nb, bs, C.c_void_p(index.data_ptr()), index.numel(), pad[0][0], pad[0][1],
-                                                                          C.c_void_p(y.data_ptr()), C.c_void_p(acts.data_ptr())), "mlp32_forward_save_indexed_pad")
-            else:
-                self._chk_grad(env, env.lib.mlp32_forward_save_indexed(env.h, h, src, rpb, rs, nb, bs, C.c_void_p(index.data_ptr()), index.numel(), C.c_void_p(y.data_ptr()),
-                                                                      C.c_void_p(acts.data_ptr())), "mlp32_forward_save_indexed")
-            cur.wait_stream(env.stream)
-        for t in (base, y, acts) + (() if index is None else (index,)):
-            t.record_stream(env.stream)
+        p = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
+        suffix, picked = self._picked(index, pad)
+        what, args = "mlp32_forward_save" + suffix, (env.h, h, C.c_void_p(base.data_ptr() + 4 * offset), rpb, rs, nb, bs, *picked, p(y), p(acts))
+        env._on_stream(what, lambda: getattr(env.lib, what)(*args), (base, y, acts) + (() if index is None else (index,)))
         return y, acts
 
     def _backward(self, env, spec, acts, dout):
         """(grad_w, grad_b) lists in ``torch.nn.Linear`` layout: ``sigmaenv_mlp32_backward`` on the env's stream, ordered as ``_forward_save``."""
-        base, offset, rpb, rs, nb, bs, index, *pad = spec
-        n, dev = rpb * (nb if index is None else index.numel()), env.device
-        dims = [int(d) for d in self._keep[0]]
-        cur = torch.cuda.current_stream(dev)
-        dout = dout.reshape(n, self.out_dim).to(torch.float32).contiguous()
-        nf = C.c_uint64()
-        h = self.handle(env.lib)
-        rc = env.lib.mlp32_backward_workspace(h, n, C.byref(nf))
-        if rc != 0:
-            raise RuntimeError(f"sigmaenv_mlp32_backward_workspace failed with code {rc}")
-        ws = torch.empty((max(int(nf.value), 4),), dtype=torch.float32, device=dev)
-        gw = [torch.empty((dims[l + 1], dims[l]), dtype=torch.float32, device=dev) for l in range(len(dims) - 1)]
-        gb = [torch.empty((dims[l + 1],), dtype=torch.float32, device=dev) for l in range(len(dims) - 1)]
-        PA = C.c_void_p * len(gw)
-        with torch.cuda.device(dev):
-            env.stream.wait_stream(cur)
-            src, tail = C.c_void_p(base.data_ptr() + 4 * offset), (C.c_void_p(acts.data_ptr()), C.c_void_p(dout.data_ptr()), C.c_void_p(ws.data_ptr()),
-                                                                   PA(*[t.data_ptr() for t in gw]), PA(*[t.data_ptr() for t in gb]))
-            if index is None:
-                self._chk_grad(env, env.lib.mlp32_backward(env.h, h, src, rpb, rs, nb, bs, *tail), "mlp32_backward")
-            elif pad:
-                self._chk_grad(env, env.lib.mlp32_backward_indexed_pad(env.h, h, src, rpb, rs, nb, bs, C.c_void_p(index.data_ptr()), index.numel(), pad[0][0], pad[0][1], *tail),
-                               "mlp32_backward_indexed_pad")
-            else:
-                self._chk_grad(env, env.lib.mlp32_backward_indexed(env.h, h, src, rpb, rs, nb, bs, C.c_void_p(index.data_ptr()), index.numel(), *tail), "mlp32_backward_indexed")
-            cur.wait_stream(env.stream)
-        for t in [base, acts, dout, ws] + gw + gb + ([] if index is None else [index]):
-            t.record_stream(env.stream)
-        return gw, gb
+        return self._backward_dx(env, spec, acts, dout, want_dx=False)[:2]
 
     def _backward_dx(self, env, spec, acts, dout, want_params=True, want_dx=True):
         """(grad_w, grad_b, dx [n, in_dim]) on the env's stream, ordered as ``_forward_save``; what is not wanted is ``None`` and is not computed:
-        ``sigmaenv_mlp32_backward_dx`` for both, ``sigmaenv_mlp32_input_grad`` for ``dx`` alone (one launch, no input row read), ``_backward`` for the parameters alone."""
-        if not want_dx:
-            return (*self._backward(env, spec, acts, dout), None) if want_params else (None, None, None)
-        if not self._input_grad:
+        ``sigmaenv_mlp32_backward_dx`` for both, ``sigmaenv_mlp32_input_grad`` for ``dx`` alone (one launch, no input row read), ``sigmaenv_mlp32_backward`` /
+        ``_indexed`` / ``_indexed_pad`` for the parameters alone, no launch for neither."""
+        if not (want_params or want_dx):
+            return None, None, None
+        if want_dx and not self._input_grad:
             raise RuntimeError("the gradient with respect to the input needs a network made with input_grad=True")
         base, offset, rpb, rs, nb, bs, index, *pad = spec
         n, dev = rpb * (nb if index is None else index.numel()), env.device
         dims = [int(d) for d in self._keep[0]]
-        cur = torch.cuda.current_stream(dev)
         dout = dout.reshape(n, self.out_dim).to(torch.float32).contiguous()
         nf = C.c_uint64()
         h = self.handle(env.lib)
-        rc = (env.lib.mlp32_backward_workspace if want_params else env.lib.mlp32_input_grad_workspace)(h, n, C.byref(nf))
+        query = "backward" if want_params else "input_grad"
+        rc = getattr(env.lib, f"mlp32_{query}_workspace")(h, n, C.byref(nf))
         if rc != 0:
-            raise RuntimeError(f"sigmaenv_mlp32_{'backward' if want_params else 'input_grad'}_workspace failed with code {rc}")
+            raise RuntimeError(f"sigmaenv_mlp32_{query}_workspace failed with code {rc}")
         ws = torch.empty((max(int(nf.value), 4),), dtype=torch.float32, device=dev)
-        dx = torch.empty((n, self.in_dim), dtype=torch.float32, device=dev)
+        dx = torch.empty((n, self.in_dim), dtype=torch.float32, device=dev) if want_dx else None
         gw = [torch.empty((dims[l + 1], dims[l]), dtype=torch.float32, device=dev) for l in range(len(dims) - 1)] if want_params else None
         gb = [torch.empty((dims[l + 1],), dtype=torch.float32, device=dev) for l in range(len(dims) - 1)] if want_params else None
         p = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
-        with torch.cuda.device(dev):
-            env.stream.wait_stream(cur)
-            if want_params:
-                PA = C.c_void_p * len(gw)
-                src, (seg_src, seg_dst) = C.c_void_p(base.data_ptr() + 4 * offset), (pad[0] if pad else (0, 0))
-                self._chk_grad(env, env.lib.mlp32_backward_dx(env.h, h, src, rpb, rs, nb, bs, None if index is None else p(index), 0 if index is None else index.numel(),
-                                                              seg_src, seg_dst, p(acts), p(dout), p(ws), PA(*[t.data_ptr() for t in gw]), PA(*[t.data_ptr() for t in gb]), p(dx)),
-                               "mlp32_backward_dx")
+        if not want_params:
+            what, args = "mlp32_input_grad", (p(acts), p(dout), n, p(ws), p(dx))
+        else:
+            PA = C.c_void_p * len(gw)
+            rows, tail = (C.c_void_p(base.data_ptr() + 4 * offset), rpb, rs, nb, bs), (p(acts), p(dout), p(ws), PA(*[t.data_ptr() for t in gw]), PA(*[t.data_ptr() for t in gb]))
+            if want_dx:
+                what, picked = "mlp32_backward_dx", (None if index is None else p(index), 0 if index is None else index.numel(), *(pad[0] if pad else (0, 0)))
+                tail += (p(dx),)
             else:
-                self._chk_grad(env, env.lib.mlp32_input_grad(env.h, h, p(acts), p(dout), n, p(ws), p(dx)), "mlp32_input_grad")
-            cur.wait_stream(env.stream)
-        for t in [base, acts, dout, ws, dx] + (gw + gb if want_params else []) + ([] if index is None else [index]):
-            t.record_stream(env.stream)
+                suffix, picked = self._picked(index, pad)
+                what = "mlp32_backward" + suffix
+            args = (*rows, *picked, *tail)
+        env._on_stream(what, lambda: getattr(env.lib, what)(env.h, h, *args),
+                       [base, acts, dout, ws] + ([dx] if want_dx else []) + (gw + gb if want_params else []) + ([] if index is None else [index]))
         return gw, gb, dx
 
     def input_grad(self, env: SigmaEnv, x: torch.Tensor | None = None, *, rows=None, index: torch.Tensor | None = None, check_index: bool = True, pad=None, dout: torch.Tensor):
@@ -555,7 +500,7 @@ class Mlp32:
         optimiser stepped and ``load`` was not called) ``apply`` raises ``RuntimeError``: the forward would use the old numbers and credit the gradient to the new.
 
         Streams: the kernels run on the env's stream after everything torch's current stream holds, and torch's current stream then waits for them -- forwards
-        and backwards alike (``load``'s discipline)."""
+        and backwards alike (``SigmaEnv._on_stream``, the one statement of that order)."""
         through_x = self._input_grad and isinstance(x, torch.Tensor) and x.requires_grad
         spec, shape = self._rows_spec(x.detach() if through_x else x, rows, env, index, check_index, pad)
         for t in self._params:
@@ -574,6 +519,32 @@ def check_record(t, shape, what: str):
     if not isinstance(t, torch.Tensor) or not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == tuple(shape)):
         raise TypeError(f"{what} must be a contiguous float32 CUDA tensor {list(shape)}")
     return t
+
+
+def check_index(index, env, what: str):
+    """A minibatch's frame or block indices: a contiguous int32 CUDA tensor ``[M]`` on the env's device."""
+    if not (isinstance(index, torch.Tensor) and index.is_cuda and index.dtype == torch.int32 and index.dim() == 1 and index.is_contiguous() and index.device == env.device):
+        raise TypeError(f"{what}: index must be a contiguous int32 CUDA tensor [M] on {env.device}")
+    return index
+
+
+def check_slab(slab, W: int, what: str = "slab", Bt: str = "Bt"):
+    """The record rows of a rollout: a contiguous float32 CUDA tensor ``[T, Bt, W]`` (``Bt``: the name the message gives the buffer's env count)."""
+    if not isinstance(slab, torch.Tensor) or not (slab.is_cuda and slab.dtype == torch.float32 and slab.is_contiguous() and slab.dim() == 3 and slab.shape[2] == W):
+        raise TypeError(f"{what} must be a contiguous float32 CUDA tensor [T, {Bt}, {W}]")
+    return slab
+
+
+def check_rows(net, base, offset, rows_per_block, row_stride, n_blocks, block_stride, pad, what: str):
+    """The row addressing of ``forward_rows`` / ``apply(rows=)`` inside ``base``, checked: row ``t * rows_per_block + b`` starts at float ``offset + t * block_stride +
+    b * row_stride`` and is ``net._pad(pad)``'s width in memory.  Returns ``(offset, rows_per_block, row_stride, n_blocks, block_stride, src, dst)`` as ints."""
+    offset, rpb, rs, nb, bs = int(offset), int(rows_per_block), int(row_stride), int(n_blocks), int(block_stride)
+    src, dst, width = net._pad(pad, what)
+    if rpb < 0 or nb < 0 or offset < 0 or rs < width or bs < 0:
+        raise ValueError(f"{what}: counts and offsets must be >= 0 and row_stride >= the width of a row in memory, {width}")
+    if rpb and nb and offset + (nb - 1) * bs + (rpb - 1) * rs + width > base.numel():
+        raise ValueError(f"{what}: the last row ends beyond the tensor")
+    return offset, rpb, rs, nb, bs, src, dst
 
 
 class Critic(Mlp32):
@@ -676,9 +647,8 @@ class PriorityNet(Mlp32):
         scratch, sc, lp = torch.empty((env.B * env.N, 2), **kw), torch.empty((env.B, env.N), **kw), torch.empty((env.B, env.N), **kw)
         ranks = torch.empty((env.B, env.N), dtype=torch.int32, device=env.device)
         p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
-        rc = env.lib.priority_forward(env.h, self.handle(env.lib, env), p(obs), p(scratch), p(sc), p(lp), p(ranks), int(seed), int(counter), int(bool(deterministic)))
-        if rc != 0:
-            raise RuntimeError(f"sigmaenv_priority_forward failed with code {rc}: {env.lib.last_error(env.h).decode()}")
+        env._chk(env.lib.priority_forward(env.h, self.handle(env.lib, env), p(obs), p(scratch), p(sc), p(lp), p(ranks), int(seed), int(counter), int(bool(deterministic))),
+                 "priority_forward")
         return sc, lp, ranks
 
 
@@ -744,13 +714,7 @@ class Actor:
         lib = group[0].lib
         h = self._bf16_handle(lib)
         wp, bp = self._mlp32._device_pointers()
-
-        def call(env):
-            rc = lib.actor_load_device(env.h, h, wp, bp)
-            if rc != 0:
-                raise RuntimeError(f"sigmaenv_actor_load_device failed with code {rc}: {lib.last_error(env.h).decode()}")
-
-        self._mlp32._ordered_pack(group, call)
+        self._mlp32._ordered_pack(group, lambda env: env._chk(lib.actor_load_device(env.h, h, wp, bp), "actor_load_device"))
         self._bf16_version[lib.path] = self._mlp32._version
 
     def load(self, env, source) -> str:
@@ -808,14 +772,11 @@ class Actor:
         p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
         if (precision or self.precision) == "fp32":
             lo, hi = self._keep[-2], self._keep[-1]
-            rc = env.lib.actor_forward_f32(env.h, self._mlp32.handle(env.lib, env), p(obs), p(self._scratch_out4(env)), lo.ctypes.data_as(C.c_void_p), hi.ctypes.data_as(C.c_void_p),
-                                            p(actions), p(log_prob), p(loc_scale), int(seed), int(counter), int(bool(deterministic)))
-            if rc != 0:
-                raise RuntimeError(f"sigmaenv_actor_forward_f32 failed with code {rc}: {env.lib.last_error(env.h).decode()}")
+            env._chk(env.lib.actor_forward_f32(env.h, self._mlp32.handle(env.lib, env), p(obs), p(self._scratch_out4(env)), lo.ctypes.data_as(C.c_void_p), hi.ctypes.data_as(C.c_void_p),
+                                               p(actions), p(log_prob), p(loc_scale), int(seed), int(counter), int(bool(deterministic))), "actor_forward_f32")
             return actions
-        rc = env.lib.actor_forward(env.h, self._bf16_handle(env.lib, env), p(obs), p(actions), p(log_prob), p(loc_scale), int(seed), int(counter), int(bool(deterministic)))
-        if rc != 0:
-            raise RuntimeError(f"sigmaenv_actor_forward failed with code {rc}: {env.lib.last_error(env.h).decode()}")
+        env._chk(env.lib.actor_forward(env.h, self._bf16_handle(env.lib, env), p(obs), p(actions), p(log_prob), p(loc_scale), int(seed), int(counter), int(bool(deterministic))),
+                 "actor_forward")
         return actions
 
     def rollout(self, env: SigmaEnv, n_steps: int, slab: torch.Tensor | None = None, log_prob: torch.Tensor | None = None,
@@ -872,11 +833,9 @@ class Actor:
                 raise ValueError("the rollout wrappers run the fp32 actor (precision='fp32')")
             opts = self._wrapper_opts(env, int(n_steps), wrapper, priority, tentative, ranks, scores, score_log_prob, base_obs, communication_noise)
             lo, hi = self._keep[-2], self._keep[-1]
-            rc = env.lib.rollout_f32_ex(env.h, self._mlp32.handle(env.lib, env), lo.ctypes.data_as(C.c_void_p), hi.ctypes.data_as(C.c_void_p), p(self._scratch_out4(env)),
-                                         int(n_steps), p(scratch), p_slab, p(log_prob), p(actions), int(seed), int(counter0), int(path_first), int(path_count),
-                                         int(bool(deterministic)), C.byref(opts))
-            if rc != 0:
-                raise RuntimeError(f"sigmaenv_rollout_f32_ex failed with code {rc}: {env.lib.last_error(env.h).decode()}")
+            env._chk(env.lib.rollout_f32_ex(env.h, self._mlp32.handle(env.lib, env), lo.ctypes.data_as(C.c_void_p), hi.ctypes.data_as(C.c_void_p), p(self._scratch_out4(env)),
+                                            int(n_steps), p(scratch), p_slab, p(log_prob), p(actions), int(seed), int(counter0), int(path_first), int(path_count),
+                                            int(bool(deterministic)), C.byref(opts)), "rollout_f32_ex")
             return
         if base_obs is not None:
             raise ValueError("base_obs belongs to wrapper='prioritized'")
@@ -884,16 +843,12 @@ class Actor:
             raise ValueError("communication_noise belongs to wrapper='prioritized'")
         if (precision or self.precision) == "fp32":
             lo, hi = self._keep[-2], self._keep[-1]
-            rc = env.lib.rollout_f32(env.h, self._mlp32.handle(env.lib, env), lo.ctypes.data_as(C.c_void_p), hi.ctypes.data_as(C.c_void_p), p(self._scratch_out4(env)), int(n_steps),
-                                      p(scratch), p_slab, p(log_prob), p(actions), int(seed), int(counter0), int(path_first), int(path_count),
-                                      int(bool(deterministic)))
-            if rc != 0:
-                raise RuntimeError(f"sigmaenv_rollout_f32 failed with code {rc}: {env.lib.last_error(env.h).decode()}")
+            env._chk(env.lib.rollout_f32(env.h, self._mlp32.handle(env.lib, env), lo.ctypes.data_as(C.c_void_p), hi.ctypes.data_as(C.c_void_p), p(self._scratch_out4(env)), int(n_steps),
+                                         p(scratch), p_slab, p(log_prob), p(actions), int(seed), int(counter0), int(path_first), int(path_count),
+                                         int(bool(deterministic))), "rollout_f32")
             return
-        rc = env.lib.rollout(env.h, self._bf16_handle(env.lib, env), int(n_steps), p(scratch), p_slab, p(log_prob), p(actions), int(seed), int(counter0), int(path_first),
-                              int(path_count), int(bool(deterministic)))
-        if rc != 0:
-            raise RuntimeError(f"sigmaenv_rollout failed with code {rc}: {env.lib.last_error(env.h).decode()}")
+        env._chk(env.lib.rollout(env.h, self._bf16_handle(env.lib, env), int(n_steps), p(scratch), p_slab, p(log_prob), p(actions), int(seed), int(counter0), int(path_first),
+                                 int(path_count), int(bool(deterministic))), "rollout")
 
     def _noise_opts(self, env: SigmaEnv, opts: capi.RolloutOpts, noise) -> None:
         """``communication_noise`` into ``opts``: the pair ``(s_v, s_d)`` of a float level, or the ``[B, 2]`` pairs of a ``[B]`` tensor of levels."""

@@ -419,7 +419,10 @@ class SigmaEnv:
         return hdr
 
     def _on_stream(self, what, fn, tensors):
-        """``fn()`` on the env's stream after what torch's current stream holds, which then waits for it."""
+        """THE hand-over between torch's current stream and the env's, stated here and nowhere else (the networks' forward and backward, the loss heads, the
+        optimiser step, the replay buffer, the episode returns, ``snapshot`` / ``restore``): the env's stream waits for what the current stream holds, ``fn()``
+        enqueues on the env's stream and returns the library's code (``sigmaenv_{what}``: a non-zero code raises here, before anything further), the current stream
+        waits for the env's, and every tensor of ``tensors`` -- all that ``fn`` reads or writes -- is recorded on the env's stream, which torch's allocator did not see."""
         cur = torch.cuda.current_stream(self.device)
         with torch.cuda.device(self.device):
             self.stream.wait_stream(cur)

@@ -39,7 +39,7 @@ import ctypes as C
 import torch
 
 from . import capi
-from .actor import Actor, Critic, Mlp32, PriorityNet, check_record, load_source, source_pairs
+from .actor import Actor, Critic, Mlp32, PriorityNet, check_index, check_record, check_slab, load_source, source_pairs
 from .params import check_initial_state_bank
 
 TD_GAMMA = 0.9  # compute_td_error's discount as the trainer calls it (mappo_cavs.py:383, :454) -- not Parameters.gamma
@@ -59,8 +59,7 @@ def gae(env, slab: torch.Tensor, state_value: torch.Tensor, next_state_value: to
     ``compute_td_error(gamma=td_gamma)`` normalised over THIS handle's ``[T, B]`` into [1e-3, 10].  Enqueued on the env's stream."""
     B, N, D = env.B, env.N, env.D
     W = N * (D + 1) + 1
-    if not isinstance(slab, torch.Tensor) or not (slab.is_cuda and slab.dtype == torch.float32 and slab.is_contiguous() and slab.dim() == 3 and slab.shape[2] == W):
-        raise TypeError(f"slab must be a contiguous float32 CUDA tensor [T, Bt, {W}]")
+    check_slab(slab, W)
     T, Bt, e0 = slab.shape[0], slab.shape[1], int(env_first)
     if T < 1 or not 0 <= e0 <= Bt - B:
         raise ValueError(f"slab {list(slab.shape)}: at least one step, and envs [{e0}, {e0 + B}) inside its {Bt}")
@@ -81,9 +80,7 @@ def gae(env, slab: torch.Tensor, state_value: torch.Tensor, next_state_value: to
     a.state_value, a.next_state_value, a.advantage, a.value_target = sv.data_ptr(), nv.data_ptr(), adv.data_ptr(), vt.data_ptr()
     a.td_priority = td.data_ptr() if td is not None else None
     a.gamma, a.lmbda, a.td_gamma = float(gamma), float(lmbda), float(td_gamma)
-    rc = env.lib.gae(env.h, C.byref(a))
-    if rc != 0:
-        raise RuntimeError(f"sigmaenv_gae failed with code {rc}: {env.lib.last_error(env.h).decode()}")
+    env._chk(env.lib.gae(env.h, C.byref(a)), "gae")
     return adv, vt, td
 
 
@@ -133,53 +130,34 @@ def collect(env, actor, critic, T: int, params=None, gamma: float | None = None,
         if k in rollout_kw:
             raise TypeError(f"collect() makes the {k} record itself")
     T, B, N, D = int(T), env.B, env.N, env.D
-    Dc = D + 2 * env.K
-    if rollout_kw.get("wrapper") == "prioritized" and (critic.in_dim == N * Dc != N * D or priority_critic is not None):
-        return _collect_prioritized(env, actor, critic, priority_critic, T, gamma, lmbda, td_gamma, td_error, seed, counter0, returns, rollout_kw)
-    if priority_critic is not None:
+    W, Dc = N * (D + 1) + 1, D + 2 * env.K
+    prioritized = rollout_kw.get("wrapper") == "prioritized" and (critic.in_dim == N * Dc != N * D or priority_critic is not None)
+    if priority_critic is not None and not prioritized:
         raise ValueError("collect(): priority_critic belongs to wrapper='prioritized'")
-    W = N * (D + 1) + 1
-    kw = dict(dtype=torch.float32, device=env.device)
-    slab, obs = torch.empty((T, B, W), **kw), torch.empty((T, B, N, D), **kw)
-    act, logp = torch.empty((T, B, N, 2), **kw), torch.empty((T, B, N), **kw)
-    actor.rollout(env, T, slab=slab, log_prob=logp, actions=act, obs_rec=obs, seed=seed, counter0=counter0, **rollout_kw)
-    sv, nv = critic.rollout_values(env, slab, obs, T)
-    adv, vt, td = gae(env, slab, sv, nv, gamma, lmbda, td_error=bool(td_error), td_gamma=td_gamma)
-    out = {
-        "observation": obs, "action": act, "sample_log_prob": logp, "slab": slab,
-        ("next", "observation"): slab[:, :, : N * D].unflatten(2, (N, D)), ("next", "reward"): slab[:, :, N * D: N * D + N], ("next", "done"): slab[:, :, N * D + N],
-        "state_value": sv, ("next", "state_value"): nv, "advantage": adv, "value_target": vt,
-    }
-    if td is not None:
-        out["td_error"] = td
-    if returns is not None:
-        out[("next", "episode_reward")], out["episode_stats"] = returns.update(slab, T)
-    return out
-
-
-def _collect_prioritized(env, actor, critic, priority_critic, T, gamma, lmbda, td_gamma, td_error, seed, counter0, returns, rollout_kw) -> dict:
-    """``collect`` under prioritized action propagation (its docstring): the records of the wrapper, the base critic on base observations, the priority critic's pair"""
-    B, N, D, K = env.B, env.N, env.D, env.K
-    W, Dc = N * (D + 1) + 1, D + 2 * K
-    net = isinstance(rollout_kw.get("priority"), PriorityNet)
+    net = prioritized and isinstance(rollout_kw.get("priority"), PriorityNet)
     if priority_critic is not None and not (net and isinstance(priority_critic, Critic)):
         raise TypeError("collect(): priority_critic is a Critic on the priority observation, next to priority= a PriorityNet")
     kw = dict(dtype=torch.float32, device=env.device)
-    slab, obs, base = torch.empty((T, B, W), **kw), torch.empty((T, B, N, D), **kw), torch.empty((T, B, N, Dc), **kw)
+    slab, obs = torch.empty((T, B, W), **kw), torch.empty((T, B, N, D), **kw)
     act, logp = torch.empty((T, B, N, 2), **kw), torch.empty((T, B, N), **kw)
-    ranks = torch.empty((T, B, N), dtype=torch.int32, device=env.device)
-    rec = dict(scores=torch.empty((T, B, N), **kw), score_log_prob=torch.empty((T, B, N), **kw)) if net else {}
-    actor.rollout(env, T, slab=slab, log_prob=logp, actions=act, obs_rec=obs, base_obs=base, ranks=ranks, seed=seed, counter0=counter0, **rec, **rollout_kw)
-    sv, nv = critic.rollout_values(env, slab, base, T, pad=(D, Dc))
+    rec = {}  # the wrapper's records: the base observation the base networks read, the ranks, and a PriorityNet's scores with their log-probabilities
+    if prioritized:
+        rec = dict(base_obs=torch.empty((T, B, N, Dc), **kw), ranks=torch.empty((T, B, N), dtype=torch.int32, device=env.device))
+    if net:
+        rec.update(scores=torch.empty((T, B, N), **kw), score_log_prob=torch.empty((T, B, N), **kw))
+    actor.rollout(env, T, slab=slab, log_prob=logp, actions=act, obs_rec=obs, seed=seed, counter0=counter0, **rec, **rollout_kw)
+    sv, nv = critic.rollout_values(env, slab, rec.get("base_obs", obs), T, pad=(D, Dc) if prioritized else None)
     adv, vt, td = gae(env, slab, sv, nv, gamma, lmbda, td_error=bool(td_error), td_gamma=td_gamma)
-    out = {
-        "observation": obs, "action": act, "sample_log_prob": logp, "slab": slab, BASE_OBS: base, PRIORITY + ("rank",): ranks,
+    out = {"observation": obs, "action": act, "sample_log_prob": logp, "slab": slab}
+    if prioritized:
+        out[BASE_OBS], out[PRIORITY + ("rank",)] = rec["base_obs"], rec["ranks"]
+    out.update({
         ("next", "observation"): slab[:, :, : N * D].unflatten(2, (N, D)), ("next", "reward"): slab[:, :, N * D: N * D + N], ("next", "done"): slab[:, :, N * D + N],
         "state_value": sv, ("next", "state_value"): nv, "advantage": adv, "value_target": vt,
-    }
+    })
     if net:
         out[PRIORITY + ("scores",)], out[PRIORITY + ("sample_log_prob",)] = rec["scores"], rec["score_log_prob"]
-    if priority_critic is not None:
+    if priority_critic is not None:  # the priority critic's own GAE; its pair takes the keys both losses read, the base critic's is re-keyed (the docstring)
         psv, pnv = priority_critic.rollout_values(env, slab, obs, T)
         padv, pvt, _ = gae(env, slab, psv, pnv, gamma, lmbda, td_error=False)
         out[PRIORITY + ("state_value",)], out[("next",) + PRIORITY + ("state_value",)] = psv, pnv
@@ -225,8 +203,7 @@ class EpisodeReturns:
         env = self.env
         B, N, D = env.B, env.N, env.D
         W = N * (D + 1) + 1
-        if not isinstance(slab, torch.Tensor) or not (slab.is_cuda and slab.dtype == torch.float32 and slab.is_contiguous() and slab.dim() == 3 and slab.shape[2] == W):
-            raise TypeError(f"slab must be a contiguous float32 CUDA tensor [T, Bt, {W}]")
+        check_slab(slab, W)
         Ts, Bt, e0 = slab.shape[0], slab.shape[1], int(env_first)
         T = Ts if T is None else int(T)
         if not 1 <= T <= Ts or not 0 <= e0 <= Bt - B:
@@ -240,15 +217,7 @@ class EpisodeReturns:
             er = check_record(episode_reward, (T, B, N), "episode_reward")
         result = torch.empty((4,), **kw)
         a = episode_args(env, T, slab.data_ptr() + 4 * e0 * W, Bt * W, self.carry.data_ptr(), result.data_ptr(), er.data_ptr() if er is not None else None)
-        cur = torch.cuda.current_stream(env.device)
-        with torch.cuda.device(env.device):  # on the env's stream after what torch's current stream holds, which then waits for it (ppo_head's discipline)
-            env.stream.wait_stream(cur)
-            rc = env.lib.episode_return(env.h, C.byref(a))
-            if rc != 0:
-                raise RuntimeError(f"sigmaenv_episode_return failed with code {rc}: {env.lib.last_error(env.h).decode()}")
-            cur.wait_stream(env.stream)
-        for t in (slab, self.carry, result) + ((er,) if er is not None else ()):
-            t.record_stream(env.stream)
+        env._on_stream("episode_return", lambda: env.lib.episode_return(env.h, C.byref(a)), (slab, self.carry, result) + ((er,) if er is not None else ()))
         return er, {k: result[i] for i, k in enumerate(capi.EPISODE_RESULT)}
 
     @staticmethod
@@ -283,27 +252,19 @@ def episode_args(env, T: int, slab_ptr, slab_stride: int, carry_ptr, result_ptr,
 
 # ---- the learner's side: minibatches of frames, the clip-PPO head, the update loop --------------------------------------------------------
 class _PpoHeadFunction(torch.autograd.Function):
-    """``ppo_head``: ``sigmaenv_ppo_head`` forwards; backwards the stored ``dout`` tensors times the incoming gradient of the loss."""
+    """``ppo_head`` / ``priority_ppo_head``: the entry point ``what`` (``sigmaenv_ppo_head`` on ``out [M, N, 4]``, ``sigmaenv_ppo_head_1d`` on ``out [M, N, 2]``) forwards;
+    backwards the stored ``dout`` tensors times the incoming gradient of the loss."""
 
     @staticmethod
-    def forward(ctx, env, args, keep, out, value):
-        dev = env.device
-        M, N = out.shape[0], out.shape[1]
-        kw = dict(dtype=torch.float32, device=dev)
-        dout_a, dout_c, result = torch.empty((M, N, 4), **kw), torch.empty((M,), **kw), torch.empty((8,), **kw)
+    def forward(ctx, env, what, args, keep, out, value):
+        M, N, width = out.shape
+        kw = dict(dtype=torch.float32, device=env.device)
+        dout_a, dout_c, result = torch.empty((M, N, width), **kw), torch.empty((M,), **kw), torch.empty((8,), **kw)
         ws = torch.empty((capi.PPO_SUMS * ((M * N + 255) // 256),), **kw)
         out, value = out.detach(), value.detach()
         args.out, args.value = out.data_ptr(), value.data_ptr()
         args.dout_actor, args.dout_critic, args.result, args.workspace = dout_a.data_ptr(), dout_c.data_ptr(), result.data_ptr(), ws.data_ptr()
-        cur = torch.cuda.current_stream(dev)
-        with torch.cuda.device(dev):  # on the env's stream after what torch's current stream holds, which then waits for it (Mlp32.apply's discipline)
-            env.stream.wait_stream(cur)
-            rc = env.lib.ppo_head(env.h, C.byref(args))
-            if rc != 0:
-                raise RuntimeError(f"sigmaenv_ppo_head failed with code {rc}: {env.lib.last_error(env.h).decode()}")
-            cur.wait_stream(env.stream)
-        for t in (out, value, dout_a, dout_c, result, ws, *keep):
-            t.record_stream(env.stream)
+        env._on_stream(what, lambda: getattr(env.lib, what)(env.h, C.byref(args)), (out, value, dout_a, dout_c, result, ws, *keep))
         ctx.save_for_backward(dout_a, dout_c)
         ctx.mark_non_differentiable(result)
         return (result[0] + result[1]) + result[2], result
@@ -311,7 +272,30 @@ class _PpoHeadFunction(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g, _):
         dout_a, dout_c = ctx.saved_tensors
-        return None, None, None, dout_a * g, dout_c * g
+        return None, None, None, None, dout_a * g, dout_c * g
+
+
+def _head_checks(fn: str, env, out, value, index, width: int, clip_epsilon) -> None:
+    """What both heads refuse before they look at a record (messages prefixed ``fn``): ``out`` / ``value`` that are not float32 CUDA tensors on the env's device, the
+    ``index`` (``check_index``), shapes other than ``[M, N, width]`` / ``[M]`` of its ``M`` frames, a ``clip_epsilon`` outside (0, 1)."""
+    for t, what in ((out, "out"), (value, "value")):
+        if not isinstance(t, torch.Tensor) or not (t.is_cuda and t.dtype == torch.float32 and t.device == env.device):
+            raise TypeError(f"{fn}: {what} must be a float32 CUDA tensor on {env.device}")
+    M = check_index(index, env, fn).numel()
+    if M < 1 or out.numel() != M * env.N * width or value.numel() != M:
+        raise ValueError(f"{fn}: out {list(out.shape)} / value {list(value.shape)} are not [M, {env.N}, {width}] / [M] of the {M} indexed frames (M >= 1)")
+    if not 0.0 < float(clip_epsilon) < 1.0:
+        raise ValueError(f"clip_epsilon = {clip_epsilon} is not in (0, 1)")
+
+
+def _head_launch(env, what: str, a, recs, index, out, value, width: int, clip_epsilon, entropy_coeff, critic_coeff, seed, counter):
+    """The fields both args structures share, then the launch (``_PpoHeadFunction``): ``(loss, info)``.  ``recs``: the four ``[T, B, ...]`` records ``a`` points at."""
+    M, N, (T, B) = index.numel(), env.N, recs[0].shape[:2]
+    a.n_index, a.n_frames, a.index = M, T * B, index.data_ptr()
+    a.clip_epsilon, a.entropy_coeff, a.critic_coeff = float(clip_epsilon), float(entropy_coeff), float(critic_coeff)
+    a.seed, a.counter = int(seed) & 0xFFFFFFFFFFFFFFFF, int(counter) & 0xFFFFFFFFFFFFFFFF
+    loss, result = _PpoHeadFunction.apply(env, what, a, (index, *recs), out.reshape(M, N, width).contiguous(), value.reshape(M).contiguous())
+    return loss, {k: result[i] for i, k in enumerate(capi.PPO_RESULT)}
 
 
 def ppo_head(env, out: torch.Tensor, value: torch.Tensor, batch: dict, index: torch.Tensor, *, low, high, clip_epsilon: float, entropy_coeff: float,
@@ -322,63 +306,17 @@ def ppo_head(env, out: torch.Tensor, value: torch.Tensor, batch: dict, index: to
     entropy sample's draws (a new ``counter`` per minibatch).  Returns ``(loss, info)``: ``loss = loss_objective + loss_entropy + loss_critic`` with a ``grad_fn``
     over ``out`` and ``value`` (a ``torch.autograd.Function``: the head writes both ``dout`` tensors in its forward launch, ``backward`` scales them), ``info`` the
     detached ``loss_objective``, ``loss_entropy``, ``loss_critic``, ``entropy``, ``clip_fraction``, ``kl_approx``.  Enqueued on the env's stream, nothing waits."""
-    N = env.N
-    for t, what in ((out, "out"), (value, "value")):
-        if not isinstance(t, torch.Tensor) or not (t.is_cuda and t.dtype == torch.float32 and t.device == env.device):
-            raise TypeError(f"ppo_head: {what} must be a float32 CUDA tensor on {env.device}")
-    if not (isinstance(index, torch.Tensor) and index.is_cuda and index.dtype == torch.int32 and index.dim() == 1 and index.is_contiguous() and index.device == env.device):
-        raise TypeError(f"ppo_head: index must be a contiguous int32 CUDA tensor [M] on {env.device}")
-    M = index.numel()
-    if M < 1 or out.numel() != M * N * 4 or value.numel() != M:
-        raise ValueError(f"ppo_head: out {list(out.shape)} / value {list(value.shape)} are not [M, {N}, 4] / [M] of the {M} indexed frames (M >= 1)")
-    act = batch["action"]
+    _head_checks("ppo_head", env, out, value, index, 4, clip_epsilon)
+    N, act = env.N, batch["action"]
     if not isinstance(act, torch.Tensor) or act.dim() != 4:
         raise TypeError("ppo_head: batch['action'] must be [T, B, N, 2]")
     T, B = act.shape[0], act.shape[1]
     recs = (check_record(act, (T, B, N, 2), "action"), check_record(batch["sample_log_prob"], (T, B, N), "sample_log_prob"),
             check_record(batch["advantage"], (T, B, N), "advantage"), check_record(batch["value_target"], (T, B, N), "value_target"))
-    if not 0.0 < float(clip_epsilon) < 1.0:
-        raise ValueError(f"clip_epsilon = {clip_epsilon} is not in (0, 1)")
     a = capi.PpoHeadArgs()
-    a.n_index, a.n_frames, a.index = M, T * B, index.data_ptr()
     a.action, a.sample_log_prob, a.advantage, a.value_target = (t.data_ptr() for t in recs)
     a.low[0], a.low[1], a.high[0], a.high[1] = float(low[0]), float(low[1]), float(high[0]), float(high[1])
-    a.clip_epsilon, a.entropy_coeff, a.critic_coeff = float(clip_epsilon), float(entropy_coeff), float(critic_coeff)
-    a.seed, a.counter = int(seed) & 0xFFFFFFFFFFFFFFFF, int(counter) & 0xFFFFFFFFFFFFFFFF
-    loss, result = _PpoHeadFunction.apply(env, a, (index, *recs), out.reshape(M, N, 4).contiguous(), value.reshape(M).contiguous())
-    return loss, {k: result[i] for i, k in enumerate(capi.PPO_RESULT)}
-
-
-class _PriorityPpoHeadFunction(torch.autograd.Function):
-    """``priority_ppo_head``: ``sigmaenv_ppo_head_1d`` forwards; backwards the stored ``dout`` tensors times the incoming gradient of the loss."""
-
-    @staticmethod
-    def forward(ctx, env, args, keep, out, value):
-        dev = env.device
-        M, N = out.shape[0], out.shape[1]
-        kw = dict(dtype=torch.float32, device=dev)
-        dout_a, dout_c, result = torch.empty((M, N, 2), **kw), torch.empty((M,), **kw), torch.empty((8,), **kw)
-        ws = torch.empty((capi.PPO_SUMS * ((M * N + 255) // 256),), **kw)
-        out, value = out.detach(), value.detach()
-        args.out, args.value = out.data_ptr(), value.data_ptr()
-        args.dout_actor, args.dout_critic, args.result, args.workspace = dout_a.data_ptr(), dout_c.data_ptr(), result.data_ptr(), ws.data_ptr()
-        cur = torch.cuda.current_stream(dev)
-        with torch.cuda.device(dev):  # on the env's stream after what torch's current stream holds, which then waits for it (ppo_head's discipline)
-            env.stream.wait_stream(cur)
-            rc = env.lib.ppo_head_1d(env.h, C.byref(args))
-            if rc != 0:
-                raise RuntimeError(f"sigmaenv_ppo_head_1d failed with code {rc}: {env.lib.last_error(env.h).decode()}")
-            cur.wait_stream(env.stream)
-        for t in (out, value, dout_a, dout_c, result, ws, *keep):
-            t.record_stream(env.stream)
-        ctx.save_for_backward(dout_a, dout_c)
-        ctx.mark_non_differentiable(result)
-        return (result[0] + result[1]) + result[2], result
-
-    @staticmethod
-    def backward(ctx, g, _):
-        dout_a, dout_c = ctx.saved_tensors
-        return None, None, None, dout_a * g, dout_c * g
+    return _head_launch(env, "ppo_head", a, recs, index, out, value, 4, clip_epsilon, entropy_coeff, critic_coeff, seed, counter)
 
 
 def priority_ppo_head(env, out: torch.Tensor, value: torch.Tensor, batch: dict, index: torch.Tensor, *, clip_epsilon: float, entropy_coeff: float,
@@ -392,30 +330,16 @@ def priority_ppo_head(env, out: torch.Tensor, value: torch.Tensor, batch: dict, 
     ``batch["advantage"]`` / ``batch["value_target"]`` and leaves the choice to whoever fills them.  ``(seed, counter)``: the key of the entropy sample's draw; the
     draw id is the priority head's own (``DRAW_PRIORITY_ENTROPY``), so the same ``(seed, counter)`` as the base head's shares no draw with it.  Returns
     ``(loss, info)`` as ``ppo_head`` does.  Enqueued on the env's stream, nothing waits."""
-    N = env.N
-    for t, what in ((out, "out"), (value, "value")):
-        if not isinstance(t, torch.Tensor) or not (t.is_cuda and t.dtype == torch.float32 and t.device == env.device):
-            raise TypeError(f"priority_ppo_head: {what} must be a float32 CUDA tensor on {env.device}")
-    if not (isinstance(index, torch.Tensor) and index.is_cuda and index.dtype == torch.int32 and index.dim() == 1 and index.is_contiguous() and index.device == env.device):
-        raise TypeError(f"priority_ppo_head: index must be a contiguous int32 CUDA tensor [M] on {env.device}")
-    M = index.numel()
-    if M < 1 or out.numel() != M * N * 2 or value.numel() != M:
-        raise ValueError(f"priority_ppo_head: out {list(out.shape)} / value {list(value.shape)} are not [M, {N}, 2] / [M] of the {M} indexed frames (M >= 1)")
-    sc = batch[("info", "priority", "scores")]
+    _head_checks("priority_ppo_head", env, out, value, index, 2, clip_epsilon)
+    N, sc = env.N, batch[("info", "priority", "scores")]
     if not isinstance(sc, torch.Tensor) or sc.dim() != 3:
         raise TypeError("priority_ppo_head: batch[('info', 'priority', 'scores')] must be [T, B, N]")
     T, B = sc.shape[0], sc.shape[1]
     recs = (check_record(sc, (T, B, N), "scores"), check_record(batch[("info", "priority", "sample_log_prob")], (T, B, N), "score log-probabilities"),
             check_record(batch["advantage"], (T, B, N), "advantage"), check_record(batch["value_target"], (T, B, N), "value_target"))
-    if not 0.0 < float(clip_epsilon) < 1.0:
-        raise ValueError(f"clip_epsilon = {clip_epsilon} is not in (0, 1)")
     a = capi.PpoHead1dArgs()
-    a.n_index, a.n_frames, a.index = M, T * B, index.data_ptr()
     a.scores, a.score_log_prob, a.advantage, a.value_target = (t.data_ptr() for t in recs)
-    a.clip_epsilon, a.entropy_coeff, a.critic_coeff = float(clip_epsilon), float(entropy_coeff), float(critic_coeff)
-    a.seed, a.counter = int(seed) & 0xFFFFFFFFFFFFFFFF, int(counter) & 0xFFFFFFFFFFFFFFFF
-    loss, result = _PriorityPpoHeadFunction.apply(env, a, (index, *recs), out.reshape(M, N, 2).contiguous(), value.reshape(M).contiguous())
-    return loss, {k: result[i] for i, k in enumerate(capi.PPO_RESULT)}
+    return _head_launch(env, "ppo_head_1d", a, recs, index, out, value, 2, clip_epsilon, entropy_coeff, critic_coeff, seed, counter)
 
 
 def minibatches(n_frames: int, minibatch_size: int, generator: torch.Generator | None = None, device="cuda") -> list:
@@ -493,7 +417,7 @@ class Adam:
     def step(self, max_grad_norm: float) -> torch.Tensor:
         """One optimiser step from the parameters' ``.grad``: the gradients of ALL networks clipped to ``max_grad_norm`` in one norm, Adam, and every weight form of
         every network repacked from the updated parameters -- three launches on the env's stream after everything torch's current stream holds, which then waits
-        for them (``ppo_head``'s discipline); nothing waits on the host.  The gradients are then set to ``None`` (``optim.zero_grad()``).  The networks hold the
+        for them (``SigmaEnv._on_stream``); nothing waits on the host.  The gradients are then set to ``None`` (``optim.zero_grad()``).  The networks hold the
         new weights without a ``load`` (``apply``'s stale-weight guard sees them fresh); each runs EXACT until ``resolve``; a handle of another library than the
         env's is brought up to date when it is next used.  Refusals (before any launch): a missing ``.grad``, a CPU tensor, a wrong shape, ``t + 1 < 1``, a bad
         scalar.  Returns the device result ``[total_norm, clip_coef]``."""
@@ -530,21 +454,11 @@ class Adam:
                 used += ts
         a.lr, a.beta1, a.beta2, a.eps, a.max_grad_norm, a.t = self.lr, b1, b2, self.eps, mg, t
         nf = C.c_uint64()
-        rc = env.lib.optim_workspace(env.h, C.byref(a), C.byref(nf))
-        if rc != 0:
-            raise RuntimeError(f"sigmaenv_optim_workspace failed with code {rc}: {env.lib.last_error(env.h).decode()}")
+        env._chk(env.lib.optim_workspace(env.h, C.byref(a), C.byref(nf)), "optim_workspace")
         ws = torch.empty((max(int(nf.value), 1),), dtype=torch.float32, device=dev)
         result = torch.empty((2,), dtype=torch.float32, device=dev)
         a.workspace, a.result = ws.data_ptr(), result.data_ptr()
-        cur = torch.cuda.current_stream(dev)
-        with torch.cuda.device(dev):  # on the env's stream after what torch's current stream holds (the backward pass), which then waits for it
-            env.stream.wait_stream(cur)
-            rc = env.lib.optim_step(env.h, C.byref(a))
-            if rc != 0:
-                raise RuntimeError(f"sigmaenv_optim_step failed with code {rc}: {env.lib.last_error(env.h).decode()}")
-            cur.wait_stream(env.stream)
-        for x in used + [ws, result]:
-            x.record_stream(env.stream)
+        env._on_stream("optim_step", lambda: env.lib.optim_step(env.h, C.byref(a)), used + [ws, result])  # (what the current stream holds: the backward pass)
         self.t = t
         for k, (net, module) in enumerate(self.networks):
             for p in ps[k]:
@@ -564,9 +478,7 @@ class Adam:
         env, modes = self.env, []
         for net, _ in self.networks:
             m32 = self._mlp32(net)
-            rc = env.lib.mlp32_resolve_mode(env.h, m32.handle(env.lib, env))
-            if rc != 0:
-                raise RuntimeError(f"sigmaenv_mlp32_resolve_mode failed with code {rc}: {env.lib.last_error(env.h).decode()}")
+            env._chk(env.lib.mlp32_resolve_mode(env.h, m32.handle(env.lib, env)), "mlp32_resolve_mode")
             m32.mode = m32._mode_in_force(env.lib)
             modes.append(m32.mode)
         return modes
@@ -654,8 +566,7 @@ class PrioritizedBuffer:
         h = C.c_void_p()
         with torch.cuda.device(env.device):
             rc = env.lib.prb_create(env.h, capacity, self.alpha, self.beta, self.eps, C.byref(h))
-        if rc != 0:
-            raise RuntimeError(f"sigmaenv_prb_create failed with code {rc}: {env.lib.last_error(env.h).decode()}")
+        env._chk(rc, "prb_create")
         self._h = h
 
     def close(self):
@@ -678,19 +589,6 @@ class PrioritizedBuffer:
             raise RuntimeError(f"PrioritizedBuffer.{what}: the env is closed")
         return self._h
 
-    def _call(self, what, fn, tensors):
-        """``fn()`` on the env's stream after what torch's current stream holds, which then waits for it (``ppo_head``'s discipline)."""
-        env, dev = self.env, self.env.device
-        cur = torch.cuda.current_stream(dev)
-        with torch.cuda.device(dev):
-            env.stream.wait_stream(cur)
-            rc = fn()
-            if rc != 0:
-                raise RuntimeError(f"sigmaenv_prb_{what} failed with code {rc}: {env.lib.last_error(env.h).decode()}")
-            cur.wait_stream(env.stream)
-        for t in tensors:
-            t.record_stream(env.stream)
-
     def extend(self, td_error: torch.Tensor) -> None:
         """Replaces the content (the reference extends a full buffer with ``frames_per_batch`` new frames every iteration): ``td_error`` is the ``[T, B]`` (or
         ``[F]``) tensor ``collect`` returns; ``len = T * B`` and ``q[f] = (td_error[f] + eps) ** alpha``."""
@@ -701,7 +599,7 @@ class PrioritizedBuffer:
         if not 1 <= n <= self.capacity:
             raise ValueError(f"PrioritizedBuffer.extend: {n} frames are not in [1, capacity = {self.capacity}]")
         env = self.env
-        self._call("extend", lambda: env.lib.prb_extend(env.h, h, C.c_void_p(td_error.data_ptr()), n), (td_error,))
+        env._on_stream("prb_extend", lambda: env.lib.prb_extend(env.h, h, C.c_void_p(td_error.data_ptr()), n), (td_error,))
         self.len = n
 
     def sample(self, M: int, seed: int, counter: int):
@@ -717,8 +615,8 @@ class PrioritizedBuffer:
         env = self.env
         index = torch.empty((M,), dtype=torch.int32, device=env.device)
         weight = torch.empty((M,), dtype=torch.float32, device=env.device)
-        self._call("sample", lambda: env.lib.prb_sample(env.h, h, M, int(seed) & 0xFFFFFFFFFFFFFFFF, int(counter) & 0xFFFFFFFFFFFFFFFF, C.c_void_p(index.data_ptr()),
-                                                         C.c_void_p(weight.data_ptr())), (index, weight))
+        env._on_stream("prb_sample", lambda: env.lib.prb_sample(env.h, h, M, int(seed) & 0xFFFFFFFFFFFFFFFF, int(counter) & 0xFFFFFFFFFFFFFFFF, C.c_void_p(index.data_ptr()),
+                                                                C.c_void_p(weight.data_ptr())), (index, weight))
         return index, weight
 
     def refresh(self, critic, batch: dict, index: torch.Tensor, td_gamma: float = TD_GAMMA) -> torch.Tensor:
@@ -732,9 +630,7 @@ class PrioritizedBuffer:
         env = self.env
         N, D = env.N, env.D
         W = N * (D + 1) + 1
-        if not (isinstance(index, torch.Tensor) and index.is_cuda and index.dtype == torch.int32 and index.dim() == 1 and index.is_contiguous() and index.device == env.device):
-            raise TypeError(f"PrioritizedBuffer.refresh: index must be a contiguous int32 CUDA tensor [M] on {env.device}")
-        M = index.numel()
+        M = check_index(index, env, "PrioritizedBuffer.refresh").numel()
         if M < 1:
             raise ValueError("PrioritizedBuffer.refresh: index is empty")
         if self.len < 1:
@@ -742,8 +638,7 @@ class PrioritizedBuffer:
         if not 0.0 <= float(td_gamma) <= 1.0:
             raise ValueError(f"td_gamma = {td_gamma} is not in [0, 1]")
         obs, slab = batch["observation"], batch["slab"]
-        if not isinstance(slab, torch.Tensor) or not (slab.is_cuda and slab.dtype == torch.float32 and slab.is_contiguous() and slab.dim() == 3 and slab.shape[2] == W):
-            raise TypeError(f"PrioritizedBuffer.refresh: batch['slab'] must be a contiguous float32 CUDA tensor [T, B, {W}]")
+        check_slab(slab, W, "PrioritizedBuffer.refresh: batch['slab']", "B")
         T, B = slab.shape[0], slab.shape[1]
         if T * B != self.len or B != env.B:
             raise ValueError(f"PrioritizedBuffer.refresh: the batch has {T} x {B} frames, the buffer holds {self.len} of an env of {env.B}")
@@ -757,7 +652,7 @@ class PrioritizedBuffer:
         a = capi.PrbRefreshArgs()
         a.n_index, a.index, a.state_value, a.next_state_value, a.slab, a.td_out = M, index.data_ptr(), sv.data_ptr(), nv.data_ptr(), slab.data_ptr(), td.data_ptr()
         a.td_gamma = float(td_gamma)
-        self._call("refresh", lambda: env.lib.prb_refresh(env.h, h, C.byref(a)), (index, sv, nv, slab, td))
+        env._on_stream("prb_refresh", lambda: env.lib.prb_refresh(env.h, h, C.byref(a)), (index, sv, nv, slab, td))
         return td
 
     def _get(self, what, n, dtype=torch.float32):
@@ -767,8 +662,7 @@ class PrioritizedBuffer:
         with torch.cuda.device(env.device):
             env.stream.wait_stream(torch.cuda.current_stream(env.device))
             rc = env.lib.prb_get(env.h, h, what, C.c_void_p(out.data_ptr()))
-        if rc != 0:
-            raise RuntimeError(f"sigmaenv_prb_get failed with code {rc}: {env.lib.last_error(env.h).decode()}")
+        env._chk(rc, "prb_get")
         return out[: int(n)]
 
     def priorities(self) -> torch.Tensor:
@@ -780,6 +674,19 @@ class PrioritizedBuffer:
         ks = range(1, len(self.level_sizes))
         return {"sum": [self._get(capi.PRB_LEVEL_SUM + k, self.level_sizes[k]) for k in ks], "min": [self._get(capi.PRB_LEVEL_MIN + k, self.level_sizes[k]) for k in ks],
                 "total": self._get(capi.PRB_TOTAL, 1)[0], "q_min": self._get(capi.PRB_QMIN, 1)[0]}
+
+
+def _optim_step(env, optim, parameters, networks, max_grad_norm: float) -> None:
+    """One optimiser step of ``update`` from the ``.grad`` of ``parameters``: a ``learn.Adam`` takes the device route, ``step(max_grad_norm)``; a torch optimiser
+    ``clip_grad_norm_`` -> ``step`` -> ``zero_grad``, and every ``(network, module)`` of ``networks`` then ``load``s its module's new weights."""
+    if isinstance(optim, Adam):
+        optim.step(max_grad_norm)
+        return
+    torch.nn.utils.clip_grad_norm_(parameters, max_grad_norm)
+    optim.step()
+    optim.zero_grad()
+    for net, module in networks:
+        net.load(env, module)
 
 
 def update(env, actor, critic, actor_module, critic_module, optim, batch: dict, params=None, *, num_epochs: int | None = None, minibatch_size: int | None = None,
@@ -834,7 +741,6 @@ def update(env, actor, critic, actor_module, critic_module, optim, batch: dict, 
             raise ValueError(f"update(): the buffer holds {buffer.len} frames of its env, the batch {frames} of this one (buffer.extend(batch['td_error']) first)")
     low, high = actor._keep[-2], actor._keep[-1]
     pars = list(actor_module.parameters()) + list(critic_module.parameters())
-    device_route = isinstance(optim, Adam)
     base = batch.get(BASE_OBS)
     Dc = D if base is None else check_record(base, (T, B, N, base.shape[-1]), "base_observation").shape[-1]
     pad = None if base is None else (D, Dc)
@@ -846,7 +752,6 @@ def update(env, actor, critic, actor_module, critic_module, optim, batch: dict, 
         if base is None or PRIORITY + ("scores",) not in batch:
             raise ValueError("update(): priority= needs a batch of collect(wrapper='prioritized', priority=PriorityNet, priority_critic=...)")
         ppars = list(pmodule.parameters()) + list(pcritic_module.parameters())
-        pdevice = isinstance(poptim, Adam)
     infos, k = [], 0
     for _ in range(num_epochs):
         for index in ([None] * (frames // mb) if buffer is not None else minibatches(frames, mb, generator, env.device)[: frames // mb]):
@@ -857,36 +762,21 @@ def update(env, actor, critic, actor_module, critic_module, optim, batch: dict, 
             loss, info = ppo_head(env, out, value, batch, index, low=low, high=high, clip_epsilon=clip_epsilon, entropy_coeff=entropy_coeff, critic_coeff=critic_coeff,
                                   seed=seed, counter=counter0 + k)
             loss.backward()
-            if device_route:
-                optim.step(max_grad_norm)
-            else:
-                torch.nn.utils.clip_grad_norm_(pars, max_grad_norm)
-                optim.step()
-                optim.zero_grad()
-                actor.load(env, actor_module)
-                critic.load(env, critic_module)
+            _optim_step(env, optim, pars, [(actor, actor_module), (critic, critic_module)], max_grad_norm)
             if priority is not None:
                 pout = pnet.apply(env, rows=(obs, 0, N, D, frames, N * D), index=index, check_index=False)
                 pvalue = pcritic.apply(env, obs, index=index, check_index=False)
                 ploss, info["priority"] = priority_ppo_head(env, pout, pvalue, batch, index, clip_epsilon=clip_epsilon, entropy_coeff=entropy_coeff, critic_coeff=critic_coeff,
                                                             seed=seed, counter=counter0 + k)
                 ploss.backward()
-                if pdevice:
-                    poptim.step(max_grad_norm)
-                else:
-                    torch.nn.utils.clip_grad_norm_(ppars, max_grad_norm)
-                    poptim.step()
-                    poptim.zero_grad()
-                    pnet.load(env, pmodule)
-                    pcritic.load(env, pcritic_module)
+                _optim_step(env, poptim, ppars, [(pnet, pmodule), (pcritic, pcritic_module)], max_grad_norm)
             if buffer is not None:
                 info["_weight"], info["td_error"] = weight, buffer.refresh(critic, batch, index, td_gamma)
             infos.append(info)
             k += 1
-    if device_route and k:
-        optim.resolve()
-    if priority is not None and pdevice and k:
-        poptim.resolve()
+    for o in (optim,) + ((poptim,) if priority is not None else ()):
+        if isinstance(o, Adam) and k:
+            o.resolve()
     return infos
 
 

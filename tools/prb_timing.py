@@ -101,7 +101,7 @@ def buffer_routes(env, critic, F):
         state["k"] += 1
         a = capi.PrbRefreshArgs()
         a.n_index, a.index, a.state_value, a.next_state_value, a.slab, a.td_out, a.td_gamma = M, idx.data_ptr(), v.data_ptr(), vn.data_ptr(), slab.data_ptr(), td.data_ptr(), GAMMA
-        buf._call("refresh", lambda: env.lib.prb_refresh(env.h, buf._h, C.byref(a)), (idx,))
+        env._on_stream("prb_refresh", lambda: env.lib.prb_refresh(env.h, buf._h, C.byref(a)), (idx,))
 
     index = buf.sample(M, 1, 0)[0]
 
