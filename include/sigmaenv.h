@@ -1189,6 +1189,63 @@ int sigmaenv_state_layout(sigmaenv_t* h, sigmaenv_state_header_t* out);
 int sigmaenv_state_save(sigmaenv_t* h, void* dev_blob, size_t bytes);
 int sigmaenv_state_restore(sigmaenv_t* h, const sigmaenv_state_header_t* hdr, const void* dev_blob, size_t bytes, const uint8_t* env_mask);
 
+/* ---- Frames of selected envs, drawn on the device (sigmarl_amd/csrc/sigmaenv_render.inc; the picture: sigmaenv_render.h) ---------------------------------------------
+ * What the reference shows through env.render / extra_render and save_video (sigmarl/scenarios/road_traffic.py:1637-1800; is_save_simulation_video,
+ * is_real_time_rendering, is_visualize_short_term_path, is_visualize_lane_boundary): a top-down view of map, short-term reference paths and vehicles.  The reference's
+ * renderer is a pyglet scene graph; it supplies the list of things drawn, sigmaenv_render.h specifies the pixels (view, fp32 predicates, layers, sample mean, palette,
+ * tile walk), and a frame is held to it bit for bit.  A frame of env b reads SIGMAENV_BUF_VERTICES[b,i,0:4], SIGMAENV_BUF_SHORT_TERM[b,i], SIGMAENV_BUF_STATE[b,i,0:2],
+ * SIGMAENV_BUF_COL_AGENTS[b,i,:], byte 0 of SIGMAENV_BUF_COL_FLAGS[b,i,:] and the map table's left / right polylines -- as the buffers stand when the launch runs.
+ * The renderer holds no env state: nothing of it is part of sigmaenv_state_layout, and an attachment is a caller's setting like an attached evaluator.
+ *
+ * sigmaenv_render_create   <- the scene set-up of extra_render, road_traffic.py:1637-1659 (the geoms of the lane boundaries :1700-1730 are drawn ONCE here: the background
+ *                          kernel rasterises layers 0 and 1 into a device coverage image u16 [H,W] and the map's resolved colours u8 [H,W,3]; the map never visits the
+ *                          host as an image).  args: the view (scale px / m, the world point (x0, y1) of the top-left corner), height, width (a multiple of 4), samples
+ *                          per axis (1, 2, 4), the half-widths in pixels, flags, the HOST palette u8 [3 + N, 3] (background, boundary, collision, agents), the HOST
+ *                          selection i32 [n_sel] (duplicates are legal; an entry outside [0, B) is refused) and ring_frames (0: no ring).  Allocates and waits for the
+ *                          two small copies: do not call inside a stream capture.
+ * sigmaenv_render_frame    <- one env.render() call, road_traffic.py:1660-1800 (short-term paths :1660-1698, vehicles and heading :560-600): ONE launch on the handle's
+ *                          stream, grid = tiles x selected envs, into out (DEVICE u8 [n_sel, H, W, 3], 16-byte aligned) or, out NULL, into the next ring slot.
+ *                          src NULL: the handle's buffers; otherwise each non-null pointer of src replaces the handle's buffer of that name, in the handle's own
+ *                          layout, 4-byte aligned (the rules of sigmaenv_eval_src_t): how recorded trajectories are drawn after the fact.
+ * sigmaenv_render_attach   (h, r, every) / (h, NULL, 0) <- save_video's frame list, one env.render() per step of the rollout: while a renderer is attached, every
+ *                          step of sigmaenv_rollout* (every wrapper, and the CBF chain) is taken apart exactly as for an evaluator and the frame of every `every`-th
+ *                          step since the attachment goes to the ring: sigmaenv_step -> (sigmaenv_eval_accumulate) -> frame -> (sigmaenv_isb_record ->
+ *                          sigmaenv_isb_restart) -> sigmaenv_auto_reset -> (sigmaenv_isb_settle).  The frame shows the step's outcome BEFORE the re-placements clear
+ *                          it; end state and records are the fused rollout's, bit for bit.  Needs a ring.  Direct calls of sigmaenv_step_autoreset* are NOT affected.
+ * sigmaenv_render_get      the ring's DEVICE base (NULL without one), the frames drawn so far as the host counts them (into the ring or a caller's tensor), those of
+ *                          them drawn into the ring (slot = count mod ring_frames) and the ring slot of the newest ring frame (-1 before the first); any of the
+ *                          four destinations may be NULL.  No wait.
+ * sigmaenv_render_destroy  waits for the handle's stream, detaches, frees.  A renderer whose handle was destroyed first can only be destroyed.
+ * Refused with SIGMAENV_EINVAL and sigmaenv_last_error set, before any launch: a null handle (no message), a null renderer, a renderer of another handle; at create a
+ * width that is no multiple of 4, samples outside {1, 2, 4}, a selection entry outside [0, B), a non-finite view, unknown flags; an override that is not 4-byte
+ * aligned, an out that is not 16-byte aligned, no out and no ring; attaching with every < 1 or without a ring. */
+typedef struct sigmaenv_render sigmaenv_render_t;
+#define SIGMAENV_RENDER_SHORT_TERM 1 /* flags: draw layer 2, the short-term reference paths (is_visualize_short_term_path) */
+typedef struct sigmaenv_render_args {
+  float scale, x0, y1;             /* the view: px = (x - x0) * scale, py = (y1 - y) * scale */
+  float h_boundary, h_path;        /* half-widths in pixels: lane boundaries; short-term paths and heading marks */
+  int32_t height, width, samples;  /* width a multiple of 4; samples per axis 1, 2 or 4 */
+  int32_t flags;                   /* SIGMAENV_RENDER_* */
+  int32_t n_sel, ring_frames;
+  int32_t reserved0;               /* zero */
+  const uint8_t* palette;          /* HOST u8 [3 + n_agents, 3] */
+  const int32_t* selection;        /* HOST i32 [n_sel] */
+  int32_t reserved[4];             /* zero */
+} sigmaenv_render_args_t;
+typedef struct sigmaenv_render_src {
+  const float* vertices;           /* optional device f32 [B, N, 5, 2] */
+  const float* short_term;         /* optional device f32 [B, N, n_points_short_term, 2] */
+  const float* state;              /* optional device f32 [B, N, 8] */
+  const uint8_t* col_agents;       /* optional device u8 [B, N, N] */
+  const uint8_t* col_flags;        /* optional device u8 [B, N, 4] */
+  int32_t reserved[4];             /* zero */
+} sigmaenv_render_src_t;
+int sigmaenv_render_create(sigmaenv_t* h, const sigmaenv_render_args_t* args, sigmaenv_render_t** out);
+void sigmaenv_render_destroy(sigmaenv_render_t* r);
+int sigmaenv_render_frame(sigmaenv_t* h, sigmaenv_render_t* r, const sigmaenv_render_src_t* src, uint8_t* out);
+int sigmaenv_render_attach(sigmaenv_t* h, sigmaenv_render_t* r, int32_t every);
+int sigmaenv_render_get(sigmaenv_t* h, sigmaenv_render_t* r, void** ring, uint64_t* frames, uint64_t* ring_drawn, int32_t* newest_slot);
+
 #ifdef __cplusplus
 }
 #endif

@@ -226,6 +226,26 @@ ISB_CHUNK, ISB_MAX_CAPACITY, ISB_MAX_STEPS_STORED = 1024, 65536, 1024  # sigmaen
 ISB_DRAW_RECORD, ISB_DRAW_USE, ISB_DRAW_INDEX = 5100, 5101, 5102  # DRAW_ISB_* of the draw table (sigmaenv_dist.h)
 
 
+class RenderArgs(C.Structure):
+    """``sigmaenv_render_args_t`` (sigmaenv_render_create): the view, the image, the half-widths in pixels, the flags, the HOST palette ``u8 [3 + N, 3]`` and the HOST
+    selection ``i32 [n_sel]``, the ring's capacity in frames."""
+
+    _fields_ = [("scale", C.c_float), ("x0", C.c_float), ("y1", C.c_float), ("h_boundary", C.c_float), ("h_path", C.c_float), ("height", C.c_int32), ("width", C.c_int32),
+                ("samples", C.c_int32), ("flags", C.c_int32), ("n_sel", C.c_int32), ("ring_frames", C.c_int32), ("reserved0", C.c_int32), ("palette", C.c_void_p),
+                ("selection", C.c_void_p), ("reserved", C.c_int32 * 4)]
+
+
+class RenderSrc(C.Structure):
+    """``sigmaenv_render_src_t`` (sigmaenv_render_frame): optional device pointers that replace the handle's buffers of the same name, in the handle's layouts."""
+
+    _fields_ = [("vertices", C.c_void_p), ("short_term", C.c_void_p), ("state", C.c_void_p), ("col_agents", C.c_void_p), ("col_flags", C.c_void_p), ("reserved", C.c_int32 * 4)]
+
+
+RENDER_SHORT_TERM = 1  # SIGMAENV_RENDER_SHORT_TERM
+RND_TILE_W, RND_TILE_H, RND_LIST_CAP, RND_MAX_DIM = 64, 16, 48, 16384  # sigmaenv_render.h
+RND_PAL_BACKGROUND, RND_PAL_BOUNDARY, RND_PAL_COLLISION, RND_PAL_AGENT0 = range(4)  # rows of the palette
+
+
 STATE_MAGIC, STATE_VERSION = 0x50414E53, 1  # SIGMAENV_STATE_MAGIC ("SNAP"), SIGMAENV_STATE_VERSION
 STATE_CBF_NONE, STATE_CBF_ATTACHED, STATE_CBF_GROUPED = 0, 1, 2  # the header's ``cbf`` quantity (sigmaenv_snapshot.h)
 
@@ -436,6 +456,11 @@ _PRODUCT_ONLY = {
     "state_layout": (C.c_int, [C.c_void_p, C.POINTER(StateHeader)]),
     "state_save": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
     "state_restore": (C.c_int, [C.c_void_p, C.POINTER(StateHeader), C.c_void_p, C.c_size_t, C.c_void_p]),
+    "render_create": (C.c_int, [C.c_void_p, C.POINTER(RenderArgs), C.POINTER(C.c_void_p)]),
+    "render_destroy": (None, [C.c_void_p]),
+    "render_frame": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(RenderSrc), C.c_void_p]),
+    "render_attach": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32]),
+    "render_get": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_int32)]),
 }
 
 

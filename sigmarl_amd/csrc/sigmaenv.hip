@@ -1821,6 +1821,7 @@ __global__ void __launch_bounds__(512) sigmaenv_auto_reset_kernel(sigmaenv_confi
 // =====================================================================================================================
 struct sigmaenv_eval;  // sigmaenv_eval.inc
 struct sigmaenv_isb;   // sigmaenv_isb.inc
+struct sigmaenv_render;  // sigmaenv_render.inc
 struct sigmaenv {
   sigmaenv_config_t cfg;
   int device = 0;
@@ -1879,6 +1880,10 @@ struct sigmaenv {
   std::vector<sigmaenv_eval*> evals;       // the evaluators created on this handle (they outlive it only as orphans: sigmaenv_destroy)
   sigmaenv_isb* isb_attached = nullptr;    // sigmaenv_isb_attach: the rollouts step as step -> record -> restart -> auto_reset -> settle while set (sigmaenv_isb.inc)
   std::vector<sigmaenv_isb*> isbs;         // the initial-state banks created on this handle (orphans after sigmaenv_destroy, like the evaluators)
+  sigmaenv_render* render_attached = nullptr;  // sigmaenv_render_attach: the rollouts step as step -> (accumulate) -> frame of every render_every-th step -> .. while set
+  int32_t render_every = 1;
+  uint64_t render_steps = 0;                   // steps of attached rollouts since the attachment
+  std::vector<sigmaenv_render*> renders;       // the renderers created on this handle (orphans after sigmaenv_destroy, like the evaluators)
   std::string err;
 };
 
@@ -1952,6 +1957,7 @@ extern "C" const char* sigmaenv_last_error(const sigmaenv_t* h) { return h ? h->
 
 static void eval_orphan(sigmaenv* h);  // sigmaenv_eval.inc: the handle's evaluators lose their owner
 static void isb_orphan(sigmaenv* h);   // sigmaenv_isb.inc: and its initial-state banks
+static void render_orphan(sigmaenv* h);  // sigmaenv_render.inc: and its renderers
 
 extern "C" void sigmaenv_destroy(sigmaenv_t* h) {
   if (!h) return;
@@ -1959,6 +1965,7 @@ extern "C" void sigmaenv_destroy(sigmaenv_t* h) {
   (void)hipStreamSynchronize(h->stream);
   eval_orphan(h);
   isb_orphan(h);
+  render_orphan(h);
   for (void* p : h->allocs) (void)hipFree(p);
   for (auto& tm : h->timers)
     for (auto& ev : tm.pool) { (void)hipEventDestroy(ev.first); (void)hipEventDestroy(ev.second); }
@@ -2562,11 +2569,14 @@ extern "C" int sigmaenv_cbf_qp(sigmaenv_t* h, const float* actions, float* actio
 // sigmaenv_eval_accumulate -> sigmaenv_auto_reset -- the same action, record target and (seed, counter) -- so that the evaluator sees the step's outcome before the
 // re-placements clear it; the header promises the same end state and record as the fused launch, bit for bit.  With an initial-state bank attached
 // (sigmaenv_isb_attach) the same split carries the bank's three calls: step -> (accumulate) -> sigmaenv_isb_record -> sigmaenv_isb_restart -> sigmaenv_auto_reset ->
-// sigmaenv_isb_settle; a rollout without device-side resets (path_count 0) only records.  Without an attachment, and for every other caller, nothing changes.
+// sigmaenv_isb_settle; a rollout without device-side resets (path_count 0) only records.  With a renderer attached (sigmaenv_render_attach) the same split draws the
+// frame of every `every`-th step after the step and the evaluator's frame and BEFORE the bank and the resets: step -> (accumulate) -> render -> (record -> restart) ->
+// auto_reset -> (settle), so a collision is on the frame before the re-placement clears it.  Without an attachment, and for every other caller, nothing changes.
 static int eval_accumulate_impl(sigmaenv* h, sigmaenv_eval* ev, const sigmaenv_eval_src_t* src, const sigmaenv_eval_study_src_t* ssrc);  // sigmaenv_eval.inc
 extern "C" int sigmaenv_isb_record(sigmaenv_t* h, sigmaenv_isb* k, uint64_t seed, uint64_t counter);  // sigmaenv_isb.inc
 extern "C" int sigmaenv_isb_restart(sigmaenv_t* h, sigmaenv_isb* k, uint64_t seed, uint64_t counter);
 extern "C" int sigmaenv_isb_settle(sigmaenv_t* h, sigmaenv_isb* k);
+static int render_attached_step(sigmaenv* h);  // sigmaenv_render.inc: one step of an attached rollout is over
 static bool eval_nominal_from_cbf(const sigmaenv* h);  // sigmaenv_eval.inc: does the chain run the CBF-QP (and SIGMAENV_BUF_CBF_NOMINAL hold the nominal action)?
 static int launch_cbf_then_step(sigmaenv* h, StepLaunch l, bool for_rollout = false) {
   if (!h || !l.actions) return SIGMAENV_EINVAL;
@@ -2578,13 +2588,14 @@ static int launch_cbf_then_step(sigmaenv* h, StepLaunch l, bool for_rollout = fa
     if (rc) return rc;
     if (h->cbf_cfg.is_apply_cbf_action || h->cbf_cfg.is_grouping) l.actions = (const float*)h->cbf_safe;
   }
-  if (for_rollout && (h->eval_attached || h->isb_attached)) {
+  if (for_rollout && (h->eval_attached || h->isb_attached || h->render_attached)) {
     int rc = launch_step(h, {l.actions, l.slab, 0, 0, 0, 0});  // sigmaenv_step
     if (rc) return rc;
     if (h->eval_attached) {
       rc = eval_accumulate_impl(h, h->eval_attached, nullptr, nullptr);  // (a study evaluator takes a study frame: sigmaenv_eval_accumulate_study with no override)
       if (rc) return rc;
     }
+    if (h->render_attached && (rc = render_attached_step(h)) != 0) return rc;
     if (h->isb_attached && (rc = sigmaenv_isb_record(h, h->isb_attached, l.seed, l.counter)) != 0) return rc;
     if (l.path_count == 0) return SIGMAENV_OK;
     if (h->isb_attached && (rc = sigmaenv_isb_restart(h, h->isb_attached, l.seed, l.counter)) != 0) return rc;
@@ -2777,3 +2788,5 @@ extern "C" int sigmaenv_trig_selftest(sigmaenv_t* h, int32_t kind, int32_t n, co
 #include "sigmaenv_cbf.inc"
 #include "sigmaenv_snapshot.h"
 #include "sigmaenv_snapshot.inc"
+#include "sigmaenv_render.h"
+#include "sigmaenv_render.inc"

@@ -238,7 +238,7 @@ def evaluation_parameters(p, n_agents: int | None = None, simulation_steps: int 
 
 
 def evaluate(env, actor, params=None, n_steps: int | None = None, seed: int = 0, counter0: int = 0, deterministic: bool = True, trace: bool = False, study: bool = False,
-             reset=None, **rollout_kw) -> dict:
+             reset=None, render=None, render_every: int = 1, **rollout_kw) -> dict:
     """The reference's evaluation rollout on the device.  ``T = n_steps or params.max_steps - 1`` frames (``params`` defaults to ``env.parameters``): in this order
     ``env.reset_random(seed)`` -- its draws keyed by the counter ``counter0 + T - 1``, the first one the rollout's steps ``counter0 .. counter0 + T - 2`` do not use, so
     that the result is a function of the arguments alone --, ``Evaluator.reset()``, ``accumulate()`` of the state after the initial reset, ``actor.rollout`` of ``T - 1`` steps with the evaluator
@@ -252,7 +252,10 @@ def evaluate(env, actor, params=None, n_steps: int | None = None, seed: int = 0,
     the caller's records (``rollout_kw`` less ``slab=``, ``actions=`` ..), keyed ``counter0 + T`` (``counter0 + T - 1`` is the reset's) -- the last step of the
     reference's ``rollout(max_steps - 1)``, which counts for ``num_task_tries`` / ``task_success_times`` but not for ``out_td``.  The result also holds ``study`` =
     ``finish_study()``'s dict and ``study_accumulators`` (host) for ``study_summary``.  Frames, records and the four metrics are those of ``study=False``, bit for
-    bit; the env ends one step further."""
+    bit; the env ends one step further.
+
+    ``render``: a ``render.Renderer`` of this env with a ring; the rollout of the ``T - 1`` steps runs with it attached as well, so every ``render_every``-th of those
+    steps is drawn into its ring after the evaluator's frame and before the resets (``renderer.video()`` afterwards).  The metrics do not change."""
     params = params if params is not None else env.parameters
     T = int(n_steps) if n_steps else int(params.max_steps) - 1
     if T < 1:
@@ -271,7 +274,7 @@ def evaluate(env, actor, params=None, n_steps: int | None = None, seed: int = 0,
         else:
             ev.accumulate()
         if T > 1:
-            with ev.attached():
+            with ev.attached(), (render.attached(render_every) if render is not None else contextlib.nullcontext()):
                 actor.rollout(env, T - 1, seed=seed, counter0=counter0, deterministic=deterministic, **rollout_kw)
         out = ev.finish()
         if study:

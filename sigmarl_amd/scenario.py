@@ -283,7 +283,8 @@ class WorldCustom(_WorldBase):
 
 
 class ScenarioRoadTraffic(BaseScenario):
-    """Drop-in for ``sigmarl.scenarios.road_traffic.ScenarioRoadTraffic`` (callbacks :104-1635; rendering is out of scope)."""
+    """Drop-in for ``sigmarl.scenarios.road_traffic.ScenarioRoadTraffic`` (callbacks :104-1635).  The scene of ``extra_render`` (:1637-1800) is drawn on the device by
+    ``sigmarl_amd.render.Renderer`` beside a ``SigmaEnv``, not through this surface."""
 
     def make_world(self, batch_dim: int, device, **kwargs):
         if getattr(getattr(self, "parameters", None), "is_challenging_initial_state_buffer", False):
