@@ -102,6 +102,11 @@ typedef struct sigmaenv_config {
   float threshold_near_boundary_low, threshold_near_boundary_high;
   float threshold_near_other_agents_low, threshold_near_other_agents_high;
   float ttc_low, ttc_high;
+  /* Each low / high pair above feeds decreasing_fcn(type="linear") (helper_scenario.py:960-996): 1 - (clamp(x, low, high) - low) / (high - low).
+   * DEGENERATE pair, high == low: the reference divides 0 by 0 there, and so does the library -- the term is NaN for EVERY entry, the proximity
+   * channel of SIGMAENV_BUF_REWARD_INFO is NaN, and the step reward, clamped with fmin / fmax (which drop a NaN operand), is -1 for every agent;
+   * states, distances and observations are unaffected.  Device and oracle agree word for word (tests/test_constants_host.py,
+   * tests/test_gpu_constants.py).  Callers that sweep the thresholds must keep high > low. */
   float penalty_deviate_from_cbf_vel, penalty_deviate_from_cbf_steer; /* road_traffic.py:238-243 (-5/100 each); SIGMAENV_REW_CBF_QP */
   int32_t is_apply_mask;        /* Parameters.is_apply_mask: observed neighbours at or beyond distance_mask_agents are masked (vertices and
                                  * distance := 1, velocity := 0; observation_provider_rt.py:638-749).  The distance criterion is the only live

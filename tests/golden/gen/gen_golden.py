@@ -35,6 +35,10 @@ refshim.install()
 
 from sigmarl.helper_common import Parameters  # noqa: E402
 
+sys.path.insert(0, os.path.abspath(os.path.join(HERE, "..", "..", "..")))
+sys.path.insert(0, os.path.abspath(os.path.join(HERE, "..", "..")))
+from perturbed_constants import AGENTS as PERTURBED_AGENTS, PARAMETERS as PERTURBED_PARAMETERS  # noqa: E402  (tests/perturbed_constants.py: the ONE perturbed set)
+
 OUT = os.path.abspath(os.path.join(HERE, ".."))
 
 REWARD_FIELDS = [
@@ -179,7 +183,14 @@ def injected_start(scenario_type, n_agents, first_point=3, stride=3):
     return idx, st
 
 
-def run_traj(name, T, B, seed, mode_pattern, no_reset=False, hook=None, inject=None, **pkw):
+def run_traj(name, T, B, seed, mode_pattern, no_reset=False, hook=None, inject=None, agents=None, **pkw):
+    if agents:
+        # vehicle constants away from the defaults: the reference reads sigmarl.constants.AGENTS[...] at run time (road_traffic.py, helper_training.py,
+        # cbf_qp.py, world_state_rt.py, observation_provider_rt.py), so the dict is updated IN PLACE, in this process only (every fixture has its own
+        # interpreter), before the scenario is constructed.  What the reference derived from it at import (constants.THRESHOLD) only feeds its own reset sampler.
+        from sigmarl.constants import AGENTS as REF_AGENTS
+
+        REF_AGENTS.update(agents)
     torch.manual_seed(seed)
     np.random.seed(seed)
     import random as _random
@@ -264,6 +275,9 @@ def run_traj(name, T, B, seed, mode_pattern, no_reset=False, hook=None, inject=N
         shp = events[0][k].shape if ne else ((N, 2) if k in ("pos", "vel") else (N,))
         out["ev_" + k] = np.stack([e[k] for e in events], axis=0) if ne else np.zeros((0,) + shp, np.float32)
     meta = dict(kw)
+    over = dict(agents=dict(agents or {}), parameters={k: pkw[k] for k in PERTURBED_PARAMETERS if k in pkw})
+    if over["agents"] or over["parameters"]:  # the overrides that were applied: tests/traj_replay.py rebuilds the configuration from them
+        meta["overrides"] = over
     meta.update(dict(
         n_agents=N, T=T, B=B, seed=seed, dt=p.dt, no_reset=bool(no_reset), rew_method=p.rew_method, scenario_type=p.scenario_type,
         is_use_mtv_distance=p.is_use_mtv_distance,
@@ -760,6 +774,21 @@ TRAJS = {
     # "clf" nominal controller (cbf_qp.py:2616-2628): the margins are evaluated at a P controller's action instead of the policy's
     "onramp4_cbf_clf": dict(T=24, B=3, seed=23, mode_pattern=[1, 0, 1], hook="cbf", n_agents=4, scenario_type="on_ramp_1", dt=0.05,
                             is_use_mtv_distance=False, rew_method="cbf", is_using_cbf_training=True, is_solve_qp=False, nom_controller_type="clf"),
+    # the constants away from their defaults (tests/perturbed_constants.py): sigmarl.constants.AGENTS patched in place, the Parameters-exposed rewards and
+    # thresholds passed on.  NOT reachable this way, hence at the reference's values here: reward_reach_goal and the collision penalties (+-100 / r_p_normalizer),
+    # the CBF deviation penalties, distance_mask_agents (5 * length: moves with length only), the mtv proximity thresholds (0 and length)
+    # (3 agents on the on-ramp, 4 in testing mode on the intersection: with the longer vehicle the reference's unbounded rejection sampler does not return for
+    # more training-mode starts there.  The mtv fixture sees no agent collision: under mtv two agents collide only at distance exactly 0, as in every mtv fixture above)
+    "pert_onramp3_c2c": dict(T=40, B=3, seed=88, mode_pattern=[1, 1, 0], agents=PERTURBED_AGENTS, n_agents=3, scenario_type="on_ramp_1", dt=0.1,
+                             is_use_mtv_distance=False, rew_method="distance_sparse", **PERTURBED_PARAMETERS),
+    "pert_cpm8_ttc": dict(T=40, B=3, seed=78, mode_pattern=[1, 1, 0], agents=PERTURBED_AGENTS, n_agents=8, scenario_type="cpm_entire", dt=0.1,
+                          is_use_mtv_distance=False, rew_method="ttc", **PERTURBED_PARAMETERS),
+    "pert_onramp6_mtv": dict(T=40, B=3, seed=91, mode_pattern=[1, 1, 0], agents=PERTURBED_AGENTS, n_agents=6, scenario_type="on_ramp_1", dt=0.1,
+                             is_use_mtv_distance=True, rew_method="distance", is_apply_mask=True, **PERTURBED_PARAMETERS),
+    "pert_intersection4_testing": dict(T=40, B=3, seed=64, mode_pattern=[1, 0, 1], agents=PERTURBED_AGENTS, n_agents=4, scenario_type="intersection_1", dt=0.1,
+                                       is_use_mtv_distance=False, rew_method="distance", is_testing_mode=True, max_steps=24, **PERTURBED_PARAMETERS),
+    "pert_onramp3_cbf": dict(T=40, B=3, seed=93, mode_pattern=[1, 1, 0], hook="cbf", agents=PERTURBED_AGENTS, n_agents=3, scenario_type="on_ramp_1", dt=0.1,
+                             is_use_mtv_distance=False, rew_method="cbf", is_using_cbf_training=True, is_solve_qp=False, **PERTURBED_PARAMETERS),
 }
 
 def gen_initial_reset():

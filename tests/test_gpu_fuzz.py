@@ -47,6 +47,22 @@ def test_fuzz_parity_32_configurations_with_random_tilings():
     assert multi >= 8
 
 
+def test_fuzz_parity_16_configurations_with_random_reward_constants():
+    """The same machinery with the Parameters-exposed reward constants (reward_progress, both near penalties, all six thresholds) drawn by a generator of their own
+    in a third of the cases: the lower thresholds non-zero, no two fields equal.  The same assertions."""
+    import fuzz_parity as fp
+
+    rng, const_rng = np.random.default_rng(20261021), np.random.default_rng(21102026)
+    steps = diff = drawn = 0
+    for k in range(16):
+        tag, n, d = fp.one_case(rng, k, const_rng=const_rng)
+        steps += n
+        diff += d
+        drawn += "ttc_low" in tag
+        assert d == 0, f"{d} differing non-observation fp32 words in {tag}"
+    assert steps > 12_000 and diff == 0 and drawn >= 2  # (a quarter of the cases and of the bound of the 64-configuration run)
+
+
 def _run_cbf(seed, n_cases, cpm_agents, forced=()):
     import fuzz_cbf as fc
 

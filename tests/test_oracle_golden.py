@@ -136,6 +136,34 @@ def test_path_table_padding_matches_reference(fn):
 @pytest.mark.parametrize("name", tr.TRAJ_NAMES)
 def test_trajectory(name):
     """End-to-end: every hot-path tensor after every step of a reference rollout, incl. replayed resets."""
+    _replay_trajectory(name)
+
+
+@pytest.mark.parametrize("name", tr.TRAJ_NAMES_PERTURBED)
+def test_trajectory_perturbed_constants(name):
+    """The same replay, at the same tolerances, of reference rollouts at the perturbed constants (tests/perturbed_constants.py): l_f != l_r, max_speed = 1.3,
+    asymmetric acceleration / steering-rate bounds, another vehicle size and steering limit, two different near penalties, three different non-zero lower
+    thresholds, non-default upper ones.  A swapped pair inside the oracle, invisible at the defaults, fails here.
+    NOT pinned to the reference by these fixtures -- the reference hard-codes them, so they are held by the device-vs-oracle tests and the swap check
+    (test_constants_host.py, test_gpu_constants.py) only: reward_reach_goal, penalty_collide_with_agents / _boundaries (+-100 / r_p_normalizer),
+    penalty_deviate_from_cbf_vel / _steer (-5 / r_p_normalizer, and the QP is not solved here), distance_mask_agents as a value of its own (5 * length: it moves
+    with length), mtv proximity thresholds other than the reference's 0 and length (that high follows the patched length IS pinned, by pert_onramp6_mtv)."""
+    meta = _replay_trajectory(name)
+    assert meta["overrides"]["agents"] and meta["overrides"]["parameters"]
+    # the fixture exercises what it claims: collisions of both kinds, finished envs, and on maps with entries / exits an agent that left
+    assert meta["n_col_lane"] > 0 and meta["n_done"] > 0, meta
+    if meta["is_use_mtv_distance"]:
+        # under mtv two agents collide only at distance exactly 0 (road_traffic.py:394-396): no mtv fixture, perturbed or not, sees one.  What this fixture pins to
+        # the reference instead: the mtv proximity threshold follows the patched length
+        cfg, _ = tr.config_from_meta(meta)
+        assert cfg.threshold_near_other_agents_high == np.float32(meta["overrides"]["agents"]["length"]) == np.float32(meta["thresholds"]["near_other_agents_high"])
+    else:
+        assert meta["n_col_agents"] > 0, meta
+    if meta["scenario_type"] != "cpm_entire":
+        assert meta["n_exit"] > 0, meta
+
+
+def _replay_trajectory(name):
     z, meta = tr.load_fixture(name)
     cfg, mp = tr.config_from_meta(meta)
     env = ob.OracleEnv(cfg, mp)
@@ -148,6 +176,7 @@ def test_trajectory(name):
     for key, err in rep.max_abs.items():
         tol = MTV_TOL if (meta["is_use_mtv_distance"] and key in ("dist_agents", "obs", "reward", "rew_total", "rew_near_other_agents")) else FTOL
         assert err <= tol, (key, err, str(rep))
+    return meta
 
 
 def _cbf_fixture():

@@ -10,6 +10,7 @@ import os
 
 import numpy as np
 
+import perturbed_constants as pc
 from sigmarl_amd import capi
 from sigmarl_amd.maps import load_map
 from sigmarl_amd.params import Parameters, make_config
@@ -24,6 +25,9 @@ TRAJ_NAMES = ["cpm16_c2c", "cpm16_mtv", "intersection4_c2c", "onramp6_mtv", "cpm
               "interchange6_mtv", "intersection5_6_testing", "roundabout1_5_c2c", "onramp2_6_mask", "interchange1_8_birdview",
               "onramp2_8_testing_mtv", "interchange2_6_cbf", "cpmmixed2_merge", "intersection8_6_bird_novert",
               "intersection4_full_bird", "intersection4_full_bird_novert", "roundabout6_full_bird_k3", "cpm8_full_bird_pad"]
+# Reference rollouts at the PERTURBED constants of tests/perturbed_constants.py (sigmarl.constants.AGENTS patched in the generator's process, the
+# Parameters-exposed rewards / thresholds passed on; the overrides are recorded in the fixture's meta): every other fixture runs at the reference's defaults.
+TRAJ_NAMES_PERTURBED = ["pert_onramp3_c2c", "pert_cpm8_ttc", "pert_onramp6_mtv", "pert_intersection4_testing", "pert_onramp3_cbf"]
 # The reference rounds the pseudo distance to fp16 and differentiates it numerically (pseudo_distance.py:118, cbf_qp.py:624-644): a
 # one-ulp difference in a float32 circle centre (torch's cos / sin -- a closed vector math library, within 1 ulp of the correctly rounded
 # value the oracle and the HIP path compute and NOT restatable, see include/sigma_trig_f32.h -- ) can flip
@@ -49,6 +53,7 @@ def params_from_meta(meta) -> Parameters:
             "is_obs_noise", "is_apply_mask", "cpm_scenario_probabilities", "is_using_cbf_training", "is_solve_qp", "nom_controller_type", "reset_agent_fixed_duration", "is_obs_steering", "is_observe_ref_path_other_agents",
             "is_observe_vertices", "is_observe_distance_to_agents", "is_observe_distance_to_center_line", "is_ego_view", "is_observe_distance_to_boundaries", "is_using_opponent_modeling", "n_points_short_term", "is_partial_observation", "n_nearing_agents_observed"]
     kw = {k: meta[k] for k in keys if k in meta}
+    kw.update(meta.get("overrides", {}).get("parameters", {}))  # the Parameters-exposed rewards / thresholds the generator passed on (perturbed fixtures only)
     return Parameters(**kw)
 
 
@@ -56,7 +61,20 @@ def config_from_meta(meta, n_envs=None):
     p = params_from_meta(meta)
     mp = load_map(meta["scenario_type"])
     cfg = make_config(p, mp, n_envs if n_envs is not None else meta["B"])
+    agents = meta.get("overrides", {}).get("agents")
+    if agents:  # the generator ran the reference with sigmarl.constants.AGENTS patched: the same vehicle constants, and what the reference derives from them
+        pc.apply_agents(cfg, agents)
     return cfg, mp
+
+
+def cbf_config_from_meta(meta):
+    from sigmarl_amd import cbf
+
+    cc = cbf.make_cbf_config(params_from_meta(meta))
+    agents = meta.get("overrides", {}).get("agents")
+    if agents:  # CBFQP reads l_r, l_wb, the speed / steering minima and the vehicle's size from the patched AGENTS as well (cbf_qp.py:377-398)
+        pc.apply_agents(None, agents, cc)
+    return cc
 
 
 def _state8(pos, rot, speed, steering, vel, sideslip):
@@ -248,9 +266,9 @@ def replay(env, z, meta, mp, steps=None, check_next=True, twin=None) -> Report:
         from sigmarl_amd import cbf
 
         seg_l, seg_r = cbf.load_segment_tables(mp)
-        env.cbf_attach(cbf.make_cbf_config(params_from_meta(meta)), seg_l, seg_r)
+        env.cbf_attach(cbf_config_from_meta(meta), seg_l, seg_r)
         if twin is not None:
-            twin.cbf_attach(cbf.make_cbf_config(params_from_meta(meta)), seg_l, seg_r)
+            twin.cbf_attach(cbf_config_from_meta(meta), seg_l, seg_r)
     for t in range(T):
         if twin is not None:  # the same calls, in the same order
             if with_cbf:

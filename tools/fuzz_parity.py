@@ -62,9 +62,25 @@ def _hip_env_with_tiling(cfg, mp, N, tiling_rng):
                 os.environ[k] = v
 
 
-def one_case(rng, k, tiling_rng=None):
-    """One random configuration.  `tiling_rng` (optional, a second generator) also draws a tiling of the step kernel; without it the function consumes exactly
-    the random numbers it always did, and the library chooses the tiling."""
+# ranges of the Parameters-exposed reward constants (tests/perturbed_constants.py: the default's sign, within about +-40 % of it; lower thresholds a
+# fraction of their upper ones): drawn in a third of the cases when one_case is given a `const_rng`
+CONST_RANGES = {"reward_progress": (0.06, 0.14), "penalty_near_boundary": (-0.28, -0.12), "penalty_near_other_agents": (-0.28, -0.12),
+                "threshold_near_boundary_high": (0.012, 0.028), "threshold_near_other_agents_c2c_high": (0.18, 0.42), "ttc_high": (2.3, 5.2)}
+CONST_LOW_OF = {"threshold_near_boundary_low": "threshold_near_boundary_high", "threshold_near_other_agents_c2c_low": "threshold_near_other_agents_c2c_high",
+                "ttc_low": "ttc_high"}
+
+
+def draw_constants(const_rng):
+    kw = {k: float(const_rng.uniform(lo, hi)) for k, (lo, hi) in CONST_RANGES.items()}
+    for low, high in CONST_LOW_OF.items():
+        kw[low] = float(const_rng.uniform(0.02, 0.25)) * kw[high]
+    return kw
+
+
+def one_case(rng, k, tiling_rng=None, const_rng=None):
+    """One random configuration.  `tiling_rng` (optional, a second generator) also draws a tiling of the step kernel; `const_rng` (optional, a third one) draws,
+    in a third of the cases, the Parameters-exposed reward constants away from their defaults.  Without them the function consumes exactly the random numbers
+    it always did, the library chooses the tiling and the constants are the defaults."""
     scen = MAPS[rng.integers(len(MAPS))]
     mp = load_map(scen)
     n_max = 20 if scen == "cpm_entire" else 6
@@ -89,6 +105,8 @@ def one_case(rng, k, tiling_rng=None):
                     capi.obs_dim(min(kw["n_nearing_agents_observed"], N - 1), obs_flags(Parameters(**kw)), kw["n_points_short_term"], N)
                 except ValueError:
                     kw.update(is_partial_observation=True, n_nearing_agents_observed=2)
+    if const_rng is not None and const_rng.integers(3) == 0:
+        kw.update(draw_constants(const_rng))
     p = Parameters(**kw)
     cfg = make_config(p, mp, B)
     tiling = ""
@@ -112,7 +130,7 @@ def one_case(rng, k, tiling_rng=None):
     seed = int(rng.integers(1 << 30))
     dev.auto_reset(seed, 0, pf, pc)
     ora.auto_reset(seed, 0, pf, pc)
-    tag = f"case {k}: {scen} N={N} B={B} " + (tiling + " " if tiling else "") + " ".join(f"{a}={b}" for a, b in kw.items() if a not in ("n_agents", "scenario_type"))
+    tag = f"case {k}: {scen} N={N} B={B} " + (tiling + " " if tiling else "") + " ".join(f"{a}={b:.4g}" if isinstance(b, float) else f"{a}={b}" for a, b in kw.items() if a not in ("n_agents", "scenario_type"))
     n_diff = tp._compare_all(dev, ora, tag + " | initial reset")
     T = int(rng.integers(8, 40))
     for t in range(T):
@@ -162,10 +180,11 @@ def main():
     ap.add_argument("--seed", type=int, default=0)
     args = ap.parse_args()
     rng = np.random.default_rng(args.seed)
+    const_rng = np.random.default_rng([args.seed, 0xC0257])  # a stream of its own: the cases of a seed are the ones they always were, a third of them at drawn constants
     t0 = time.time()
     k = n_steps = n_diff = 0
     while time.time() - t0 < args.seconds:
-        tag, steps, diff = one_case(rng, k)
+        tag, steps, diff = one_case(rng, k, const_rng=const_rng)
         n_steps += steps
         n_diff += diff
         if diff:
